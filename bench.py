@@ -2,7 +2,12 @@
 """bench.py - MPC horizon-steps/s of the fused closed-loop kernel on BASELINE config 3
 (3-level transmon, n=9, m=2, T=40, n_steps=20, 65,536-member model ensemble per GPU).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--batch B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of its own: the CPU baseline
+(the NumPy oracle on the host cores, `cpu_baseline` in the line).  --dump-outputs DIR writes what the last timed step returned
+(xs, us, exit codes, steps done, QP solve counts of a fixed, seeded sample of members; rank 0's share when N > 1) as
+DIR/<name>.npy in float64.
 
 ONE invocation for any N.  With --gpus N > 1 and no launcher in the environment (WORLD_SIZE unset) this process is only the
 launcher: it never touches the GPU, starts N child processes of this same script - one rank per GPU, RANK / LOCAL_RANK /
@@ -167,6 +172,25 @@ def cpu_baseline(config, p, cores, seconds_budget=20.0, members_per_core=64):
                                         p["horizon"])}
 
 
+DUMP_BYTES = 32 << 20       # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(out_dir, res):
+    """What one step returned to its caller (EnsembleSession.results) as out_dir/<name>.npy in float64: complex arrays with a trailing
+    axis of 2 (real, imaginary), integer counts as exact floats.  Members beyond the byte budget are sampled with a fixed seed
+    (sample_members.npy lists which), so two builds run with the same arguments write comparable files."""
+    import numpy as np
+    B = len(res["exit_codes"])
+    per_member = 8 + sum(v[0].size * (16 if np.iscomplexobj(v) else 8) for v in res.values())
+    k = min(B, max(1, DUMP_BYTES // per_member))
+    members = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, size=k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sample_members.npy"), members.astype(np.float64))
+    for name, v in res.items():
+        a = v[members]
+        np.save(os.path.join(out_dir, name + ".npy"), np.stack([a.real, a.imag], axis=-1) if np.iscomplexobj(a) else a.astype(np.float64))
+
+
 def visible_devices():
     """GPUs a rank of this job could open, counted in a CHILD process (m4q_device_count there): the launcher itself must never
     initialise the GPU (a process that has, and then starts ranks, is what takes these hosts down)."""
@@ -242,7 +266,10 @@ def main():
     ap.add_argument("--config", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None, help="ensemble members per GPU (default: the config's own size)")
     ap.add_argument("--order", type=int, default=1, help="order of the Taylor-truncated model (vectorize.py:8-49); 1 = the BASELINE configs'")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what a plain run leaves out: the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results (a seeded sample of "
+                                                                        "at most %d MB) as DIR/<name>.npy" % (DUMP_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) leave the CPU baseline out")
     ap.add_argument("--cpu-cores", type=int, default=0, help="host cores for the CPU baseline (0 = all this job may use: affinity "
                                                              "mask cut to the cgroup CPU quota)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="time budget of every CPU-baseline worker")
@@ -291,7 +318,7 @@ def main():
     # The CPU baseline runs FIRST: its worker processes are started, and have ended, before this process loads the HIP library
     # or makes its first HIP call (they need nothing from the GPU run; a process that holds a GPU context starts no children).
     cpu_base = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if world == 1 and rank == 0 and args.full and not args.no_cpu_baseline:
         cpu_base = cpu_baseline(args.config, p, args.cpu_cores or usable_cores(), args.cpu_seconds)
     P = _lib.lib().m4q_library_size(p["order"], m)
     per_model = p["scales"] is not None
@@ -355,6 +382,8 @@ def main():
     if os.environ.get("M4Q_PHASE_TRACE"):
         sess.qp_stats()              # development builds (-DM4Q_DEV_PHASE_CLOCK): prints the wavefront time per phase of the main loop
     res = sess.results()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     units_per_step = int(res["qp_solves"].astype(np.int64).sum()) * T
     ok = int((res["exit_codes"] == 0).sum())
     code_hist = [int((res["exit_codes"] == c).sum()) for c in range(4)]     # members by exit code (mpc.py:130): 0 done, 1 exit_condition,
@@ -451,7 +480,7 @@ def main():
                                          else "FETCH_SIZE/WRITE_SIZE of profiles/r05_pmc.json, taken on this binary (launch time "
                                                 "within 3 %): L2-miss bytes per launch, mostly served by the Infinity Cache"},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_base
         print(json.dumps(out))
     if multi:

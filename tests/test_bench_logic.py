@@ -1,4 +1,5 @@
-"""Host-side logic of bench.py that needs no GPU: the roofline inputs, the staleness rule for counter records, the CPU share."""
+"""Host-side logic of bench.py that needs no GPU: the roofline inputs, the staleness rule for counter records, the CPU share,
+the output dump."""
 import importlib.util
 import json
 import os
@@ -78,6 +79,35 @@ def test_usable_cores_is_positive_and_bounded():
     n = b.usable_cores()
     assert 1 <= n <= len(os.sched_getaffinity(0))
 
+
+
+def test_dump_outputs_writes_a_seeded_sample_in_float64(tmp_path, monkeypatch):
+    """--dump-outputs: every array a step returns, complex as a trailing (real, imaginary) axis, integers as floats; past the byte
+    budget a fixed, seeded sample of members, the same in every run."""
+    import numpy as np
+    b = _bench()
+    B, ns, n, m = 1000, 3, 4, 2
+    rng = np.random.default_rng(7)
+    res = {"xs": rng.standard_normal((B, ns + 1, n)) + 1j * rng.standard_normal((B, ns + 1, n)), "us": rng.standard_normal((B, ns, m)),
+           "exit_codes": rng.integers(0, 4, B).astype(np.int32), "steps_done": np.full(B, ns, np.int32),
+           "qp_solves": rng.integers(1, 5, (B, ns)).astype(np.int32)}
+    b.dump_outputs(str(tmp_path / "all"), res)                          # within the budget: every member, in order
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in list(res) + ["sample_members"]}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["sample_members"], np.arange(B)) and np.array_equal(got["qp_solves"], res["qp_solves"])
+    assert np.array_equal(got["xs"][..., 0], res["xs"].real) and np.array_equal(got["xs"][..., 1], res["xs"].imag)
+    monkeypatch.setattr(b, "DUMP_BYTES", 100 * 1024)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), res)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(k + ".npy" for k in got) and names == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 100 * 1024 + 128 * len(names)
+    idx = np.load(tmp_path / "a" / "sample_members.npy").astype(np.int64)
+    assert 0 < len(idx) < B and np.all(np.diff(idx) > 0)
+    for f in names:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    assert np.array_equal(np.load(tmp_path / "a" / "us.npy"), res["us"][idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "exit_codes.npy"), res["exit_codes"][idx])
 
 # ---- the launcher: `bench.py --gpus N` starts N ranks itself (VERDICT r3 item 1) ---------------------------------------------
 def _run_bench(*argv, env=None, timeout=120):

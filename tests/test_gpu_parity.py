@@ -1842,13 +1842,14 @@ print("rank %%d ok" %% rank)
 
 
 def test_bench_line_schema():
-    """bench.py prints ONE JSON line with the driver's contract fields, the roofline of the dominant kernel and the CPU baseline."""
+    """bench.py --full prints ONE JSON line with the driver's contract fields, the roofline of the dominant kernel and the CPU
+    baseline."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "512", "--cpu-cores",
-                          "2", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600, cwd=root)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "512",
+                          "--cpu-cores", "2", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -1867,6 +1868,30 @@ def test_bench_line_schema():
     assert abs(d["value"] - d["config"]["qp_solves_per_step"] * d["config"]["horizon"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 2 and c["value"] > 0 and c["unit"] == d["unit"] and "sample" in c
+
+
+def test_bench_plain_run_dumps_what_its_last_step_returned(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and leaves the CPU baseline out; --dump-outputs writes the
+    last timed step's results as float64 .npy files that agree with the line it printed."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "512",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert "cpu_baseline" not in d and d["steps"] == 3 and d["ms_per_step"] > 0 and d["roofline"]["launches"] == 3
+    got = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert sorted(got) == ["exit_codes", "qp_solves", "sample_members", "steps_done", "us", "xs"]
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    c = d["config"]
+    assert np.array_equal(got["sample_members"], np.arange(512))
+    assert got["xs"].shape == (512, c["n_steps"] + 1, 9, 2) and got["us"].shape == (512, c["n_steps"], 2)
+    assert int(got["qp_solves"].sum()) == c["qp_solves_per_step"] and int((got["exit_codes"] == 0).sum()) == c["instances_ok"] == 512
+    assert np.all(got["steps_done"] == c["n_steps"]) and np.abs(got["us"]).max() > 0
 
 
 def test_bench_gpus_flag_on_a_one_gpu_box():

@@ -9,10 +9,12 @@
 tag=${1:?tag}
 export TMPDIR=/tmp
 mkdir -p gpurun_out/$tag
+out=$_          # the records folder the line above made; every record of this call goes there
+[ -d "$out" ] && [ "${out##*/}" = "$tag" ] || { echo "final_records.sh: records folder not found ('$out')" >&2; exit 1; }
 if [ "$2" = pmc ]; then tools/pmc_all.sh $tag; exit; fi
-python bench.py > gpurun_out/$tag/bench_default.json 2> gpurun_out/$tag/bench_default.err; echo "bench rc=$?"; tail -c 600 gpurun_out/$tag/bench_default.json
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$tag/trace_bench -- python3 bench.py --no-cpu-baseline > gpurun_out/$tag/trace_bench.log 2>&1; echo "trace rc=$?"
-find gpurun_out/$tag/trace_bench -name "*kernel_stats.csv" -exec cp {} gpurun_out/$tag/kernel_stats_bench_default.csv \;
-rm -rf gpurun_out/$tag/trace_bench
-tools/all_configs.sh > gpurun_out/$tag/all_configs.txt 2>&1; cat gpurun_out/$tag/all_configs.txt
-timeout -k 10 420 python3 tools/soak.py --minutes 5 > gpurun_out/$tag/soak.txt 2>&1; echo "soak rc=$?"; tail -n 3 gpurun_out/$tag/soak.txt
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"; tail -c 600 $out/bench_default.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_bench -- python3 bench.py > $out/trace_bench.log 2>&1; echo "trace rc=$?"
+find $out/trace_bench -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats_bench_default.csv \;
+rm -rf $out/trace_bench
+tools/all_configs.sh > $out/all_configs.txt 2>&1; cat $out/all_configs.txt
+timeout -k 10 420 python3 tools/soak.py --minutes 5 > $out/soak.txt 2>&1; echo "soak rc=$?"; tail -n 3 $out/soak.txt
