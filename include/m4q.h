@@ -56,6 +56,11 @@ extern "C" {
 #define M4Q_PLANT_NONE 0        /* caller supplies xs[step+1] between m4q_session_run calls */
 #define M4Q_PLANT_HAMILTONIAN 1 /* rho+ = U rho U^H, U = expm(-i dt (H0 + sum_k u_k H_k)), d x d operators */
 #define M4Q_PLANT_GENERATOR 2   /* x+ = expm(dt (L0 + sum_k u_k L_k)) x, n x n operators */
+/* gate synthesis (experiment.py:336-417, QSynthesis): x = vec_r(M) is the process vector of a d x d unitary, M = U (x) U^* a
+ * d^2 x d^2 matrix, n = d^4 (a qubit gate: d = 2, n = 16).  x+ = vec_r((V (x) V^*) M), V = expm(-i dt (H0 + sum_k u_k H_k)), d x d
+ * operators.  The loop state is the process vector itself (no lift).  Sessions with this plant always run the complex path
+ * (m4q_session_path 0): V (x) V^* does not keep M Hermitian.  M4Q_E_BADARG if n is not a fourth power. */
+#define M4Q_PLANT_PROCESS 3
 
 /* options (m4q_problem.reserved).  By default a session whose model, states, targets and costs are real in a
  * Hermitian operator basis (every vectorised-Liouvillian model and Hermitian state is) runs the closed loop in
@@ -94,9 +99,11 @@ extern "C" {
  * A non-zero code ends that member's run at the step where it occurred: steps_done says how many steps are valid. */
 
 typedef struct m4q_problem {
-  int32_t dim_x;   /* n = d*d: 4, 9 or 16; also 8 (two reduced qubit states, experiment.py:238-306) with M4Q_PLANT_NONE */
+  int32_t dim_x;   /* n = d*d: 4, 9 or 16; also 8 (two reduced qubit states, experiment.py:238-306) with M4Q_PLANT_NONE;
+                      n = d^4 = 16 with M4Q_PLANT_PROCESS */
   int32_t dim_u;   /* m */
-  int32_t order;   /* control-library order (1 or 2) */
+  int32_t order;   /* control-library order (1 or 2; 1-4 for (16, 1): models of orders 3-4 are uploaded, m4q_session_build_models
+                      and m4q_discretize_batch refuse them) */
   int32_t horizon; /* T (StepClock.horizon, mpc.py:17) */
   int32_t n_steps; /* StepClock.n_steps (mpc.py:18) */
   int32_t max_iter;   /* SQP iteration cap per MPC step (mpc.py:128, default 100) */
@@ -159,7 +166,8 @@ M4Q_API int m4q_discretize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
                          int32_t gen_per_instance, const double* scales, double* models);
 
 /* replaces QExperiment.simulate over one held-control step (experiment.py:202-212, mpc.py:256-260).
- * x [B][n] c, u [B][m] r, op0 [B|1][k][k] c, ops [B|1][m][k][k] c with k = d (HAMILTONIAN) or n (GENERATOR)
+ * x [B][n] c, u [B][m] r, op0 [B|1][k][k] c, ops [B|1][m][k][k] c with k = d (HAMILTONIAN, n = d^2), n (GENERATOR) or
+ * d (PROCESS, n = d^4)
  * -> x_next [B][n] c */
 M4Q_API int m4q_plant_step_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, double dt, const double* x,
                          const double* u, const double* op0, const double* ops, int32_t plant_per_instance,

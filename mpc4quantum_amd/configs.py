@@ -144,3 +144,37 @@ def build(config, batch=None, order=1, horizon=None, n_steps=None, offset=0, tot
                 du=du, Q=Qm, R=R, Qf=Qm.copy(), x0=np.ascontiguousarray(x0),
                 models=None if models is None else np.ascontiguousarray(models), generators=gens, scales=scales,
                 X_targ=X_targ, U_targ=U_targ, plant_op0=plant0, plant_ops=plantk, batch=B)
+
+
+def synthesis(batch=1, order=1, detuning_spread=0.0, horizon=15, n_steps=50, seed=7):
+    """NOT-gate synthesis ensemble (the reference's TestGateSynth.test_NOT_gate, tests/test_mpc4quantum.py:47-145): MPC on the
+    process vector P = vec_r(U (x) U^*) of a single qubit (n = 16, one drive), dt 0.05, T 15, 50 steps, sat 1, du 0.25,
+    Q = I_16, Qf = 10 Q, R = 1e-2, P0 from Rx(1e-3), target sigma_x (x) sigma_x^*, U_bm = 0.5.
+    The qubit is RWA_Qubit(wQ = wD = wR = pi) (util_qubits.py:61-79): H0 = 0, H1 = sigma_x / 2.  Member b's plant is detuned,
+    H0_b = delta_b sigma_z / 2 with delta_b = detuning_spread * N(0, 1) (seeded); every member shares the nominal model discretize_homogeneous([L_k (x) I_4]), L_k = -i (H_k (x) I - I (x) H_k^*).
+    Not a numbered configuration: bench.py does not run it (tools/synthesis_bench.py does).
+    Returns the keys of build() with plant_kind = PLANT_PROCESS, plant_op0 [B, 2, 2], plant_ops [1, 1, 2, 2], detunings [B]."""
+    from ._lib import PLANT_PROCESS
+    B = int(batch)
+    d, m, n = 2, 1, 16
+    dt, sat, du = 0.05, 1.0, 0.25
+    T, ns = horizon, n_steps
+    H_model = [0.0 * SZ, 0.5 * SX]
+    eye = np.identity(d)
+    gens = np.stack([np.kron(-1j * (np.kron(h, eye) - np.kron(eye, h.conj())), np.identity(d * d)) for h in H_model])
+    models = discretize_homogeneous(list(gens), dt, order)[None]
+    rng = np.random.default_rng(seed)
+    delta = detuning_spread * rng.standard_normal(B)
+    plant0 = 0.5 * delta[:, None, None] * SZ[None]
+    plantk = np.stack([H_model[1]])[None]
+    U0 = rx(1e-3)
+    x0 = np.tile(np.kron(U0, U0.conj()).reshape(1, -1), (B, 1))
+    target = np.kron(SX, SX.conj()).reshape(-1)
+    cols = ns + T + 1
+    X_targ = np.tile(target.reshape(-1, 1), (1, cols))
+    U_targ = 0.5 * np.ones((m, cols - 1))
+    Qm = np.identity(n)
+    return dict(name="synthesis", dim_x=n, dim_u=m, d=d, order=order, dt=dt, horizon=T, n_steps=ns, sat=sat, du=du, Q=Qm,
+                R=1e-2 * np.identity(m), Qf=10 * Qm, x0=np.ascontiguousarray(x0), models=np.ascontiguousarray(models),
+                generators=gens, scales=None, X_targ=X_targ, U_targ=U_targ, plant_op0=plant0, plant_ops=plantk, batch=B,
+                plant_kind=PLANT_PROCESS, detunings=delta, target=target)

@@ -115,6 +115,16 @@ const m4q::ShapeOps* gen_shape(int nx, int nu, int order, std::string& why) {
 }
 
 int dim_d(int nx) { return nx == 4 ? 2 : nx == 9 ? 3 : nx == 16 ? 4 : 0; }
+// d with d^4 = nx (M4Q_PLANT_PROCESS: the process vector of a d x d unitary), 0 if nx is not a fourth power
+int dim_q(int nx) {
+  for (int d = 1; d * d * d * d <= nx; ++d)
+    if (d * d * d * d == nx) return d;
+  return 0;
+}
+// side of the plant operators: n (GENERATOR), d with d^4 = n (PROCESS), d with d^2 = n (HAMILTONIAN)
+size_t plant_dim(int kind, int nx) {
+  return kind == M4Q_PLANT_GENERATOR ? (size_t)nx : kind == M4Q_PLANT_PROCESS ? (size_t)dim_q(nx) : (size_t)dim_d(nx);
+}
 
 struct DevBuf {
   void* p = nullptr;
@@ -370,10 +380,13 @@ int m4q_session_create(const m4q_problem* p, int32_t B, int32_t device, m4q_sess
     return fail(M4Q_E_BADARG, "qp_flags has bits outside M4Q_QP_REF_LQR | M4Q_QP_DU_BAND | M4Q_QP_EXACT_BOX (0x%x)", p->qp_flags);
   if ((p->qp_flags & M4Q_QP_EXACT_BOX) && (p->qp_flags & M4Q_QP_REF_LQR))
     return fail(M4Q_E_BADARG, "M4Q_QP_EXACT_BOX cannot be combined with M4Q_QP_REF_LQR");
+  if (p->plant_kind == M4Q_PLANT_PROCESS && dim_q(p->dim_x) == 0)
+    return fail(M4Q_E_BADARG, "M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power (the process vector of a d x d unitary has d^4 entries)",
+                p->dim_x);
   {
     // per-instance targets / plant operators are reached through 32-bit byte offsets from one base
     const double lim = 4294967296.0;
-    const double kk = p->plant_kind == M4Q_PLANT_GENERATOR ? p->dim_x : dim_d(p->dim_x);
+    const double kk = (double)plant_dim(p->plant_kind, p->dim_x);
     if (p->target_per_instance && (double)B * p->target_cols * p->dim_x * 16.0 >= lim)
       return fail(M4Q_E_BADARG, "per-instance targets must stay below 4 GiB in total");
     if (p->plant_per_instance && (double)B * p->dim_u * kk * kk * 16.0 >= lim)
@@ -396,7 +409,10 @@ int m4q_session_create(const m4q_problem* p, int32_t B, int32_t device, m4q_sess
       return fail(M4Q_E_UNSUPPORTED, "%s", why.c_str());
     }
   }
-  s->force_complex = (p->reserved & 1) != 0 || std::getenv("M4Q_FORCE_COMPLEX") != nullptr || sh->d * sh->d != p->dim_x;
+  // (a process plant runs on the complex path alone: V (x) V^* does not keep M Hermitian as a d^2 x d^2 matrix, so the Hermitian lift
+  // of data that happens to pass it would still be wrong after the first plant step)
+  s->force_complex = (p->reserved & 1) != 0 || std::getenv("M4Q_FORCE_COMPLEX") != nullptr || sh->d * sh->d != p->dim_x ||
+                     p->plant_kind == M4Q_PLANT_PROCESS;
   // (M4Q_QP_REF_LQR builds its cost terms on xbar itself, lqr.py:54-58: the trace coordinate of the target does not drop out)
   s->no_traceless = (p->reserved & M4Q_OPT_NO_TRACELESS) != 0 || std::getenv("M4Q_NO_TRACELESS") != nullptr ||
                     (p->qp_flags & M4Q_QP_REF_LQR) != 0;
@@ -409,7 +425,7 @@ int m4q_session_create(const m4q_problem* p, int32_t B, int32_t device, m4q_sess
   HIP_TRY_OWNED(s, hipEventCreate(&s->ev0));
   HIP_TRY_OWNED(s, hipEventCreate(&s->ev1));
   const size_t n = p->dim_x, m = p->dim_u, P = sh->np, T = p->horizon, ns = p->n_steps, cols = p->target_cols;
-  const size_t k = p->plant_kind == M4Q_PLANT_GENERATOR ? n : (size_t)sh->d;
+  const size_t k = plant_dim(p->plant_kind, p->dim_x);
   const size_t C = 16;
   size_t* fb = s->fbytes;
   fb[M4Q_F_MODELS] = (p->model_per_instance ? B : 1) * n * n * (1 + P) * C;
@@ -706,7 +722,7 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   if (rc) return rc;
   const m4q_problem& p = s->prob;
   const size_t n = p.dim_x, m = p.dim_u, P = s->shape->np;
-  const size_t k = p.plant_kind == M4Q_PLANT_GENERATOR ? n : (size_t)s->shape->d;
+  const size_t k = plant_dim(p.plant_kind, p.dim_x);
   const int path = s->path();
   const bool real_path = path != 0;
   const size_t ns = path >= 2 ? n - 1 : n;         // dimension of the recursion
@@ -989,6 +1005,9 @@ int m4q_discretize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order,
   const m4q::ShapeOps* sh = find_shape(dim_x, dim_u, order);
   if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d order=%d", dim_x, dim_u, order);
   if (B <= 0 || !generators || !models) return fail(M4Q_E_BADARG, "m4q_discretize_batch: bad argument");
+  if (order > 2)
+    return fail(M4Q_E_UNSUPPORTED, "m4q_discretize_batch: the device discretisation covers orders 1 and 2 (order %d: use the host "
+                "discretize_homogeneous and upload the models)", order);
   int rc = need_device();
   if (rc) return rc;
   const size_t n = dim_x, m = dim_u, P = sh->np, C = 16;
@@ -1011,6 +1030,9 @@ int m4q_session_build_models(m4q_session* s, double dt, const double* generators
                              const double* scales) {
   if (!s || !generators) return fail(M4Q_E_BADARG, "m4q_session_build_models: bad argument");
   const m4q_problem& p = s->prob;
+  if (p.order > 2)
+    return fail(M4Q_E_UNSUPPORTED, "m4q_session_build_models: the device discretisation covers orders 1 and 2 (order %d: build the "
+                "models with the host discretize_homogeneous and upload them)", p.order);
   const size_t n = p.dim_x, m = p.dim_u, P = s->shape->np, C = 16;
   const size_t nset = gen_per_instance ? (size_t)s->B : 1;
   const size_t nmodels = p.model_per_instance ? (size_t)s->B : 1;
@@ -1098,12 +1120,15 @@ int m4q_plant_step_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_
                          double* x_next) {
   const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
   if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d", dim_x, dim_u);
-  if (B <= 0 || !x || !u || !op0 || !ops || !x_next || (plant_kind != M4Q_PLANT_HAMILTONIAN && plant_kind != M4Q_PLANT_GENERATOR))
+  if (B <= 0 || !x || !u || !op0 || !ops || !x_next ||
+      (plant_kind != M4Q_PLANT_HAMILTONIAN && plant_kind != M4Q_PLANT_GENERATOR && plant_kind != M4Q_PLANT_PROCESS))
     return fail(M4Q_E_BADARG, "m4q_plant_step_batch: bad argument");
+  if (plant_kind == M4Q_PLANT_PROCESS && dim_q(dim_x) == 0)
+    return fail(M4Q_E_BADARG, "M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", dim_x);
   int rc = need_device();
   if (rc) return rc;
   const size_t n = dim_x, m = dim_u, C = 16;
-  const size_t k = plant_kind == M4Q_PLANT_GENERATOR ? n : (size_t)sh->d;
+  const size_t k = plant_dim(plant_kind, dim_x);
   Tmp t;
   m4q::PlantArgs a{};
   a.B = B; a.kind = plant_kind; a.dt = dt;

@@ -33,6 +33,10 @@ constexpr int ORDER = M4Q_ORDER;
 // experiment.py:238-306) has no device plant and no Hermitian-basis path: only the complex QP machinery is built.
 constexpr int DD = (NX == 4) ? 2 : (NX == 9) ? 3 : (NX == 16) ? 4 : 1;
 constexpr bool SQUARE = DD * DD == NX;
+// n = d^4: a process vector vec_r(U (x) U^*) of a d x d unitary (gate synthesis, QSynthesis).  The process plant is built on the
+// complex path alone: V (x) V^* acting on M does not keep M Hermitian as a d^2 x d^2 matrix, so no Hermitian-basis path applies.
+constexpr int DQ = fourth_root(NX);
+constexpr bool QUARTIC = DQ > 0;
 constexpr int NP = PowTab<NU, ORDER>::NP;
 constexpr int PITCH = ModelPitch<NX>::value;
 constexpr int MODEL_ELEMS = (1 + NP) * NX * PITCH;        // per instance, elements (of S) in LDS
@@ -1012,6 +1016,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
             for (int k = 0; k < NU; ++k)
               ui[k] = (i == 0 || !(ok && measure)) ? uapp[k] : gld(a->us, b * sUs + (long)(step - i) * NU + k);
             if constexpr (PLANT == PLANT_HAMILTONIAN) xc = plant_hamiltonian<NX, NU, DD>(xc, ui, op0, ops, dt, scratch, jio, jj);
+            else if constexpr (PLANT == PLANT_PROCESS) xc = plant_process<NX, NU, DQ>(xc, ui, op0, ops, dt, scratch, jio, jj);
             else xc = plant_generator<NX, NU>(xc, ui, op0, ops, dt, jio);
           }
           xn = xc;
@@ -1325,6 +1330,8 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_kernel(PlantArgs a) {
     cplx xn;
     if constexpr (PLANT == PLANT_HAMILTONIAN)
       xn = plant_hamiltonian<NX, NU, DD>(x, u, op0, ops, a.dt, scratch, j, jj);
+    else if constexpr (PLANT == PLANT_PROCESS)
+      xn = plant_process<NX, NU, DQ>(x, u, op0, ops, a.dt, scratch, j, jj);
     else
       xn = plant_generator<NX, NU>(x, u, op0, ops, a.dt, j);
     if (valid && jj < NX) gst(a.x_next, b * NX + j, xn);
@@ -1482,6 +1489,11 @@ static int pick_plant(const Op& op, int plant_kind) {
 #else
     if (plant_kind == PLANT_HAMILTONIAN) return op.template run<S, PLANT_HAMILTONIAN, EXACT, TL, TILE, SG>();
     if (plant_kind == PLANT_GENERATOR) return op.unsupported();          // (libm4q_hip_gen.so: the host routes such sessions there)
+    if (plant_kind == PLANT_PROCESS) {
+      // the complex path alone (the host forces it for a process plant: m4q_session_create)
+      if constexpr (QUARTIC && std::is_same<S, cplx>::value && !TL && !TILE && !SG) return op.template run<S, PLANT_PROCESS, EXACT, false, false>();
+      else return op.unsupported();
+    }
     return op.template run<S, PLANT_NONE, EXACT, TL, TILE, SG>();
 #endif
   }
@@ -1555,7 +1567,10 @@ static int launch_plant(const PlantArgs& a, hipStream_t s) {
   const size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
   if (a.kind == PLANT_HAMILTONIAN)
     hipLaunchKernelGGL(plant_kernel<PLANT_HAMILTONIAN>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
-  else
+  else if (a.kind == PLANT_PROCESS) {
+    if constexpr (QUARTIC) hipLaunchKernelGGL(plant_kernel<PLANT_PROCESS>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
+    else return -(int)hipErrorInvalidValue;
+  } else
     hipLaunchKernelGGL(plant_kernel<PLANT_GENERATOR>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
   return -(int)hipGetLastError();
   }
@@ -1565,8 +1580,9 @@ static int launch_plant(const PlantArgs& a, hipStream_t s) {
 static int launch_plant(const PlantArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
 #endif
 
-#ifndef M4Q_NO_AUX
+#if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
 // path: 0 complex generators, 1 real n x n (lifted to the Hermitian basis), 2 real (n-1) x (n-1) (their traceless blocks)
+// (orders 3 and 4 have closed-loop kernels but no device discretisation: their models come from the host, discretize_homogeneous)
 static int launch_discretize(const DiscArgs& a, int path, hipStream_t s) {
   if (!SQUARE && path) return -(int)hipErrorInvalidValue;
   const size_t elems = (size_t)ROWS * (1 + NU) * NX * NX;

@@ -2276,7 +2276,14 @@ __device__ __forceinline__ void expm_cols(cplx (&A)[N], int j) {
 }
 
 // Plant kinds (mirrored in include/m4q.h)
-enum : int { PLANT_NONE = 0, PLANT_HAMILTONIAN = 1, PLANT_GENERATOR = 2 };
+enum : int { PLANT_NONE = 0, PLANT_HAMILTONIAN = 1, PLANT_GENERATOR = 2, PLANT_PROCESS = 3 };
+
+// d with d^4 = n (the process plant's operator dimension), 0 if n is not a fourth power
+constexpr int fourth_root(int n) {
+  for (int d = 1; d * d * d * d <= n; ++d)
+    if (d * d * d * d == n) return d;
+  return 0;
+}
 
 // rho+ = U rho U^H with U = expm(-i dt (H0 + sum_k u_k H_k)); x = vec_r(rho)  (experiment.py:190-212).
 // sc: per-instance LDS scratch of at least D*D + 2*NX complex.  One wave per block: __syncthreads
@@ -2313,6 +2320,49 @@ __device__ __forceinline__ cplx plant_hamiltonian(cplx x, const double (&u)[NU],
   cplx out = czero();
 #pragma unroll
   for (int c = 0; c < D; ++c) cmac_cj(out, Us[e * D + c], Ms[a * D + c]); // sum_c (U rho)[a][c] conj(U[e][c])
+  wave_sync();
+  return out;
+}
+
+// Gate synthesis (experiment.py:336-417, QSynthesis): the state is the process vector x = vec_r(M), M = U (x) U^* a d^2 x d^2
+// matrix (n = d^4), and one held-control step is M+ = (V (x) V^*) M with V = expm(-i dt (H0 + sum_k u_k H_k)), d x d operators.
+// Column c of M is vec_r of a d x d matrix rho_c, and (V (x) V^*) vec_r(rho_c) = vec_r(V rho_c V^H): every column takes one
+// Hamiltonian-plant step.  Lane j holds M[r][c] (r = j / d^2, c = j % d^2) with r = a d + e, i.e. rho_c[a][e].
+// sc: per-instance LDS scratch of at least D*D + 2*NX complex (SCRATCH_ELEMS of a square NX).
+template <int NX, int NU, int D>
+__device__ __forceinline__ cplx plant_process(cplx x, const double (&u)[NU], const GView& H0, const GView& Hk, double dt,
+                                              cplx* sc, int j, int jj) {
+  static_assert(D * D * D * D == NX, "state is the process vector of a d x d unitary");
+  constexpr int D2 = D * D;
+  const int jc = j < D ? j : D - 1;
+  cplx G[D];
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    cplx hsum = H0.ld<cplx>(i * D + jc);
+#pragma unroll
+    for (int k = 0; k < NU; ++k) cmac_r(hsum, Hk.ld<cplx>((k * D + i) * D + jc), u[k]);
+    G[i] = mk(hsum.im * dt, -hsum.re * dt);              // -i dt H
+  }
+  expm_cols<D>(G, jc);
+  cplx* Vs = sc;             // [D][D]
+  cplx* xs = sc + D * D;     // [NX]
+  cplx* Ms = xs + NX;        // [NX]
+  if (jj < D) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) Vs[a * D + jj] = G[a];
+  }
+  if (jj < NX) xs[jj] = x;
+  wave_sync();
+  const int r = j / D2, c = j - (j / D2) * D2;
+  const int a = r / D, e = r - (r / D) * D;
+  cplx m = czero();
+#pragma unroll
+  for (int q = 0; q < D; ++q) cmac(m, Vs[a * D + q], xs[(q * D + e) * D2 + c]);      // (V rho_c)[a][e]
+  if (jj < NX) Ms[jj] = m;
+  wave_sync();
+  cplx out = czero();
+#pragma unroll
+  for (int q = 0; q < D; ++q) cmac_cj(out, Vs[e * D + q], Ms[(a * D + q) * D2 + c]); // sum_q (V rho_c)[a][q] conj(V[e][q])
   wave_sync();
   return out;
 }

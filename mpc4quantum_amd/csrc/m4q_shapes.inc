@@ -3,11 +3,18 @@
 // under two controls of the reference's crosstalk scenario (tests/test_mpc4quantum.py:281-397) is stepped by the host-side
 // QCoupledExperiment, its closed loop runs on the reduced (8, 2, 1) model; the 21 closed-loop kernels of (16, 2, 1) were 3.3 MB
 // nobody could launch.
+// (16, 1, 1-4): a single-qubit gate's process vector (n = 2^4, one drive; the reference's TestGateSynth.test_NOT_gate,
+// tests/test_mpc4quantum.py:47-145, loops over orders 1-4) - also a d = 4 density matrix under one drive.  Orders 3 and 4 have no
+// device discretisation (discretize_kernel: orders 1-2): their models come from the host.
 M4Q_SHAPE(4, 1, 1)
 M4Q_SHAPE(4, 1, 2)
 M4Q_SHAPE(4, 2, 1)
 M4Q_SHAPE(9, 2, 1)
 M4Q_SHAPE(9, 2, 2)
 M4Q_SHAPE(16, 3, 1)
+M4Q_SHAPE(16, 1, 1)
+M4Q_SHAPE(16, 1, 2)
+M4Q_SHAPE(16, 1, 3)
+M4Q_SHAPE(16, 1, 4)
 M4Q_SHAPE(8, 2, 1)
 M4Q_SHAPE(16, 2, 1)   // plant-only

@@ -2,7 +2,9 @@
 simulate).  `QExperiment` is the state-preparation plant of experiment.py:175-212 with the ODE
   d rho/dt = -i [H0 + sum_k u_k(t) H_k, rho]
 solved exactly over each held-control interval by the HIP Pade-13 kernel (m4q_plant_step_batch)
-instead of qutip.mesolve.  `mpc()` recognises it and keeps the whole closed loop on the GPU."""
+instead of qutip.mesolve.  `mpc()` recognises it and keeps the whole closed loop on the GPU.
+`QSynthesis` is the gate-synthesis plant of experiment.py:336-417: its state is the process vector vec_r(U (x) U^*), stepped
+exactly by the same kernel family (M4Q_PLANT_PROCESS) instead of qutip.propagator."""
 from abc import ABC, abstractmethod
 
 import numpy as np
@@ -38,14 +40,23 @@ def _as_array(op):
 
 
 def plant_step_batch(x, u, op0, ops, dt, kind=_lib.PLANT_HAMILTONIAN):
-    """x [B,n], u [B,m], op0 [B|1,k,k] (or [k,k]), ops [B|1,m,k,k] (or [m,k,k]) -> x_next [B,n]."""
+    """x [B,n], u [B,m], op0 [B|1,k,k] (or [k,k]), ops [B|1,m,k,k] (or [m,k,k]) -> x_next [B,n].
+    k = d for HAMILTONIAN (n = d^2) and PROCESS (n = d^4), n for GENERATOR."""
     x = np.ascontiguousarray(x, dtype=np.complex128)
     u = np.ascontiguousarray(u, dtype=np.float64)
     Bn, n = x.shape
     m = u.shape[1]
     op0 = np.ascontiguousarray(op0, dtype=np.complex128)
     ops = np.ascontiguousarray(ops, dtype=np.complex128)
+    if int(kind) == _lib.PLANT_PROCESS:
+        d = process_dim(n)
+        if op0.shape[-2:] != (d, d) or ops.shape[-3:] != (m, d, d) or op0.ndim not in (2, 3) or ops.ndim not in (3, 4):
+            raise ValueError("process plant of n = %d = %d^4: op0 must be [B|1, %d, %d] and ops [B|1, %d, %d, %d], got %s and %s"
+                             % (n, d, d, d, m, d, d, op0.shape, ops.shape))
     per = 1 if (op0.ndim == 3 and op0.shape[0] > 1) else 0
+    if per and (ops.ndim == 3 or ops.shape[0] == 1):
+        # per-member op0 with one shared set of control operators: the kernel reads both with the member's stride
+        ops = np.ascontiguousarray(np.broadcast_to(ops.reshape((-1,) + ops.shape[-3:])[:1], (Bn,) + ops.shape[-3:]))
     out = np.empty_like(x)
     L = _lib.lib()
     _lib.check(L.m4q_plant_step_batch(Bn, n, m, int(kind), float(dt), _lib.cbuf(x)[1], _lib.rbuf(u)[1], _lib.cbuf(op0)[1],
@@ -150,6 +161,92 @@ class LExperiment(QExperiment):
             u = np.reshape(us(ts[i]) if callable(us) else np.atleast_2d(us)[:, i], -1)[:m]
             x = plant_step_batch(x[None], np.real(u)[None], self.H0, np.stack(self.H1_list), ts[i + 1] - ts[i],
                                  _lib.PLANT_GENERATOR)[0]
+            cols.append(x)
+        self.ts, self.us = ts, us
+        self.xs = np.stack(cols, axis=1)
+        return self.xs
+
+
+def process_dim(n):
+    """d with d^4 = n: the unitary dimension of a process vector of length n (ValueError otherwise)."""
+    n = int(n)
+    d = int(round(n ** 0.25))
+    if d < 1 or d ** 4 != n:
+        raise ValueError("a process vector has d^4 entries; %d is not a fourth power" % n)
+    return d
+
+
+class QSynthesis(Experiment):
+    """Gate-synthesis plant (experiment.py:336-417): H0 and H1_list are d x d Hermitian (ndarray or qutip.Qobj).
+
+    The loop state is the process vector P = vec_r(U (x) U^*) (n = d^4), and mpc() does NOT lift it: the lift in the loop is the
+    identity (difference 4 - the reference's QSynthesis cannot drive its own mpc.py, whose lift of a process vector
+    has d^8 entries).  `lift(U)` / `proj(P)` keep the reference's meaning (U <-> U (x) U^*, proj up to a global phase) as helpers.
+    simulate() steps the process vector itself, exactly over each held-control interval (M4Q_PLANT_PROCESS):
+    P+ = vec_r((V (x) V^*) M), V = expm(-i dt (H0 + sum_k u_k H_k)) - qutip.propagator's U(t) applied to the state, without it."""
+
+    plant_kind = _lib.PLANT_PROCESS
+
+    def __init__(self, H0, H1_list):
+        super().__init__()
+        self.H0 = _as_array(H0)
+        self.H1_list = [_as_array(h) for h in H1_list]
+        self._prop_args = {}
+
+    def set(self, key, value):
+        """Keyword argument of the reference's propagator call (experiment.py:354-358): kept and ignored, as QExperiment keeps
+        the integrator's options - except 'c_ops': open-system process maps are not a unitary's process vector."""
+        if key == "c_ops" and value is not None and len(value):
+            raise ValueError("QSynthesis: collapse operators (c_ops) are not supported - the process plant propagates a unitary's "
+                             "process vector U (x) U^*; open-system process maps are out of scope")
+        self._prop_args[key] = value
+
+    def operators(self):
+        """(op0, ops) for the device plant: the d x d Hamiltonians."""
+        return self.H0, np.stack(self.H1_list)
+
+    def f(self, t, x, u):
+        """dP/dt = (L (x) I) P with L = -i (H (x) I - I (x) H^*), P = vec_r(M) (M' = L M)."""
+        d = self.H0.shape[0]
+        H = self.H0 + sum(h * uk for h, uk in zip(self.H1_list, np.reshape(u, -1)))
+        eye = np.identity(d)
+        L = -1j * (np.kron(H, eye) - np.kron(eye, H.conj()))
+        return (L @ np.reshape(x, (d * d, d * d))).reshape(-1)
+
+    @staticmethod
+    def lift(U):
+        """experiment.py:364-375: flat d x d unitary (d^2,) -> flat process vector vec_r(U (x) U^*) (d^4,)."""
+        U = np.asarray(U)
+        n = isqrt(U.shape[0])
+        U = U.reshape(n, n)
+        return np.kron(U, U.conj()).flatten()
+
+    @staticmethod
+    def proj(P):
+        """experiment.py:377-394: flat process vector (d^4,) -> a flat unitary (d^2,) equal to U up to a global phase: the first
+        non-zero d x d block U_ab U^* of P, conjugated and divided by the square root of its own entry (a, b) = |U_ab|^2."""
+        P = np.asarray(P)
+        n = isqrt(isqrt(P.shape[0]))
+        blocks = split_blocks(P.reshape(n ** 2, n ** 2), n, n)
+        U = np.zeros((n, n))
+        for i, val in enumerate([np.any(b) for b in blocks]):
+            if val:
+                U = blocks[i].conj() / np.emath.sqrt(blocks[i].flatten()[i])
+                break
+        return U.flatten()
+
+    def simulate(self, x0, ts, us):
+        """Process vectors in, process vectors out (experiment.py:396-417), shape (n, len(ts)); column 0 is x0.  Piecewise-constant
+        control as QExperiment.simulate: `us` is a callable of time or an (m, len(ts)) array whose column i is held on
+        [ts[i], ts[i+1])."""
+        ts = np.asarray(ts, dtype=float)
+        m = len(self.H1_list)
+        x = np.reshape(np.asarray(x0, dtype=np.complex128), -1)
+        op0, ops = self.operators()
+        cols = [x]
+        for i in range(len(ts) - 1):
+            u = np.reshape(us(ts[i]) if callable(us) else np.atleast_2d(us)[:, i], -1)[:m]
+            x = plant_step_batch(x[None], np.real(u)[None], op0, ops, ts[i + 1] - ts[i], _lib.PLANT_PROCESS)[0]
             cols.append(x)
         self.ts, self.us = ts, us
         self.xs = np.stack(cols, axis=1)

@@ -9,7 +9,7 @@ the target window (:276-277), exit codes and the dropped last entry (:294-304)."
 import numpy as np
 
 from . import _lib
-from .experiment import Experiment, QExperiment
+from .experiment import Experiment, QExperiment, QSynthesis
 from .library import krtimes
 from .linearize import WrapModel
 from .session import EnsembleSession
@@ -123,6 +123,18 @@ def _native_plant(experiment):
             and getattr(experiment, "_me_args", {}).get("e_ops") is None)
 
 
+def _identity(x):
+    return x
+
+
+def _loop_maps(experiment):
+    """(lift, proj) the loop applies to the plant's states.  A QSynthesis experiment's loop state IS its process vector: the lift
+    in the loop is the identity (difference 4), its lift / proj are helpers between U and U (x) U^*."""
+    if isinstance(experiment, QSynthesis):
+        return _identity, _identity
+    return experiment.lift, experiment.proj
+
+
 def _trim(xs, us, code, done):
     """mpc.py:294-304: normal exit keeps done+1 states and done controls; an early exit drops the attempted entry."""
     if code == 0:
@@ -137,10 +149,13 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
     exact_qp (extension): solve each QP to the box-constrained optimum, as the reference's OSQP call does, instead of
     clipping the Riccati rollout (identical whenever no bound is active).
     qp_flags (extension): M4Q_QP_* bits; _lib.QP_REF_LQR runs the loop around the arithmetic of the reference's lqr.py as
-    written, which is what tests/golden/mpc_loop.npz (the reference's own mpc.py around its own lqr.py) pins."""
+    written, which is what tests/golden/mpc_loop.npz (the reference's own mpc.py around its own lqr.py) pins.
+    A QSynthesis experiment (gate synthesis) runs on its process vector with the identity as the loop's lift: x0, the states
+    returned and the states exit_condition sees are process vectors vec_r(U (x) U^*)."""
     mf = int(clock.measure_freq)
     x0 = np.asarray(x0, dtype=np.complex128).reshape(-1)
-    lift_x0 = np.asarray(experiment.lift(x0), dtype=np.complex128).reshape(-1)
+    lift, proj = _loop_maps(experiment)
+    lift_x0 = np.asarray(lift(x0), dtype=np.complex128).reshape(-1)
     A_x, A_u = model.get_discrete()
     wrapped = WrapModel(A_x, A_u, dim_u, order)          # validates the library size like mpc.py:156
     n = wrapped.dim_x
@@ -148,7 +163,7 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
     X_targ = np.atleast_2d(np.asarray(X_targ))
     U_targ = np.atleast_2d(np.asarray(U_targ))
     cols = min(X_targ.shape[1], ns + T + 1)
-    fused = _native_plant(experiment) and exit_condition is None and not streaming
+    fused = (_native_plant(experiment) or isinstance(experiment, QSynthesis)) and exit_condition is None and not streaming
     kind = experiment.plant_kind if fused else _lib.PLANT_NONE
     sess = EnsembleSession(1, n, dim_u, order, T, ns, clock.dt, sat, du, max_iter, warm_start, qp_flags=qp_flags,
                            plant_kind=kind, target_cols=cols, measure_freq=mf, exact_qp=exact_qp)
@@ -197,14 +212,14 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
                 result = experiment.simulate(xs[step + 1 - mf], ts_step, _HeldControl(ts_step, us_step))   # mpc.py:256-260
                 xs.append(np.asarray(result)[:, -1])
             else:
-                lx = np.asarray(experiment.lift(xs[step])).reshape(-1, 1)                      # mpc.py:261-267
+                lx = np.asarray(lift(xs[step])).reshape(-1, 1)                                 # mpc.py:261-267
                 lu = wrapped.lift_u(u.reshape(-1, 1))
-                xs.append(np.asarray(experiment.proj(model.predict(lx, krtimes(lu, lx)))).flatten())
-            sess.put_state(step + 1, np.asarray(experiment.lift(xs[step + 1]), dtype=np.complex128).reshape(1, -1))
+                xs.append(np.asarray(proj(model.predict(lx, krtimes(lu, lx)))).flatten())
+            sess.put_state(step + 1, np.asarray(lift(xs[step + 1]), dtype=np.complex128).reshape(1, -1))
             if streaming:                                                                      # mpc.py:281-285
                 lu = wrapped.lift_u(u.reshape(-1, 1))
-                lx = np.asarray(experiment.lift(xs[step])).reshape(-1, 1)
-                model.fit_iteration(np.asarray(experiment.lift(xs[step + 1])).reshape(-1, 1), lx, krtimes(lu, lx))
+                lx = np.asarray(lift(xs[step])).reshape(-1, 1)
+                model.fit_iteration(np.asarray(lift(xs[step + 1])).reshape(-1, 1), lx, krtimes(lu, lx))
             if exit_condition is not None and exit_condition(xs[step + 1], xs[step], us[step]):
                 code = 1
                 break
@@ -283,7 +298,8 @@ def mpc_batch(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_
     """B independent closed loops in one launch.
     x0 [B, n]; models [B|1, n, n(1+P)] (or None with generators / scales: built on the device, see open_session);
     X_targ (n, cols) / U_targ (m, cols) shared (or [B, ...] each);
-    plant_op0 [B|1, k, k], plant_ops [B|1, m, k, k].  Returns a dict: xs [B, n, n_steps+1], us [B, m, n_steps]
+    plant_op0 [B|1, k, k], plant_ops [B|1, m, k, k] (k = d; plant_kind=_lib.PLANT_PROCESS: x0 and the targets are process vectors
+    of n = d^4 entries and k = d, the gate's Hamiltonians - that plant always runs the complex path).  Returns a dict: xs [B, n, n_steps+1], us [B, m, n_steps]
     (entries beyond steps_done are not meaningful), exit_codes, steps_done, qp_solves [B, n_steps]."""
     sess = open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_ops, Q, R, Qf, sat, du, max_iter,
                         warm_start, qp_flags, plant_kind, device, force_complex, exact_qp, traceless, tile, generators, scales,
