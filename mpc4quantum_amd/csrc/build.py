@@ -45,8 +45,8 @@ def run(cmd):
 
 
 def build(force=False, jobs=None, extra=()):
-    """Objects built with other extra flags than the ones requested now (experiment / ablation / debug builds write to the
-    same files) are rebuilt: a plain build() never ships the leftovers of an experiment."""
+    """Objects built with other extra flags than the ones requested now (development / debug builds write to the same files)
+    are rebuilt: a plain build() never ships the leftovers of one."""
     os.makedirs(OBJ, exist_ok=True)
     hdrs = [os.path.join(HERE, h) for h in HEADERS]
     gen = os.path.join(HERE, "m4q_dpp_gen.h")
@@ -99,11 +99,11 @@ if __name__ == "__main__":
     ap.add_argument("--dev", action="store_true", help="development build (-DM4Q_DEV): required for --shfl and for any --define of a "
                                                        "development switch; the sources refuse those switches without it")
     ap.add_argument("--shfl", action="store_true", help="debug build (needs --dev): row broadcasts through ds_bpermute instead of DPP")
-    ap.add_argument("--define", action="append", default=[], help="extra -D for the kernel objects (tuning experiments; forces a rebuild)")
+    ap.add_argument("--define", action="append", default=[], help="extra -D for the kernel objects, e.g. a development instrument (forces a rebuild)")
     ap.add_argument("--flag", action="append", default=[], help="extra compiler flag for the kernel objects, e.g. "
                                                                 "--flag=-mllvm --flag=-amdgpu-sched-strategy=max-ilp (forces a rebuild)")
     a = ap.parse_args()
-    dev_names = ("M4Q_BCAST_SHFL", "M4Q_NOP", "M4Q_DEV_PHASE_CLOCK", "M4Q_TWO_INDEX_COMPLEX", "M4Q_EXP")
+    dev_names = ("M4Q_BCAST_SHFL", "M4Q_NOP", "M4Q_DEV_PHASE_CLOCK")
     if not a.dev and (a.shfl or any(d.split("=")[0] in dev_names for d in a.define)):
         sys.exit("development switches need --dev (the library they produce is not the product)")
     extra = (["-DM4Q_DEV"] if a.dev else []) + (["-DM4Q_BCAST_SHFL"] if a.shfl else []) + ["-D" + d for d in a.define] + list(a.flag)

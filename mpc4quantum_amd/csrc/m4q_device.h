@@ -17,12 +17,10 @@
 #include <type_traits>
 #include <utility>
 
-// Development-only switches - a debug form of the row broadcast (ds_bpermute instead of DPP), an override of the DPP wait-state
-// pad, the per-phase clock, the two-index complex sweep - exist only in builds that say so: build.py passes -DM4Q_DEV for
-// `--dev` alone and tools/build_variant.sh (whose libraries never ship) always.  The timing-only ablation paths of round 2
-// ("results wrong": M4Q_EXP) are gone from the sources; what they measured is in profiles/r02_ab_experiments.txt.
-#if !defined(M4Q_DEV) && (defined(M4Q_BCAST_SHFL) || defined(M4Q_NOP) || defined(M4Q_DEV_PHASE_CLOCK) || defined(M4Q_TWO_INDEX_COMPLEX) || \
-                          defined(M4Q_EXP))
+// Development-only instruments - a debug form of the row broadcast (ds_bpermute instead of DPP), an override of the DPP wait-state
+// pad, the per-phase clock - exist only in builds that say so: build.py passes -DM4Q_DEV for `--dev` alone and
+// tools/build_variant.sh (whose libraries never ship) always.  They measure and debug; they do not choose between variants.
+#if !defined(M4Q_DEV) && (defined(M4Q_BCAST_SHFL) || defined(M4Q_NOP) || defined(M4Q_DEV_PHASE_CLOCK))
 #error "development switch without -DM4Q_DEV: use build.py --dev or tools/build_variant.sh"
 #endif
 

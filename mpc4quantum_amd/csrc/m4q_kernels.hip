@@ -43,19 +43,7 @@ constexpr int MODEL_ELEMS = (1 + NP) * NX * PITCH;        // per instance, eleme
 // the traceless path (m4q_mpc.h) runs the recursion on NX - 1 coordinates; everything it stages is no larger than the above
 constexpr int SCRATCH_ELEMS = (SQUARE ? DD * DD : 0) + 2 * NX;   // plant / basis-change scratch per instance (complex)
 constexpr int ROWS = 4;                                    // instances per wavefront
-// Timing-only ablations (development builds, tools/build_variant.sh ... -DM4Q_EXP=<bits>; RESULTS WRONG, never shipped - m4q_device.h
-// refuses the macro without -DM4Q_DEV).  What they bound is in profiles/r05_ab_experiments.txt.
-//   1  every line-search step stops after exactly 3 SQP iterations and no member ever fails: the work of a launch no longer depends
-//      on the numbers, so the variants below can be compared with a baseline built with bit 1 alone
-//   2  all workgroups of an XCD share ONE per-row workspace (guesses, solution, gains): every workspace access hits the L2 -
-//      the launch time that is left is what the workspace's L2 misses cost
-//   4  the four members of a workgroup share ONE model slot in LDS: the LDS footprint of a kernel whose members' models are
-//      (1 + m) shared generators - what d = 4 would need to run two wavefronts per SIMD (with -DM4Q_WAVES_REAL=2 -DM4Q_N15_HOIST=0)
-//  16  (m4q_tile3.h) the lower off-diagonal tiles of the symmetric P are copied, not computed: bound of a symmetric-P sweep
-#ifndef M4Q_EXP
-#define M4Q_EXP 0
-#endif
-constexpr int MODEL_ROWS = (M4Q_EXP & 4) ? 1 : ROWS;       // model slots per workgroup in LDS
+// (what the timing-only ablations of round 5 bound: profiles/r05_ab_experiments.txt)
 // the backward sweep on matrix-core tiles (m4q_tile3.h) is built where it is the faster form: d = 2, 3 (3 and 8 traceless coordinates)
 // with an order-1 library.  At d = 4 (15 coordinates = 4 x 4 tiles) it does not fit the register file (543 spilled VGPRs, 505 against
 // 71 ms on config 4) and full DPP rows leave nothing to gain; the host asks m4q_shape_*()->has_tile.
@@ -69,15 +57,9 @@ constexpr bool HAS_SG = SQUARE && ORDER == 1 && NX == 16;
 // register budget: waves per SIMD the kernels are compiled for (512 / budget VGPRs per lane).  d = 2 was compiled for four until the
 // end of round 3: at 128 registers every d = 2 closed-loop kernel spilled (59-372 VGPRs), and its launches are chains of
 // dependent passes that a third and fourth wavefront do not shorten: config 2 5.3 -> 4.2 ms at two (131,072 members: 23.6 -> 19.5 ms).
-#ifndef M4Q_WAVES
-#define M4Q_WAVES ((M4Q_NX <= 9) ? 2 : 1)
-#endif
-#ifndef M4Q_WAVES_REAL
-#define M4Q_WAVES_REAL ((M4Q_NX <= 9) ? 2 : 1)
-#endif
-#define M4Q_OCC __attribute__((amdgpu_waves_per_eu(M4Q_WAVES, 8)))
-template <class S> struct WavesFor { static constexpr int value = M4Q_WAVES; };
-template <> struct WavesFor<double> { static constexpr int value = M4Q_WAVES_REAL; };
+// The same on the complex and the real path, and in the exact mode.
+constexpr int WAVES = NX <= 9 ? 2 : 1;
+#define M4Q_OCC __attribute__((amdgpu_waves_per_eu(WAVES, 8)))
 
 extern __shared__ __align__(16) unsigned char m4q_lds_raw[];
 
@@ -153,7 +135,7 @@ template <class S, int N, bool EXACT> constexpr bool cost_transposed() { return 
 template <class S, bool TL, bool EXACT> constexpr bool exact_tile() { return EXACT && TL && HAS_TILE && sizeof(S) == sizeof(double); }
 // SG: ROWS blocks A_i and ONE set of NP blocks N_k instead of ROWS x (1 + NP) blocks
 template <int N, bool SG> constexpr int model_lds_elems() {
-  return SG ? (ROWS + NP) * N * ModelPitch<N>::value : MODEL_ROWS * model_elems<N>();
+  return SG ? (ROWS + NP) * N * ModelPitch<N>::value : ROWS * model_elems<N>();
 }
 template <class S, bool TL = false, bool TILE = false, bool EXACT = false, bool SG = false>
 constexpr size_t mpc_lds_layout_bytes() {
@@ -219,7 +201,7 @@ struct ExactTile {
     TileBackwardB<NS, NU, ORDER, true> ts;
     const int mb = ts.L.mb;
     const int dm = mb - g;
-    ts.mdl = lds_models + (MODEL_ROWS == ROWS ? mb : 0) * model_elems<NS>();
+    ts.mdl = lds_models + mb * model_elems<NS>();
     ts.T = T;
     ts.Xg = Xg; ts.Xg.off = Xg.off + (unsigned)(dm * (int)(sX * sizeof(double)));
     ts.Ug = Ug; ts.Ug.off = Ug.off + (unsigned)(dm * (int)(sU * sizeof(double)));
@@ -247,32 +229,11 @@ constexpr int TC_MIN_N = 8;
 // (round 3, when every cut cost two passes of 41 basis changes: one cut at 5.  Round 4, with the guess handed over as it is:
 //  {4, 7, 12} - config 3 185-187 ms either way, config 4 1,747 -> 1,657, config 5's share 4,315 -> 4,155; {5, 10}: 1,704 at
 //  config 4; a cut at every step 3..9: 189 ms at config 3; profiles/r04_ab_experiments.txt)
-#ifndef M4Q_EXACT_CUTS
-#define M4Q_EXACT_CUTS 4, 7, 12
-#endif
-constexpr int XCUTS[] = {M4Q_EXACT_CUTS};
+constexpr int XCUTS[] = {4, 7, 12};
 constexpr int NXC = (int)(sizeof(XCUTS) / sizeof(int));
-#ifndef M4Q_WAVES_EXACT
-#define M4Q_WAVES_EXACT(S) WavesFor<S>::value
-#endif
-#ifndef M4Q_PUBLISH_NODES
-#define M4Q_PUBLISH_NODES 1
-#endif
-#ifndef M4Q_LS_NODES
-#define M4Q_LS_NODES 1
-#endif
-#ifndef M4Q_UPD16
-#define M4Q_UPD16 1
-#endif
-#ifndef M4Q_PIECE_RAW
-#define M4Q_PIECE_RAW 1
-#endif
-#ifndef M4Q_WAVES_SG
-#define M4Q_WAVES_SG 2
-#endif
-#ifndef M4Q_WAVES_TILE
-#define M4Q_WAVES_TILE 2
-#endif
+// the shared-generator and the tile kernels are compiled for two wavefronts per SIMD at every shape
+constexpr int WAVES_SG = 2;
+constexpr int WAVES_TILE = 2;
 // Development builds (-DM4Q_DEV_PHASE_CLOCK): PhaseClock (m4q_device.h) sums the 100 MHz clock over the phases of the main loop; every
 // wavefront adds its sums to queue[8..23] (u64) on exit; M4Q_PHASE_TRACE=1 makes m4q_session_qp_stats print them.
 #if defined(M4Q_DEV_PHASE_CLOCK)
@@ -283,7 +244,7 @@ constexpr int NXC = (int)(sizeof(XCUTS) / sizeof(int));
 #define M4Q_PHASE_DECL PhaseClock pc;
 #define M4Q_PHASE_MARK(i) pc.mark(i);
 template <class S, int PLANT, bool EXACT, bool TL = false, bool TILE = false, bool SG = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAVES_SG : TILE ? M4Q_WAVES_TILE : EXACT ? M4Q_WAVES_EXACT(S) : WavesFor<S>::value, 8))) void mpc_kernel(MpcArgs) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_SG : TILE ? WAVES_TILE : WAVES, 8))) void mpc_kernel(MpcArgs) {
   static_assert(!TL || (sizeof(S) == sizeof(double) && SQUARE), "the traceless path is a real path of a d x d density matrix");
   static_assert(!TILE || (TL && !EXACT && ORDER == 1), "tile sweep: clipped solve on the traceless real coordinates, order-1 libraries");
   static_assert(!SG || (TL && !TILE && !EXACT && ORDER == 1), "shared generators: the clipped traceless kernel of an order-1 library");
@@ -301,7 +262,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
   constexpr bool QTR = cost_transposed<S, NS, EXACT>();
   // (SG: MODEL_K is one block - the member's A_i -, the NP shared blocks N_k follow the ROWS of them)
   constexpr int MODEL_K = SG ? NS * ModelPitch<NS>::value : model_elems<NS>(), COST_K = cost_elems<NS>() + (QTR ? 2 * NS * NS : 0);
-  S* mdl = lds + (MODEL_ROWS == ROWS || SG ? g : 0) * MODEL_K;
+  S* mdl = lds + g * MODEL_K;
   S* mdn = lds + ROWS * MODEL_K;                   // (SG only)
   scratch += g * SCRATCH_ELEMS;
   S* ldsQ = lds + model_lds_elems<NS, SG>();
@@ -384,17 +345,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
   // workspace of this resident row: wave-uniform base per workgroup, lane part = row within the wave
   const unsigned sX = (unsigned)(T0 + 1) * NS, sU = (unsigned)T0 * NU, sG = (unsigned)T0 * (NS + 1) * NU;
   const unsigned sXc = (unsigned)(T0 + 1) * NX;            // the SQP-guess checkpoint field: complex, NX per node
-  constexpr bool PIECE_RAW = M4Q_PIECE_RAW && sizeof(S) == sizeof(double);     // (between items of one launch: see the publish step)
+  constexpr bool PIECE_RAW = sizeof(S) == sizeof(double);     // (between items of one launch: see the publish step)
   // Lanes NX..15 of a row own no column (7 of 16 at d = 3, 12 of 16 at d = 2).  Left enabled they run the sweeps on a copy of
   // column NX-1's data: harmless for the results, but the fp64 pipe spends power on them, and the clock this chip holds under an
   // fp64-dense load follows the power.  EXEC is therefore off for them during the two sweeps (every DPP source is a lane < NX;
   // results bit-identical): the complex path runs at 2.30 GHz instead of 2.04 (133.3 -> 117.6 ms, config 3), the real path at 2.29
   // instead of 2.18 (51.2 -> 50.4 ms; config 5's share 171.2 -> 166.3 ms).  profiles/r02_ab_experiments.txt, r02_clock_ramp.txt.
-  constexpr bool MASK_IDLE = M4Q_MASK_IDLE && NS < 16 && !EXACT && !TILE;
+  constexpr bool MASK_IDLE = NS < 16 && !EXACT && !TILE;
   GView Xg, Ug, Xo, Uo, gains, Xalt, Ualt, pin_stat;
   {
     KArgs* a = kargs();
-    const long wsb = (M4Q_EXP & 2) ? (long)(blockIdx.x & 7) : (long)blockIdx.x;
+    const long wsb = blockIdx.x;
     M4Q_GLOBAL S* wX = (M4Q_GLOBAL S*)a->ws_Xg;
     Xg = gview(wX, wsb * ROWS * sX, g * sX);
     Ug = gview(a->ws_Ug, wsb * ROWS * sU, g * sU);
@@ -560,7 +521,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
           if (rs_raw) {
             const M4Q_GLOBAL double* raw = (const M4Q_GLOBAL double*)(a->Xg + b * sXc);
             const int count = (T + 1) * NS;
-            if constexpr (M4Q_UPD16 && NS % 2 == 0) {
+            if constexpr (NS % 2 == 0) {
               constexpr int U = 6;
               for (int e0 = 2 * jj; e0 < count; e0 += 32 * U) {
                 d2_t v[U];
@@ -678,7 +639,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
           TileBackwardB<NS, NU, ORDER> ts;
           const int mb = ts.L.mb;
           const int dm = mb - g;                                 // this lane's member there minus its member here
-          ts.mdl = reinterpret_cast<const double*>(lds) + (MODEL_ROWS == ROWS ? mb : 0) * MODEL_K;
+          ts.mdl = reinterpret_cast<const double*>(lds) + mb * MODEL_K;
           ts.T = T;
           ts.Xg = Xg; ts.Xg.off = Xg.off + (unsigned)(dm * (int)(sX * sizeof(double)));
           ts.Ug = Ug; ts.Ug.off = Ug.off + (unsigned)(dm * (int)(sU * sizeof(double)));
@@ -698,7 +659,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
         // the rollout on DPP rows (on tiles it was built twice: round 3's per-index form took 2.3 times as long, round 4's time-batched
         // form - tools/tile_rollout_r04.h - the same SIMD time at d = 3 and 14 % more of the launch at d = 2)
         // (idle lanes sit it out as in the DPP kernels: MASK_IDLE itself is off for TILE because the tile sweep needs all 64 lanes)
-        constexpr bool MASK_FWD = M4Q_MASK_IDLE && NS < 16;
+        constexpr bool MASK_FWD = NS < 16;
         if (!MASK_FWD || lane_ok)         // (the tile path runs with a constant target only)
           chk = rollout_forward<S, NS, NU, false, true>(prov, T, x_cur, win, cost, flags, gains, sat, lo0, hi0, Xo, Uo, j, st, uapp, !use_ls, &Xg, &Ug);
         if constexpr (MASK_FWD) {
@@ -710,7 +671,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
         // (xbar_t the same for every t: the sweep needs no row form of A_t - wave-uniform choice between two instantiations.
         //  Round 2: n = 16 only - config 4 85.5 -> 84.2 ms, while at n = 9 the kernel with both instantiations was SLOWER, 50.65 -> 51.7 ms,
         //  although it executes 27 vector instructions fewer per horizon index (profiles/r02_ab_experiments.txt).  Round 3, with the
-        //  kernel off the register ceiling: n >= 8 - M4Q_TC_MIN_N above.)
+        //  kernel off the register ceiling: n >= 8 - TC_MIN_N above.)
         constexpr bool HAS_TC = NS >= TC_MIN_N && sizeof(S) == sizeof(double);
         bool tc = false;
         if constexpr (HAS_TC) tc = (flags & QP_TARG_CONST) != 0;
@@ -722,15 +683,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
         if (!tc && (!MASK_IDLE || lane_ok)) riccati_backward<S, NS, NU>(prov, T, win, cost, flags, gains, j, st);
         wave_sync();
         M4Q_PHASE_MARK(1)
-        constexpr bool HAS_TCF = HAS_TC && M4Q_TCF(NS);
-        bool tcf = false;
-        if constexpr (HAS_TCF) tcf = tc;
-        if constexpr (HAS_TCF) {
+        if constexpr (HAS_TC) {
           if (tc && (!MASK_IDLE || lane_ok))
             chk = rollout_forward<S, NS, NU, false, true>(prov, T, x_cur, win, cost, flags, gains, sat, lo0, hi0, Xo, Uo, j, st, uapp,
                                                           !use_ls, &Xg, &Ug);
         }
-        if (!tcf && (!MASK_IDLE || lane_ok))
+        if (!tc && (!MASK_IDLE || lane_ok))
           chk = rollout_forward<S, NS, NU, false>(prov, T, x_cur, win, cost, flags, gains, sat, lo0, hi0, Xo, Uo, j, st, uapp,
                                                   !use_ls, &Xg, &Ug);
         if constexpr (MASK_IDLE) {
@@ -860,7 +818,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
     stash.get_x(x_meas);
     // exit code 3: non-finite objective (mpc.py:200-203).  exit code 2 (EXACT only): the solver gave up - the analogue of
     // the solver warning mpc.py:183-197 turns into code 2; either way the member's run ends here (mpc.py:196,203,231).
-    const bool fail = (M4Q_EXP & 1) ? false : (!finite_d(chk) || capped);
+    const bool fail = !finite_d(chk) || capped;
     if (solved) ++iter;
     double alpha = 1.0;
     bool fin = true;
@@ -871,14 +829,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
       double al = 1.0, stepn = 0.0;
       if constexpr (TL) {
         // (the host selects TL only with diagonal costs)
-        if constexpr (M4Q_LS_NODES && NS % 2 == 0) line_search_tl_nodes<NX, NU, DD, TILE>(z, ldsW, ldsW + 2 * NX, ldsW + 4 * NX, jj, al, stepn);
+        if constexpr (NS % 2 == 0) line_search_tl_nodes<NX, NU, DD, TILE>(z, ldsW, ldsW + 2 * NX, ldsW + 4 * NX, jj, al, stepn);
         else line_search_tl<NX, NU, DD>(z, ldsW, ldsW + 2 * NX, ldsW + 4 * NX, jj, al, stepn);
       } else if (ls_diag) {
         line_search_diag<S, NX, NU, DD>(z, ldsW, ldsW + 2 * NX, ldsW + 4 * NX, jj, al, stepn);
       } else {
         if constexpr (sizeof(S) == sizeof(cplx)) line_search<NX, NU>(z, a->Cq, a->Cqf, a->Cr, jj, al, stepn);
       }
-      if (use_ls) { alpha = al; fin = (M4Q_EXP & 1) ? iter >= 3 : stepn < a->ls_tol; }   // mpc.py:224
+      if (use_ls) { alpha = al; fin = stepn < a->ls_tol; }   // mpc.py:224
     }
     wave_sync();
     M4Q_PHASE_MARK(4)
@@ -887,7 +845,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
     // (these small per-element passes are latency bound: unrolled so that several loads are in flight)
     // (the row's 16 lanes share the (T + 1) NS contiguous elements, and a batch of U elements per lane issues all its loads
     //  before the first store: left to the compiler the unrolled loop waited for every pair in turn - 22,000 cycles per update)
-    if constexpr (M4Q_UPD16 && NS % 2 == 0 && sizeof(S) == sizeof(double)) {
+    if constexpr (NS % 2 == 0 && sizeof(S) == sizeof(double)) {
       // (n even: rows of the workspace start on 16-byte boundaries and hold an even number of doubles - two elements per access)
       if (upd) {
         constexpr int U = 6;
@@ -929,7 +887,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
           if (e0 + 16 * u < count) Xg.st<S>(e0 + 16 * u, cadd(xg[u], cscale(csub(xo[u], xg[u]), alpha)));
       }
     }
-    if constexpr (M4Q_UPD16 && NU % 2 == 0) {
+    if constexpr (NU % 2 == 0) {
       if (upd) {
         constexpr int V = 4;
         const int cu = T * NU;
@@ -1085,7 +1043,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
       // launch: on the real paths it goes into the same field as it is (PIECE_RAW: (T + 1) NS doubles, flat) - 41 basis changes less
       // on either side of every cut, and no rounding at the cuts.
       const bool last_piece = row_end == a->step_end;
-      if constexpr (TL && M4Q_PUBLISH_NODES && NS % 2 == 0) {
+      if constexpr (TL && NS % 2 == 0) {
         // (traceless path, n_s even: one trajectory node per lane - its coordinates as 16-byte pairs, its NX slots formed and stored
         //  by that lane (tl_node_to_complex) - instead of a slot per lane with an exchange through LDS per node)
         if (finished && last_piece) {
@@ -1122,7 +1080,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? M4Q_WAV
         if (finished && !last_piece) {
           M4Q_GLOBAL double* raw = (M4Q_GLOBAL double*)(a->Xg + b * sXc);
           const int count = (T + 1) * NS;
-          if constexpr (M4Q_UPD16 && NS % 2 == 0) {
+          if constexpr (NS % 2 == 0) {
             constexpr int U = 6;
             for (int e0 = 2 * jj; e0 < count; e0 += 32 * U) {
               double v[U][2];

@@ -8,8 +8,8 @@
 #pragma once
 #include "m4q_device.h"
 
-// Settled by A/B runs and no longer switches (each was a macro until round 4; the losing branches are gone from the source, their
-// numbers are in profiles/r02_ab_experiments.txt, r03_exact_qp_log.txt, r04_ab_experiments.txt):
+// Settled by A/B runs and no longer switches (the losing branches are gone from the source; their numbers are in
+// profiles/r02_ab_experiments.txt, r03_exact_qp_log.txt, r04_ab_experiments.txt):
 //   real path, n <= 9: the model's column and row forms read from LDS in one batch per horizon index (51.98 -> 50.38 ms), in the
 //     rollout too (51.2 -> 50.85); with a constant target the N_p rows and column j of Q stay in registers over the sweep
 //     (39.4 -> 38.25 ms) and the row form over the rollout (40.4 -> 39.4);
@@ -19,30 +19,12 @@
 //     adjoint pass (226 -> 221);
 //   constant targets: A_t xbar from 1 + NP products formed once per sweep (recursions of dimension >= 8: 41.3 -> 40.3 ms);
 //   scheduling barriers between the phases of a sweep: slower (53.3 -> 52.5 ms without); the two-index form of the COMPLEX sweep:
-//     brings nothing and one experimental d = 4 build of it faulted - the complex sweep runs one index per trip.
-#ifndef M4Q_MASK_IDLE
-#define M4Q_MASK_IDLE 1      // lanes that own no column sit the two sweeps out (EXEC off): less power, higher clock (m4q_kernels.hip)
-#endif
-// Round 4: vector-memory instructions of the two sweeps (profiles/r04_ab_experiments.txt; every line an A/B on one box)
-#ifndef M4Q_TC_XB_ONCE
-#define M4Q_TC_XB_ONCE(n) ((n) < 15)  // constant-target backward sweep: xbar loaded once per sweep, not per index.  n = 15 (one wavefront
-                                      // per SIMD): the sweep WITHOUT that load is slower, 73.0 against 71.2 ms on config 4 - kept per index there
-#endif
-#ifndef M4Q_TCF
-#define M4Q_TCF(n) true               // constant-target instantiation of the rollout as well (xbar loaded once): config 3 35.77 -> 35.52 ms
-#endif
-#ifndef M4Q_SG_VFORM
-#define M4Q_SG_VFORM 1              // shared-generator rollout: the step as one product of the row [A | N_1 .. N_m] (63.3 -> 62.5 ms at config 4)
-#endif
-#ifndef M4Q_STORE_ALL
-// n >= 15: one wavefront per SIMD with 512 registers - loop-invariant operands of the exact mode's passes stay in registers
-#ifndef M4Q_N15_HOIST
-#define M4Q_N15_HOIST 1               // 0 (experiment builds): n >= 15 compiled for TWO wavefronts per SIMD - nothing held over a sweep
-#endif
-#define M4Q_XH15(n) (M4Q_N15_HOIST && (n) >= 15)
-#define M4Q_STORE_ALL(n) true         // values replicated over a row (k, u) are stored by every lane of the row - no exec mask to set up -
-                                      // instead of by lane 0: config 4 75.5 -> 73.0 ms, config 3 together with M4Q_TC_XB_ONCE 36.05 -> 35.6
-#endif
+//     brings nothing and one experimental d = 4 build of it faulted - the complex sweep runs one index per trip;
+//   lanes that own no column sit the two sweeps out (EXEC off): less power, higher clock (m4q_kernels.hip: MASK_IDLE);
+//   constant targets: the rollout instantiated for them as well, xbar loaded once (config 3 35.77 -> 35.52 ms);
+//   shared-generator rollout: the step as one product of the row [A | N_1 .. N_m] (63.3 -> 62.5 ms at config 4);
+//   values replicated over a row (k, u) are stored by every lane of the row - no exec mask to set up - instead of by lane 0:
+//     config 4 75.5 -> 73.0 ms, config 3 together with tc_xb_once below 36.05 -> 35.6.
 
 namespace m4q {
 
@@ -54,6 +36,14 @@ enum : int {
   QP_TARG_CONST = 256,   // internal (set by the host when every column of X_targ is the same): xbar_t does not depend on t
   QP_NO_TILE = 512,      // internal (M4Q_OPT_NO_TILE in the exact mode, whose kernel holds both forms of the pinned sweep)
 };
+
+// Round 4: vector-memory instructions of the two sweeps (profiles/r04_ab_experiments.txt; every line an A/B on one box).
+// Constant-target backward sweep: xbar loaded once per sweep, not per index.  n = 15 (one wavefront per SIMD): the sweep WITHOUT
+// that load is slower, 73.0 against 71.2 ms on config 4 - kept per index there.
+constexpr bool tc_xb_once(int n) { return n < 15; }
+// n >= 15: one wavefront per SIMD with 512 registers - loop-invariant operands of the sweeps and the exact mode's passes stay in
+// registers over a sweep (compiled for two wavefronts per SIMD instead, nothing can be held)
+constexpr bool xh15(int n) { return n >= 15; }
 
 // ---------------------------------------------------------------------------------------------
 // Control-monomial table, in the order of linearize.create_power_list (linearize.py:92-116):
@@ -805,7 +795,7 @@ __device__ __forceinline__ void riccati_backward(const Prov& prov, int T, const 
   auto load = [&](int t) __attribute__((always_inline)) {
     Ops o;
     o.lin = prov.fetch(t);
-    if constexpr (TC && (M4Q_TC_XB_ONCE(NX) || fused_kind<Prov>::sg)) o.xb = xb_next;   // (constant target: the column loaded above serves every index)
+    if constexpr (TC && (tc_xb_once(NX) || fused_kind<Prov>::sg)) o.xb = xb_next;   // (constant target: the column loaded above serves every index)
     else o.xb = win.xbm.ld<S>(t * NX + j);
     ldn<NU>(win.ubm, t * NU, o.ub);
     if constexpr (PINNED) ldn<NU>(pin->stat, t * NU, o.stv);
@@ -818,7 +808,7 @@ __device__ __forceinline__ void riccati_backward(const Prov& prov, int T, const 
   constexpr bool HOIST_SMALL = TC && sizeof(S) == sizeof(double) && NX < 15 &&
                                std::is_same<Prov, FusedProv<S, NX, NU, Prov::ORDER_>>::value && batch_fits<NX, NU, Prov::ORDER_>();
   constexpr bool HOIST = (std::is_same<Prov, FusedProv<S, NX, NU, Prov::ORDER_>>::value && sizeof(S) == sizeof(double) &&
-                          M4Q_XH15(NX)) || HOIST_SMALL;
+                          xh15(NX)) || HOIST_SMALL;
   ModelRegs<S, NX, NU, Prov::ORDER_> mregs;
   if constexpr (HOIST) mregs.load_rows(prov, j);
   // constant target: real fused path with batched (n <= 9) or hoisted (n = 16, mode 2) model reads
@@ -977,7 +967,7 @@ __device__ __forceinline__ void riccati_backward(const Prov& prov, int T, const 
     if (store_ok) {
       const unsigned gt = (unsigned)t * (NX + 1) * NU;
       stn<NU>(gains, gt + j * NU, Kst);
-      if (M4Q_STORE_ALL(NX) || j == 0) stn<NU>(gains, gt + NX * NU, kst);   // (replicated over the row: every lane may write the same bytes)
+      stn<NU>(gains, gt + NX * NU, kst);   // (replicated over the row: every lane may write the same bytes)
     }
 
     // closed loop: Sx = A_t + B Kx (column j, in place): Ac[i] += lane_i(B[i][k]) Kx[k];  s = c + B k
@@ -1075,7 +1065,7 @@ __device__ __forceinline__ void adjoint_pass(const Prov& prov, int T, const Wind
                           sizeof(S) == sizeof(double) && batch_fits<NX, NU, Prov::ORDER_>() && Prov::ORDER_ == 1;
   // n >= 15 (one wavefront per SIMD, 512 registers): both forms of the model and Q's row stay in registers over the pass -
   // at one wavefront per SIMD every LDS read-to-use latency is exposed
-  constexpr bool AH15 = std::is_same<Prov, FusedProv<S, NX, NU, Prov::ORDER_>>::value && sizeof(S) == sizeof(double) && M4Q_XH15(NX) &&
+  constexpr bool AH15 = std::is_same<Prov, FusedProv<S, NX, NU, Prov::ORDER_>>::value && sizeof(S) == sizeof(double) && xh15(NX) &&
                         Prov::ORDER_ == 1;
   ModelRegs<S, NX, NU, Prov::ORDER_> mregs;
   S Qrow[AH15 ? NX : 1];
@@ -1202,7 +1192,7 @@ __device__ __forceinline__ double rollout_forward(const Prov& prov, int T, S x0,
     return o;
   };
   constexpr bool HOIST = std::is_same<Prov, FusedProv<S, NX, NU, Prov::ORDER_>>::value && sizeof(S) == sizeof(double) &&
-                         (M4Q_XH15(NX) || (batch_fits<NX, NU, Prov::ORDER_>()));
+                         (xh15(NX) || (batch_fits<NX, NU, Prov::ORDER_>()));
   ModelRegs<S, NX, NU, Prov::ORDER_> mregs;
   if constexpr (HOIST) mregs.load_rows(prov, j);
   // one horizon index: `cur` holds its operands, those of the next index are fetched into `nxt` meanwhile.  The loop
@@ -1213,7 +1203,7 @@ __device__ __forceinline__ double rollout_forward(const Prov& prov, int T, S x0,
     nxt = load(t + 1 < T ? t + 1 : t);
     // (SGV, shared generators: the step as ONE product of the row [A | N_1 .. N_m] read from LDS once,
     //  x+ = A_i x + sum_k N_k (u~g_k x + (u~_k - u~g_k) xg) with u~ = s u - no row of A_t is built: NU NX FMAs per index fewer)
-    constexpr bool SGV = M4Q_SG_VFORM && fused_kind<Prov>::sg;
+    constexpr bool SGV = fused_kind<Prov>::sg;
     S ax, Brow[NU], dlt;
     if constexpr (SGV) { (void)ax; (void)Brow; (void)dlt; }
     else if constexpr (HOIST) prov.rows(mregs, cur.lin, x, ax, Brow, dlt);
@@ -1281,10 +1271,10 @@ __device__ __forceinline__ double rollout_forward(const Prov& prov, int T, S x0,
       Xd.st<S>((t + xs_shift) * NX + j, x);
       // (u is replicated over the row: every lane writes the same bytes.  A shifting row's u_0 has no slot: it goes to slot 0,
       //  which the same lane's store of u_1 overwrites - no exec mask to set up)
-      if (M4Q_STORE_ALL(NX) || j == 0) stn<NU>(Ud, (unsigned)(t + us_shift > 0 ? t + us_shift : 0) * NU, u);
+      stn<NU>(Ud, (unsigned)(t + us_shift > 0 ? t + us_shift : 0) * NU, u);
       if (shift_out && t == T - 1) {
         Xd.st<S>(T * NX + j, x);                       // repeat the last column
-        if (M4Q_STORE_ALL(NX) || j == 0) stn<NU>(Ud, (T - 1) * NU, u);
+        stn<NU>(Ud, (T - 1) * NU, u);
       }
     }
   };
@@ -1386,10 +1376,10 @@ __device__ __forceinline__ double rollout_policy(const Prov& prov, int T, S x0, 
   // (the row form of the model in registers over the rollout, as rollout_forward: n <= 9 real paths; exact mode 190 -> 184 ms with
   //  this in the policy and open rollouts and their replicated u stores unmasked: profiles/r04_ab_experiments.txt)
   constexpr bool HOIST = std::is_same<Prov, FusedProv<S, NX, NU, Prov::ORDER_>>::value && sizeof(S) == sizeof(double) &&
-                         (M4Q_XH15(NX) || batch_fits<NX, NU, Prov::ORDER_>());
+                         (xh15(NX) || batch_fits<NX, NU, Prov::ORDER_>());
   ModelRegs<S, NX, NU, Prov::ORDER_> mregs;
   if constexpr (HOIST) mregs.load_rows(prov, j);
-  constexpr bool QH = HOIST && M4Q_XH15(NX);          // (n >= 15, one wavefront per SIMD: Q's row in registers as well; at n = 8,
+  constexpr bool QH = HOIST && xh15(NX);          // (n >= 15, one wavefront per SIMD: Q's row in registers as well; at n = 8,
                                                        //  two wavefronts per SIMD, the 16 registers cost more: 185 -> 190 ms)
   S Qrow[QH ? NX : 1];
   if constexpr (QH) load_qrow<NX>(cost, T, j, Qrow);
@@ -1444,7 +1434,7 @@ __device__ __forceinline__ double rollout_policy(const Prov& prov, int T, S x0, 
     x = xn;
     if (store_ok) {
       Xc.st<S>((t + 1) * NX + j, x);
-      if (M4Q_STORE_ALL(NX) || j == 0) stn<NU>(Uc, t * NU, un);      // (replicated over the row: same bytes from every lane)
+      stn<NU>(Uc, t * NU, un);      // (replicated over the row: same bytes from every lane)
     }
   };
   Ops opsA = load(0), opsB;
@@ -1482,10 +1472,10 @@ __device__ __forceinline__ double rollout_open(const Prov& prov, int T, S x0, co
     return o;
   };
   constexpr bool HOIST = std::is_same<Prov, FusedProv<S, NX, NU, Prov::ORDER_>>::value && sizeof(S) == sizeof(double) &&
-                         (M4Q_XH15(NX) || batch_fits<NX, NU, Prov::ORDER_>());
+                         (xh15(NX) || batch_fits<NX, NU, Prov::ORDER_>());
   ModelRegs<S, NX, NU, Prov::ORDER_> mregs;
   if constexpr (HOIST) mregs.load_rows(prov, j);
-  constexpr bool QH = HOIST && M4Q_XH15(NX);
+  constexpr bool QH = HOIST && xh15(NX);
   S Qrow[QH ? NX : 1];
   if constexpr (QH) load_qrow<NX>(cost, T, j, Qrow);
   auto step = [&](int t, const Ops& cur, Ops& nxt) __attribute__((always_inline)) {
@@ -1515,7 +1505,7 @@ __device__ __forceinline__ double rollout_open(const Prov& prov, int T, S x0, co
     x = xn;
     if (store_ok) {
       Xc.st<S>((t + 1) * NX + j, x);
-      if (M4Q_STORE_ALL(NX) || j == 0) stn<NU>(Uc, t * NU, u);
+      stn<NU>(Uc, t * NU, u);
     }
   };
   Ops opsA = load(0), opsB;
@@ -1578,10 +1568,7 @@ struct BoxQpRow {
 // pdas_switch_proto.py: config 3's hard solves - the first warm steps, whose shifted guess is poor - need up to 22 on the members
 // tried; config 4's often cycle, and pay for the try).  Measured on config 3, 65,536 members: cap 16 298 ms, 24 278, 40 254, 64 263,
 // 100 272 (profiles/r03_exact_qp_log.txt).
-#ifndef M4Q_PDAS_CAP
-#define M4Q_PDAS_CAP 40
-#endif
-constexpr int PDAS_CAP = M4Q_PDAS_CAP;
+constexpr int PDAS_CAP = 40;
 
 // The pinned sweep of box_qp_iterate on matrix-core tiles instead of DPP rows (m4q_tile3.h: TileBackwardB<..., PINNED>), where the
 // kernel provides it: an object with `enabled` and sweep(T, win, pin, store_ok).  NoTileSweep: DPP rows.

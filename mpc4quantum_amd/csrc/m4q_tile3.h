@@ -34,12 +34,6 @@ __device__ __forceinline__ double to_sgpr(double x) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
 }
 
-#ifndef M4Q_TILE_GB_BATCH
-#define M4Q_TILE_GB_BATCH 1
-#endif
-#ifndef M4Q_TILE_CBLK
-#define M4Q_TILE_CBLK 1               // the affine column c of a block's four indices formed once per block (bit-identical; config 3 29.8 -> 29.3 ms)
-#endif
 // PINNED: the sweep of the exact box-QP iteration (riccati_backward<PINNED> of m4q_mpc.h, same algebra): controls of the working
 // set `stat` ([T][NU]: 0 free, +1 / -1 pinned at the upper / lower bound) are constants of their stage; the stored row of a pinned
 // control is the affine form of its multiplier.
@@ -177,16 +171,7 @@ struct TileBackwardB {
         }
 #pragma unroll
       for (int K = 0; K < NT; ++K) {
-        double a;
-        if constexpr (M4Q_TILE_CBLK) {
-          a = cin[K];                                                           // (formed for the block's four indices at once: block())
-        } else {
-          a = tt[0][K];
-#pragma unroll
-          for (int p = 0; p < NP; ++p) a = fma(ug[p], tt[1 + p][K], a);
-#pragma unroll
-          for (int s = 0; s < NU; ++s) a = fma(b[s][K], ub[s] - ug[s], a);      // + B ubar + Delta, Delta = -B u_g
-        }
+        const double a = cin[K];                                                // (formed for the block's four indices at once: block())
         c[K] = a;
         double w = isq[NU] ? a : 0.0;                                           // W = [B | c | 0]
 #pragma unroll
@@ -214,7 +199,6 @@ struct TileBackwardB {
       wave_sync();
       cplx gm[NU][NU], ginv[NU][NU];
       double h[NU];
-#if M4Q_TILE_GB_BATCH
       {
         // (all reads of the G / h tile issued before the first use: gb is volatile, and read-add-read-add made each of the
         //  NU (NU + 3) / 2 reads its own LDS round trip on the index's dependent chain)
@@ -233,14 +217,6 @@ struct TileBackwardB {
           h[s] = hv[s];
         }
       }
-#else
-#pragma unroll
-      for (int s = 0; s < NU; ++s) {
-#pragma unroll
-        for (int l = s; l < NU; ++l) gm[s][l] = mk(gb[s * 4 + l] + Rm[s][l], 0.0);
-        h[s] = gb[s * 4 + NU];
-      }
-#endif
       wave_sync();
       bool fix[NU];
       double dufix[NU], hraw[NU], Gf[NU][NU];
@@ -380,11 +356,6 @@ struct TileBackwardB {
         pv[I] = pn;
 #pragma unroll
         for (int J = 0; J < NT; ++J) {
-#if defined(M4Q_EXP) && (M4Q_EXP & 16)
-          // timing-only (RESULTS WRONG): the lower off-diagonal tiles of the symmetric P are not computed - what a sweep that derived
-          // them from the upper ones FOR FREE would save (the 4 x 4 transposes it would really need are not paid here)
-          if (J < I) { P[I][J] = P[J][I]; continue; }
-#endif
           double e;
           if constexpr (QLDS) e = Qlane[4 * I * NS + 4 * J];
           else e = Qt[I][J];
@@ -410,18 +381,16 @@ struct TileBackwardB {
         }
       // the affine column c = A xbar - xbar+ + sum_p u_p N_p xbar + B (ubar - u_g) of the block's four indices as ONE tile per K (lane
       // q holds time tb - q, as the operands do): the same fused multiply-adds in the same order as per index - bit-identical - issued
-      // once per block instead of once per index (M4Q_TILE_CBLK)
+      // once per block instead of once per index (config 3 29.8 -> 29.3 ms)
       double CT[NT];
-      if constexpr (M4Q_TILE_CBLK) {
 #pragma unroll
-        for (int K = 0; K < NT; ++K) {
-          double a = tt[0][K];
+      for (int K = 0; K < NT; ++K) {
+        double a = tt[0][K];
 #pragma unroll
-          for (int p = 0; p < NP; ++p) a = fma(cur.ug[p], tt[1 + p][K], a);
+        for (int p = 0; p < NP; ++p) a = fma(cur.ug[p], tt[1 + p][K], a);
 #pragma unroll
-          for (int s = 0; s < NU; ++s) a = fma(BT[s][K], cur.ub[s] - cur.ug[s], a);
-          CT[K] = a;
-        }
+        for (int s = 0; s < NU; ++s) a = fma(BT[s][K], cur.ub[s] - cur.ug[s], a);
+        CT[K] = a;
       }
       static_for<0, 4>([&](auto jj) {
         constexpr int j = decltype(jj)::value;
@@ -430,13 +399,13 @@ struct TileBackwardB {
 #pragma unroll
           for (int s = 0; s < NU; ++s) {
             ug[s] = quad_bcast<j>(cur.ug[s]);
-            ub[s] = (PINNED || !M4Q_TILE_CBLK) ? quad_bcast<j>(cur.ub[s]) : 0.0;
+            ub[s] = PINNED ? quad_bcast<j>(cur.ub[s]) : 0.0;
             stv[s] = PINNED ? quad_bcast<j>(cur.st[s]) : 0.0;
 #pragma unroll
             for (int I = 0; I < NT; ++I) b[s][I] = quad_bcast<j>(BT[s][I]);
           }
 #pragma unroll
-          for (int K = 0; K < NT; ++K) cin[K] = M4Q_TILE_CBLK ? quad_bcast<j>(CT[K]) : 0.0;
+          for (int K = 0; K < NT; ++K) cin[K] = quad_bcast<j>(CT[K]);
           step(tb - j, ug, ub, b, stv, cin);
         }
       });

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Experiment builds that never touch the product library:  tools/build_variant.sh <name> "<shape ...|all>" [extra hipcc flags...]
-#   e.g. tools/build_variant.sh TI 16_3_1 -DM4Q_TWO_INDEX_COMPLEX=1   -> tools/bin/libTI.so
+#   e.g. tools/build_variant.sh PC all -DM4Q_DEV_PHASE_CLOCK   -> tools/bin/libPC.so
 # Recompiles the named shapes' kernel objects with the extra flags into tools/bin/obj_<name>/ and links them with the product's
 # other objects (mpc4quantum_amd/csrc/build/, which must be up to date).  Run a variant on the GPU box with
 #   M4Q_LIB=tools/bin/lib<name>.so python ...     (mpc4quantum_amd/_lib.py honours M4Q_LIB)
