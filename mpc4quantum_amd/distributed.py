@@ -431,6 +431,12 @@ def mpc_batch_sharded(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0
     gather buffer.  Tests pass a host transport and `solver`, a host callable with mpc_batch's signature, whose results take
     the same packed path."""
     from .mpc import open_session
+    # (before the transport exists: a rank that raises here has joined nothing)
+    if models is not None and kw.get("generators") is not None:
+        raise ValueError("pass models or generators (and scales), not both")
+    if kw.get("scales") is not None and (np.ndim(kw["scales"]) != 2 or np.shape(kw["scales"])[0] != np.shape(x0)[0]):
+        raise ValueError("scales must have one row per ensemble member, shape (%d, 1+m); got %s: a block of rows is what each rank "
+                         "takes" % (np.shape(x0)[0], np.shape(kw["scales"])))
     own = transport is None
     if own:
         transport = RcclComm.from_env()

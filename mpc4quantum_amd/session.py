@@ -14,6 +14,18 @@ _DTYPES = {
 }
 
 
+def check_build_models_shapes(B, dim_x, dim_u, generators, scales):
+    """The shapes m4q_session_build_models reads: generators [1+m, n, n], [1, 1+m, n, n] or [B, 1+m, n, n]; scales None or
+    [B, 1+m].  The C side takes the sizes from the session, not from the arrays: anything else would be read past its end."""
+    g = np.shape(generators)
+    k = 1 + int(dim_u)
+    if not (g == (k, dim_x, dim_x) or (len(g) == 4 and g[1:] == (k, dim_x, dim_x) and g[0] in (1, B))):
+        raise ValueError("generators must have shape (%d, %d, %d), (1, %d, %d, %d) or (%d, %d, %d, %d), got %s"
+                         % (k, dim_x, dim_x, k, dim_x, dim_x, B, k, dim_x, dim_x, g))
+    if scales is not None and np.shape(scales) != (B, k):
+        raise ValueError("scales must have shape (%d, %d), got %s" % (B, k, np.shape(scales)))
+
+
 class EnsembleSession:
     def __init__(self, B, dim_x, dim_u, order, horizon, n_steps, dt, sat, du=None, max_iter=100, warm_start=True,
                  qp_flags=None, plant_kind=_lib.PLANT_HAMILTONIAN, model_per_instance=False, plant_per_instance=False,
@@ -96,6 +108,7 @@ class EnsembleSession:
 
     def build_models(self, dt, generators, scales=None):
         """Fill the MODELS field on the device: generators [1+m, n, n] (shared) or [B, 1+m, n, n], scales [B, 1+m]."""
+        check_build_models_shapes(self.B, self.problem.dim_x, self.problem.dim_u, generators, scales)
         g = np.ascontiguousarray(generators, dtype=np.complex128)
         per = 1 if g.ndim == 4 and g.shape[0] > 1 else 0
         sc = None if scales is None else np.ascontiguousarray(scales, dtype=np.float64)

@@ -1,0 +1,227 @@
+"""CPU checks of tests/kernel_variants.py (the matrix tests/test_gpu_variant_matrix.py runs) and of the input shapes
+EnsembleSession.build_models and mpc_batch_sharded accept.
+
+The rule lines of m4q_kernels.hip and build.py must read exactly as the Python mirrors assume: a new shape changes the matrix,
+a changed rule fails here - neither can leave a compiled variant untested without notice."""
+import os
+
+import numpy as np
+import pytest
+
+from mpc4quantum_amd import configs
+from mpc4quantum_amd.library import size_of_library
+from mpc4quantum_amd.session import check_build_models_shapes
+from oracle import m4q_oracle as orc
+from tests import kernel_variants as kv
+
+
+def _src(name):
+    with open(os.path.join(kv.CSRC, name)) as f:
+        return f.read()
+
+
+# ---------------------------------------------------------------- the mirrors against the sources
+def test_rule_lines_read_as_mirrored():
+    k = _src("m4q_kernels.hip")
+    for line in ("constexpr int DD = (NX == 4) ? 2 : (NX == 9) ? 3 : (NX == 16) ? 4 : 1;",
+                 "constexpr bool SQUARE = DD * DD == NX;",
+                 "constexpr int DQ = fourth_root(NX);",
+                 "constexpr bool QUARTIC = DQ > 0;",
+                 "constexpr bool HAS_TILE = SQUARE && ORDER == 1 && NX - 1 <= 8;",
+                 "constexpr bool HAS_SG = SQUARE && ORDER == 1 && NX == 16;"):
+        assert k.count(line) == 1, line
+    # pick_kernel: !SQUARE runs PLANT_NONE on path 0 alone; path 4 only unexact where HAS_SG; path 3 only unexact where HAS_TILE
+    body = k[k.index("static int pick_kernel("):k.index("#ifndef M4Q_PLANT_ONLY\nstatic int launch_mpc")]
+    assert "if (path || plant_kind != PLANT_NONE) return unsupported;" in body
+    assert "if (path == 4 && !exact) return pick_plant<double, false, true, false, Op, true>(op, plant_kind);" in body
+    assert "if (path == 4) path = 2;" in body
+    assert "if constexpr (HAS_TILE) { if (path == 3 && !exact) return pick_plant<double, false, true, true>(op, plant_kind); }" in body
+    assert ("if (path >= 2) return exact ? pick_plant<double, true, true, false>(op, plant_kind) : "
+            "pick_plant<double, false, true, false>(op, plant_kind);") in body
+    assert ("if (path == 1) return exact ? pick_plant<double, true, false, false>(op, plant_kind) : "
+            "pick_plant<double, false, false, false>(op, plant_kind);") in body
+    assert ("return exact ? pick_plant<cplx, true, false, false>(op, plant_kind) : pick_plant<cplx, false, false, false>(op, "
+            "plant_kind);") in body
+    # pick_plant: the generator plant in the gen object alone, the process plant on quartic complex kernels alone
+    body = k[k.index("static int pick_plant("):k.index("static int pick_kernel(")]
+    assert body.count("return op.template run<S, PLANT_NONE, EXACT, false, false>();") == 1          # !SQUARE
+    assert "if (plant_kind == PLANT_GENERATOR) return op.template run<S, PLANT_GENERATOR, EXACT, TL, TILE, SG>();" in body
+    assert "if (plant_kind == PLANT_HAMILTONIAN) return op.template run<S, PLANT_HAMILTONIAN, EXACT, TL, TILE, SG>();" in body
+    assert ("if constexpr (QUARTIC && std::is_same<S, cplx>::value && !TL && !TILE && !SG) return op.template run<S, PLANT_PROCESS, "
+            "EXACT, false, false>();") in body
+    assert "return op.template run<S, PLANT_NONE, EXACT, TL, TILE, SG>();" in body
+    b = _src("build.py")
+    assert b.count("d = {4: 2, 9: 3, 16: 4}.get(nx)") == 1 and b.count("if d and not plant_only:") == 1
+    assert '"-DM4Q_VARIANT_GEN"' in b
+
+
+def test_mirrors_agree_with_the_rule_text():
+    for nx in (4, 8, 9, 16):
+        assert kv.square(nx) == (nx in (4, 9, 16)) and kv.quartic(nx) == (nx == 16)
+    assert [kv.fourth_root(n) for n in (1, 4, 8, 9, 16, 81)] == [1, 0, 0, 0, 2, 3]
+    assert kv.has_tile(4, 1) and kv.has_tile(9, 1) and not kv.has_tile(16, 1) and not kv.has_tile(4, 2)
+    assert kv.has_sg(16, 1) and not kv.has_sg(16, 2) and not kv.has_sg(9, 1)
+
+
+# ---------------------------------------------------------------- the matrix
+def test_spot_check_of_the_cells():
+    cells = kv.closed_loop_cells()
+    ids = [kv.cell_id(c) for c in cells]
+    assert len(ids) == len(set(ids))
+    shape = {}
+    for c in cells:
+        shape.setdefault((c.nx, c.nu, c.order), []).append(c)
+    # (8, 2, 1): the complex kernel with no plant, clipped and exact - nothing else is built
+    assert sorted((c.path, c.exact, c.plant) for c in shape[(8, 2, 1)]) == [(kv.COMPLEX, False, kv.NONE), (kv.COMPLEX, True, kv.NONE)]
+    # (16, 2, 1) is plant-only: no closed-loop cell, plant cells only
+    assert (16, 2, 1) not in shape
+    entry = kv.entry_point_cells()
+    assert [(c.kind, c.mode) for c in entry if (c.nx, c.nu) == (16, 2)] == [("plant", kv.HAMILTONIAN), ("plant", kv.GENERATOR)]
+    # the shared-generator kernel at (16, 1, 1), clipped only, under each plant it is built with; none at (16, 1, 2)
+    sg = [c for c in shape[(16, 1, 1)] if c.path == kv.SG]
+    assert sorted(c.plant for c in sg) == sorted([kv.NONE, kv.HAMILTONIAN, kv.GENERATOR]) and not any(c.exact for c in sg)
+    assert not any(c.path == kv.SG for c in shape[(16, 1, 2)])
+    # the process plant: complex path, quartic shapes, both solves
+    proc = sorted((c.nx, c.nu, c.order, c.path, c.exact) for c in cells if c.plant == kv.PROCESS)
+    assert proc == sorted((16, nu, o, kv.COMPLEX, e) for nu, o in ((1, 1), (1, 2), (1, 3), (1, 4), (3, 1)) for e in (False, True))
+    # tile cells (clipped backward sweep, exact pinned sweep) exactly where HAS_TILE
+    assert sorted({(c.nx, c.order) for c in cells if c.path == kv.TILE}) == [(4, 1), (9, 1)]
+    assert all(c.plant != kv.GENERATOR or kv.square(c.nx) for c in cells)
+    # per shape: (clipped paths + exact paths) x (none, hamiltonian, generator) + the process cells
+    for (nx, nu, o), cs in shape.items():
+        n_paths = len(kv.clipped_paths(nx, o)) + len(kv.exact_paths(nx, o))
+        expect = n_paths * (3 if kv.square(nx) else 1) + (2 if kv.quartic(nx) else 0)
+        assert len(cs) == expect, (nx, nu, o)
+    qp = {(c.nx, c.nu) for c in entry if c.kind == "qp"}
+    assert qp == {(4, 1), (4, 2), (9, 2), (16, 3), (16, 1), (8, 2)}
+    assert {(c.nx, c.nu, c.order) for c in entry if c.kind == "discretize"} == {
+        (4, 1, 1), (4, 1, 2), (4, 2, 1), (9, 2, 1), (9, 2, 2), (16, 3, 1), (16, 1, 1), (16, 1, 2), (8, 2, 1)}
+
+
+def test_every_closed_loop_shape_has_a_scenario():
+    for nx, nu, order, plant_only in kv.shapes():
+        if plant_only:
+            with pytest.raises(KeyError):
+                kv.scenario(nx, nu, order)
+        else:
+            assert kv.scenario(nx, nu, order)["dim_x"] == nx
+
+
+def _density(x, d):
+    rho = np.reshape(x, (d, d))
+    return np.abs(rho - rho.conj().T).max() <= 1e-14 and abs(np.trace(rho) - 1) <= 1e-14
+
+
+@pytest.mark.parametrize("shape", [s[:3] for s in kv.shapes() if not s[3]], ids=lambda s: "%d-%d-%d" % s)
+def test_scenario_is_well_formed(shape):
+    """States and targets Hermitian with unit trace (two of them side by side at n = 8); models equal the oracle's expansion of the
+    scaled generators; every operator has the shape the C ABI reads; bounds and sizes as the matrix wants them."""
+    nx, nu, order = shape
+    p = kv.scenario(nx, nu, order)
+    B, n, m, T, ns = p["batch"], p["dim_x"], p["dim_u"], p["horizon"], p["n_steps"]
+    assert (B, T, ns) == (kv.BATCH, kv.HORIZON, kv.STEPS) and T % 4 != 0 and T > 4
+    P = size_of_library(order, m) - 1
+    assert p["models"].shape == (B, n, n * (1 + P)) and p["generators"].shape == (1 + m, n, n) and p["scales"].shape == (B, 1 + m)
+    assert p["x0"].shape == (B, n) and p["X_targ"].shape == (n, ns + T + 1) and p["U_targ"].shape == (m, ns + T)
+    assert p["Q"].shape == p["Qf"].shape == (n, n) and p["R"].shape == (m, m) and p["sat"] > 0
+    parts = [(slice(0, 4), 2), (slice(4, 8), 2)] if n == 8 else [(slice(0, n), kv.dd(n))]
+    for sl, d in parts:
+        assert all(_density(x[sl], d) for x in p["x0"])
+        assert all(_density(x[sl], d) for x in p["X_targ"].T)
+    assert len({tuple(np.round(x, 12)) for x in p["x0"]}) == B                      # distinct members
+    for b in range(B):
+        ref = orc.discretize_homogeneous([p["scales"][b, k] * p["generators"][k] for k in range(1 + m)], p["dt"], order)
+        assert np.abs(p["models"][b] - ref).max() <= 1e-13 * max(1.0, np.abs(ref).max())
+    assert np.abs(p["models"][0] - p["models"][1]).max() > 1e-6
+    if kv.square(n):
+        d = kv.dd(n)
+        assert p["plant_op0"].shape == (1, d, d) and p["plant_ops"].shape == (1, m, d, d)
+        assert p["gen_op0"].shape == (1, n, n) and p["gen_ops"].shape == (1, m, n, n)
+        # the generator plant is trace preserving (so the traceless path applies) and dissipative (not a Liouvillian)
+        eye = np.eye(d).reshape(-1)
+        assert np.abs(eye @ p["gen_op0"][0]).max() <= 1e-14 and np.abs(p["gen_op0"][0] @ eye).max() > 1e-3
+    else:
+        assert p["gen_op0"].shape == (1, n, n) and p["gen_ops"].shape == (1, m, n, n)
+
+
+@pytest.mark.parametrize("nu,order", sorted({(c.nu, c.order) for c in kv.closed_loop_cells() if c.plant == kv.PROCESS}))
+def test_process_scenario_is_well_formed(nu, order):
+    p = kv.process_scenario(nu, order)
+    B, m = p["batch"], p["dim_u"]
+    P = size_of_library(order, m) - 1
+    assert m == nu and p["models"].shape == (1, 16, 16 * (1 + P)) and p["U_targ"].shape[0] == m and p["R"].shape == (m, m)
+    assert p["x0"].shape == (B, 16) and p["plant_op0"].shape == (B, 2, 2) and p["plant_ops"].shape == (1, m, 2, 2)
+    assert p["gen_op0"].shape == (B, 16, 16) and p["gen_ops"].shape == (1, m, 16, 16)
+    ref = orc.discretize_homogeneous(list(p["generators"]), p["dt"], order)
+    assert np.abs(p["models"][0] - ref).max() <= 1e-13
+    for x in p["x0"]:
+        M = x.reshape(4, 4)
+        assert np.abs(M @ M.conj().T - np.eye(4)).max() <= 1e-14            # U (x) U^* is unitary
+    assert len({round(float(h[0, 0].real), 12) for h in p["plant_op0"]}) == B   # detuned members
+    assert np.abs(p["U_targ"]).max() > p["sat"]                              # the reference ramps past the bound
+
+
+# ---------------------------------------------------------------- build_models / mpc_batch_sharded input shapes
+def test_build_models_shape_check():
+    B, n, m = 5, 16, 3
+    g = np.zeros((1 + m, n, n))
+    sc = np.ones((B, 1 + m))
+    for gens in (g, g[None], np.stack([g] * B)):
+        for scales in (None, sc):
+            check_build_models_shapes(B, n, m, gens, scales)
+    bad = [(g, sc[0]), (g, sc[:, 0]), (g, sc[:-1]), (g, np.ones((B, m))), (g, sc[None]),       # scales
+           (np.stack([g] * (B - 1)), None), (np.stack([g] * 2), sc), (g[:-1], None), (g[None, None], None),
+           (np.zeros((1 + m, n, n - 1)), None), (np.zeros((1 + m, 9, 9)), None)]                  # generators
+    for gens, scales in bad:
+        with pytest.raises(ValueError):
+            check_build_models_shapes(B, n, m, gens, scales)
+
+
+class _Rank1Of2:
+    """A host transport as rank 1 of two: its block is [3, 5) of five members, the gather goes to rank 0 (None here)."""
+    on_device = False
+    rank, world = 1, 2
+
+    def gather_host(self, buf, dst):
+        return None
+
+    def wait(self, slot=-1):
+        pass
+
+
+def _sharded(**kw):
+    import mpc4quantum_amd as m4q
+    from mpc4quantum_amd.distributed import mpc_batch_sharded
+    p = configs.build(4, batch=5, horizon=4, n_steps=2)
+    seen = {}
+
+    def solver(x0, models, dim_u, order, X_targ, U_targ, clock, op0, ops, Q, R, Qf, sat, du, **skw):
+        seen.update(skw, x0=x0)
+        b = len(x0)
+        return {"xs": np.zeros((b, 16, 3), complex), "us": np.zeros((b, 3, 2)), "exit_codes": np.zeros(b, np.int32),
+                "steps_done": np.full(b, 2, np.int32), "qp_solves": np.ones((b, 2), np.int32)}
+    args = dict(generators=p["generators"], scales=p["scales"])
+    args.update(kw)
+    models = args.pop("models", None)
+    out = mpc_batch_sharded(p["x0"], models, 3, 1, p["X_targ"], p["U_targ"], m4q.StepClock(p["dt"], 4, 2), p["plant_op0"],
+                            p["plant_ops"], p["Q"], p["R"], p["Qf"], p["sat"], p["du"], transport=_Rank1Of2(), solver=solver, **args)
+    return p, out, seen
+
+
+def test_sharded_scales_are_sliced_by_member():
+    p, out, seen = _sharded()
+    assert out is None                                                       # not the gathering rank
+    assert np.array_equal(seen["scales"], p["scales"][3:5]) and np.array_equal(seen["x0"], p["x0"][3:5])
+    assert np.array_equal(seen["generators"], p["generators"])               # one shared set: every rank gets it whole
+    per = np.stack([p["generators"] * (1 + 0.1 * b) for b in range(5)])
+    _, _, seen = _sharded(generators=per)
+    assert np.array_equal(seen["generators"], per[3:5])
+
+
+def test_sharded_rejects_bad_scales_and_models_with_generators():
+    p = configs.build(4, batch=5, horizon=4, n_steps=2)
+    for scales in (p["scales"][0], p["scales"][:, 0], p["scales"][:4], p["scales"].T):
+        with pytest.raises(ValueError, match="scales"):
+            _sharded(scales=scales)
+    with pytest.raises(ValueError, match="not both"):
+        _sharded(models=np.zeros((1, 16, 64), complex))
