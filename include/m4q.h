@@ -92,7 +92,8 @@ extern "C" {
  * such a session on its per-member models.  Uploaded models (m4q_session_upload) always do. */
 #define M4Q_OPT_NO_SG 16
 
-/* exit codes per instance (mpc.py:130,195,202,291): 0 normal, 1 exit_condition (host side),
+/* exit codes per instance (mpc.py:130,195,202,291): 0 normal, 1 exit_condition (set from the host with m4q_session_set_codes, or
+ *   by the kernel itself for a condition given to m4q_session_set_exit),
  * 2 solver gave up (mpc.py:183-197 turns a cvxpy/OSQP warning into this; here: an M4Q_QP_EXACT_BOX solve that stopped at
  *   its iteration cap - the clipped Riccati solve cannot produce it), 3 non-finite objective (mpc.py:200-203; also where
  *   the reference would raise on NaN data: a batched engine cannot raise for one member).
@@ -229,6 +230,21 @@ M4Q_API int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end
 M4Q_API int m4q_session_sync(m4q_session* s);
 /* mark instances finished from the host (exit_condition, mpc.py:289-292): codes [B] i32, nonzero = stop */
 M4Q_API int m4q_session_set_codes(m4q_session* s, const int32_t* codes);
+/* exit condition the closed-loop kernel evaluates itself (mpc.py:289-292 for one family of conditions), for every member on its own,
+ * after each MPC step that completed with code 0:
+ *     q = Re((x - f)^H W (x - f)),  fires when q < thr (M4Q_EXIT_BELOW) or q > thr (M4Q_EXIT_ABOVE)
+ * with x = xs[step] (M4Q_EXIT_PREV: the state the step started from) or xs[step + 1] (M4Q_EXIT_NEXT: the state it produced - on a
+ * step that is not measured, the model's prediction), exactly as stored in XS.  A member it fires for ends with exit code 1 and
+ * steps_done = step: that step's entries are dropped, as mpc.py:298-304 drops them.  W [n][n] c (not required to be Hermitian),
+ * target [B|1][n] c, thr [B|1] r are host buffers, copied into buffers the session owns; the condition holds for the launches that
+ * follow.  mode 0 clears it.  M4Q_E_BADARG for any other combination of bits or a missing array, M4Q_E_UNSUPPORTED for a
+ * M4Q_PLANT_NONE session (its host supplies the states and evaluates its own condition). */
+#define M4Q_EXIT_PREV 1
+#define M4Q_EXIT_NEXT 2
+#define M4Q_EXIT_BELOW 4
+#define M4Q_EXIT_ABOVE 8
+M4Q_API int m4q_session_set_exit(m4q_session* s, int32_t mode, const double* W, const double* target, int32_t target_per_instance,
+                                 const double* thr, int32_t thr_per_instance);
 /* kernel time of the launches since the last call, from HIP events on the session stream */
 M4Q_API int m4q_session_kernel_ms(m4q_session* s, double* total_ms, int32_t* launches);
 /* arithmetic path the uploaded problem will run on: 0 complex, 1 real (Hermitian operator basis, d*d coordinates),

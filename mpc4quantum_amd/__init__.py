@@ -2,6 +2,7 @@
 
 Same public names as the reference package (mpc4quantum/__init__.py:3-7 star-exports experiment,
 linearize, model, mpc, vectorize), backed by hand-written HIP kernels in libm4q_hip.so."""
+from .exit_condition import QuadraticExit  # noqa: F401
 from .experiment import (Experiment, LExperiment, QCoupledExperiment, QExperiment, QExperiment32, QSynthesis,  # noqa: F401
                          isqrt, plant_step_batch, process_dim, split_blocks)
 from .library import (create_library, create_library_from_list, create_power_list, diff_library, krtimes,  # noqa: F401

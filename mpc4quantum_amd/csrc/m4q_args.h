@@ -47,7 +47,14 @@ struct MpcArgs {
   // shared-generator sessions (path 4): dt L_k on the recursion's coordinates, [1 + m][ns][ns] doubles, and the members' scales
   // [B][1 + m]; the kernel forms A_i = I + s_i0 dt L_0 itself and never reads `models`
   M4Q_P(const double) gens; M4Q_P(const double) scales;
+  // exit condition (m4q_session_set_exit; device plants only): exit_mode is 0 (none) or one of EXIT_PREV / EXIT_NEXT with one of
+  // EXIT_BELOW / EXIT_ABOVE.  q = Re((x - f)^H W (x - f)) of the stored state x = xs[step] (PREV) or xs[step + 1] (NEXT);
+  // W [n][n] complex, f [B|1][n] complex (exit_tstride n or 0), thresholds [B|1] (exit_thr_stride 1 or 0)
+  int exit_mode;
+  M4Q_P(const cplx) exit_W; M4Q_P(const cplx) exit_target; long exit_tstride;
+  M4Q_P(const double) exit_thr; long exit_thr_stride;
 };
+enum : int { EXIT_PREV = 1, EXIT_NEXT = 2, EXIT_BELOW = 4, EXIT_ABOVE = 8 };     // (mirrored in include/m4q.h: M4Q_EXIT_*)
 
 struct LinArgs {
   int B, T;

@@ -311,6 +311,10 @@ struct m4q_session {
   bool force_complex = false;
   bool launched = false;        // a closed-loop launch has been enqueued since the watchdog flag was last read
   bool targ_const = false;      // every column of X_targ equals the first (per member, if per-member): xbar does not depend on t
+  // exit condition (m4q_session_set_exit): M4Q_EXIT_* bits (0: none), W [n][n] c, target [B|1][n] c, thresholds [B|1]
+  int exit_mode = 0;
+  bool exit_target_per = false, exit_thr_per = false;
+  DevBuf exit_W, exit_target, exit_thr;
   bool use_real(bool diag) const {
     return !force_complex && diag && herm_ok[M4Q_F_MODELS] && herm_ok[M4Q_F_X0] && herm_ok[M4Q_F_X_TARG] &&
            herm_ok[M4Q_F_Q] && herm_ok[M4Q_F_QF] && herm_ok[M4Q_F_R];
@@ -734,6 +738,10 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   a.dt = p.dt; a.sat = p.sat; a.du = p.du; a.ls_tol = p.ls_tol;
   a.models = path >= 2 ? s->t_models.p : real_path ? s->r_models.p : s->f[M4Q_F_MODELS].p;
   a.gens = (const double*)s->sg_gens.p; a.scales = (const double*)s->sg_scales.p;
+  a.exit_mode = s->exit_mode;
+  a.exit_W = (const cplx*)s->exit_W.p;
+  a.exit_target = (const cplx*)s->exit_target.p; a.exit_tstride = s->exit_target_per ? (long)n : 0;
+  a.exit_thr = (const double*)s->exit_thr.p; a.exit_thr_stride = s->exit_thr_per ? 1 : 0;
   a.model_stride = p.model_per_instance ? (long)(ns * ns * (1 + P)) : 0;
   a.x0c = (const cplx*)s->f[M4Q_F_X0].p;
   a.x0s = path >= 2 ? s->t_x0.p : real_path ? s->r_x0.p : s->f[M4Q_F_X0].p;
@@ -796,6 +804,36 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   HIP_TRY(hipEventRecord(e1, s->stream));
   s->pending.emplace_back(e0, e1);
   s->launched = true;
+  return 0;
+}
+
+int m4q_session_set_exit(m4q_session* s, int32_t mode, const double* W, const double* target, int32_t target_per_instance,
+                         const double* thr, int32_t thr_per_instance) {
+  if (!s) return fail(M4Q_E_BADARG, "m4q_session_set_exit: null session");
+  const int side = mode & (M4Q_EXIT_PREV | M4Q_EXIT_NEXT), sense = mode & (M4Q_EXIT_BELOW | M4Q_EXIT_ABOVE);
+  if (mode != 0 && ((mode & ~(M4Q_EXIT_PREV | M4Q_EXIT_NEXT | M4Q_EXIT_BELOW | M4Q_EXIT_ABOVE)) ||
+                    (side != M4Q_EXIT_PREV && side != M4Q_EXIT_NEXT) || (sense != M4Q_EXIT_BELOW && sense != M4Q_EXIT_ABOVE)))
+    return fail(M4Q_E_BADARG, "m4q_session_set_exit: mode 0x%x is not 0 or one of M4Q_EXIT_PREV / NEXT with one of M4Q_EXIT_BELOW / "
+                "ABOVE", mode);
+  if (mode != 0 && (!W || !target || !thr)) return fail(M4Q_E_BADARG, "m4q_session_set_exit: W, target and thr are required");
+  if (mode != 0 && s->prob.plant_kind == M4Q_PLANT_NONE)
+    return fail(M4Q_E_UNSUPPORTED, "m4q_session_set_exit: M4Q_PLANT_NONE sessions take their states from the host, which evaluates "
+                "the exit condition itself");
+  // a launch still in flight may read the buffers about to be replaced
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  s->exit_mode = 0;
+  s->exit_W.release(); s->exit_target.release(); s->exit_thr.release();
+  if (mode == 0) return 0;
+  const size_t n = s->prob.dim_x, B = s->B, C = 16;
+  const size_t tb = (target_per_instance ? B : 1) * n * C, hb = (thr_per_instance ? B : 1) * 8;
+  int rc;
+  if ((rc = s->exit_W.alloc(n * n * C)) || (rc = s->exit_target.alloc(tb)) || (rc = s->exit_thr.alloc(hb))) return rc;
+  HIP_TRY(hipMemcpy(s->exit_W.p, W, n * n * C, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->exit_target.p, target, tb, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->exit_thr.p, thr, hb, hipMemcpyHostToDevice));
+  s->exit_target_per = target_per_instance != 0;
+  s->exit_thr_per = thr_per_instance != 0;
+  s->exit_mode = mode;
   return 0;
 }
 

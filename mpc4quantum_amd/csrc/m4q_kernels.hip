@@ -1022,6 +1022,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
         iter = 0;
         step = fail ? row_end : step + 1;
       }
+      if constexpr (PLANT != PLANT_NONE) {
+        // exit condition (m4q_session_set_exit), once the step is complete: q = Re((x - f)^H W (x - f)) of the state just stored
+        // (NEXT: xs[step + 1] - the plant's, or the model's on a step that is not measured) or of the one the step started from
+        // (PREV: xs[step], x0 at step 0), read back as stored: complex, original basis, on every path.  A row it fires for ends its
+        // run with code 1 and steps_done = the step just taken, whose entries are dropped (mpc.py:289-304).  Mode 0: one scalar branch.
+        const int xmode = a->exit_mode;
+        if (xmode != 0) {
+          const int s0 = step - 1;                                 // (ok rows: the step just completed)
+          const bool prev = (xmode & EXIT_PREV) != 0;
+          const cplx x = !ok ? czero() : (prev && s0 == 0) ? gld(a->x0c, b * NX + jio)
+                                                           : gld(a->xs, b * sXs + (long)(prev ? s0 : s0 + 1) * NX + jio);
+          const cplx d = csub(x, ok ? gld(a->exit_target, b * a->exit_tstride + jio) : czero());
+          const M4Q_GLOBAL cplx* Wr = a->exit_W + jio * NX;       // row jio of W (shared, small) against the row's d
+          cplx y = czero();
+          static_for<0, NX>([&](auto k) { cmac(y, gld(Wr, decltype(k)::value), bcast<decltype(k)::value>(d)); });
+          const double q = rowsum<NX>(dot_re(d, y));
+          const double thr = ok ? gld(a->exit_thr, b * a->exit_thr_stride) : 0.0;
+          if (ok && ((xmode & EXIT_ABOVE) ? q > thr : q < thr)) {
+            code = 1;
+            done_steps = s0;
+            step = row_end;
+          }
+        }
+      }
       wave_sync();
       if constexpr (PLANT == PLANT_NONE) {
         // the caller writes xs[step+1] before the next launch; inside one launch carry what is there

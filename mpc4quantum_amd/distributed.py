@@ -429,14 +429,17 @@ def mpc_batch_sharded(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0
     (xs [B, n, cols], us [B, m, n_steps], exit_codes, steps_done, qp_solves), the others None.
     transport: an RcclComm (default: RcclComm.from_env()) - the block runs on the rank's GPU with its outputs bound into the
     gather buffer.  Tests pass a host transport and `solver`, a host callable with mpc_batch's signature, whose results take
-    the same packed path."""
-    from .mpc import open_session
+    the same packed path.  exit_condition (a QuadraticExit) is sliced like the ensemble: each rank's block gets its members' targets
+    and thresholds where those are per member."""
+    from .mpc import check_batch_exit, open_session
     # (before the transport exists: a rank that raises here has joined nothing)
     if models is not None and kw.get("generators") is not None:
         raise ValueError("pass models or generators (and scales), not both")
     if kw.get("scales") is not None and (np.ndim(kw["scales"]) != 2 or np.shape(kw["scales"])[0] != np.shape(x0)[0]):
         raise ValueError("scales must have one row per ensemble member, shape (%d, 1+m); got %s: a block of rows is what each rank "
                          "takes" % (np.shape(x0)[0], np.shape(kw["scales"])))
+    check_batch_exit(kw.get("exit_condition"), np.shape(x0)[0], np.shape(x0)[1], kw.get("plant_kind", _lib.PLANT_HAMILTONIAN),
+                     "mpc_batch_sharded")
     own = transport is None
     if own:
         transport = RcclComm.from_env()
@@ -445,6 +448,9 @@ def mpc_batch_sharded(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0
     B, n = x0.shape
     ns = clock.n_steps
     lo, hi = shard_bounds(B, rank, world)
+    if kw.get("exit_condition") is not None:
+        kw = dict(kw)
+        kw["exit_condition"] = kw["exit_condition"].block(lo, hi, B)
     counts = [shard_bounds(B, r, world)[1] - shard_bounds(B, r, world)[0] for r in range(world)]
     rows = max(counts)
     if transport.on_device and min(counts) == 0:

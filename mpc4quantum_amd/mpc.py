@@ -9,6 +9,7 @@ the target window (:276-277), exit codes and the dropped last entry (:294-304)."
 import numpy as np
 
 from . import _lib
+from .exit_condition import QuadraticExit, require_device_exit
 from .experiment import Experiment, QExperiment, QSynthesis
 from .library import krtimes
 from .linearize import WrapModel
@@ -142,6 +143,13 @@ def _trim(xs, us, code, done):
     return [xs[:, :done + 1], us[:, :done] if done > 0 else None]
 
 
+def _runs_fused(experiment, exit_condition, streaming):
+    """mpc() keeps the whole loop in one launch when the plant runs on the device and the exit condition, if any, is one the kernel
+    evaluates (a QuadraticExit); a plain callable, a host plant or streaming updates take one launch per MPC step."""
+    return ((_native_plant(experiment) or isinstance(experiment, QSynthesis)) and not streaming
+            and (exit_condition is None or isinstance(exit_condition, QuadraticExit)))
+
+
 def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sat=None, du=None, max_iter=100,
         exit_condition=None, streaming=False, warm_start=True, progress_bar=True, verbose=False, exact_qp=False,
         qp_flags=None):
@@ -151,7 +159,9 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
     qp_flags (extension): M4Q_QP_* bits; _lib.QP_REF_LQR runs the loop around the arithmetic of the reference's lqr.py as
     written, which is what tests/golden/mpc_loop.npz (the reference's own mpc.py around its own lqr.py) pins.
     A QSynthesis experiment (gate synthesis) runs on its process vector with the identity as the loop's lift: x0, the states
-    returned and the states exit_condition sees are process vectors vec_r(U (x) U^*)."""
+    returned and the states exit_condition sees are process vectors vec_r(U (x) U^*).
+    exit_condition: any callable exit_condition(x_next, x, u) runs the loop on the host, one launch per MPC step; a QuadraticExit
+    with a native plant or QSynthesis (and no streaming) keeps the loop fused: the kernel evaluates it after every step."""
     mf = int(clock.measure_freq)
     x0 = np.asarray(x0, dtype=np.complex128).reshape(-1)
     lift, proj = _loop_maps(experiment)
@@ -163,7 +173,7 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
     X_targ = np.atleast_2d(np.asarray(X_targ))
     U_targ = np.atleast_2d(np.asarray(U_targ))
     cols = min(X_targ.shape[1], ns + T + 1)
-    fused = (_native_plant(experiment) or isinstance(experiment, QSynthesis)) and exit_condition is None and not streaming
+    fused = _runs_fused(experiment, exit_condition, streaming)
     kind = experiment.plant_kind if fused else _lib.PLANT_NONE
     sess = EnsembleSession(1, n, dim_u, order, T, ns, clock.dt, sat, du, max_iter, warm_start, qp_flags=qp_flags,
                            plant_kind=kind, target_cols=cols, measure_freq=mf, exact_qp=exact_qp)
@@ -171,6 +181,8 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
         op0, ops = experiment.operators() if fused else (None, None)
         sess.load_problem(np.hstack([A_x, A_u])[None], lift_x0[None], X_targ, U_targ, Q, R, Qf, op0, ops)
         if fused:
+            if exit_condition is not None:
+                sess.set_exit_condition(exit_condition)
             sess.run(0, ns)
             res = sess.results()
             code, done = int(res["exit_codes"][0]), int(res["steps_done"][0])
@@ -246,16 +258,27 @@ class _HeldControl:
         return self.y[..., idx]
 
 
+def check_batch_exit(cond, B, n, plant_kind, where):
+    """The batched entry points take None or a QuadraticExit that fits the ensemble: TypeError / ValueError before any device call."""
+    require_device_exit(cond, where)
+    if cond is not None:
+        cond.check(B, n)
+        if plant_kind == _lib.PLANT_NONE:
+            raise ValueError("%s: an exit condition needs a device plant (with PLANT_NONE the host supplies the states)" % where)
+
+
 def open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_ops, Q, R, Qf, sat, du=None,
                  max_iter=100, warm_start=True, qp_flags=None, plant_kind=_lib.PLANT_HAMILTONIAN, device=-1,
                  force_complex=False, exact_qp=False, traceless=True, tile=None, generators=None, scales=None,
-                 shared_generators=None):
+                 shared_generators=None, exit_condition=None):
     """An EnsembleSession loaded with mpc_batch's arguments (everything resident in HBM, nothing run yet).
     models = None with generators [1+m, n, n] (or [B, 1+m, n, n]) and optional scales [B, 1+m]: the members' models are built on the
     device (discretize_homogeneous of the scaled generators, vectorize.py:8-49), and a set of SHARED generators at order 1 lets the
-    closed loop run on them directly where that kernel exists (d = 4; EnsembleSession(shared_generators=...))."""
+    closed loop run on them directly where that kernel exists (d = 4; EnsembleSession(shared_generators=...)).
+    exit_condition: None or a QuadraticExit the kernel evaluates for every member (EnsembleSession.set_exit_condition)."""
     x0 = np.ascontiguousarray(x0, dtype=np.complex128)
     Bn, n = x0.shape
+    check_batch_exit(exit_condition, Bn, n, plant_kind, "open_session")
     if models is None:
         if generators is None:
             raise TypeError("models is None: pass generators (and scales) to have the models built on the device")
@@ -286,6 +309,8 @@ def open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, pla
         if models is None:
             sess.build_models(clock.dt, generators, scales)
         sess.load_problem(models, x0, X_targ, U_targ, Q, R, Qf, op0, ops)
+        if exit_condition is not None:
+            sess.set_exit_condition(exit_condition)
     except Exception:
         sess.close()
         raise
@@ -294,16 +319,19 @@ def open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, pla
 
 def mpc_batch(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_ops, Q, R, Qf, sat, du=None,
               max_iter=100, warm_start=True, qp_flags=None, plant_kind=_lib.PLANT_HAMILTONIAN, device=-1,
-              force_complex=False, exact_qp=False, traceless=True, tile=None, generators=None, scales=None, shared_generators=None):
+              force_complex=False, exact_qp=False, traceless=True, tile=None, generators=None, scales=None, shared_generators=None,
+              exit_condition=None):
     """B independent closed loops in one launch.
     x0 [B, n]; models [B|1, n, n(1+P)] (or None with generators / scales: built on the device, see open_session);
     X_targ (n, cols) / U_targ (m, cols) shared (or [B, ...] each);
     plant_op0 [B|1, k, k], plant_ops [B|1, m, k, k] (k = d; plant_kind=_lib.PLANT_PROCESS: x0 and the targets are process vectors
     of n = d^4 entries and k = d, the gate's Hamiltonians - that plant always runs the complex path).  Returns a dict: xs [B, n, n_steps+1], us [B, m, n_steps]
-    (entries beyond steps_done are not meaningful), exit_codes, steps_done, qp_solves [B, n_steps]."""
+    (entries beyond steps_done are not meaningful), exit_codes, steps_done, qp_solves [B, n_steps].
+    exit_condition: None or a QuadraticExit, evaluated on the device; a member it stops has exit code 1 and steps_done = the step
+    after which it fired (that step's entries are dropped, as mpc() drops them)."""
     sess = open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_ops, Q, R, Qf, sat, du, max_iter,
                         warm_start, qp_flags, plant_kind, device, force_complex, exact_qp, traceless, tile, generators, scales,
-                        shared_generators)
+                        shared_generators, exit_condition)
     try:
         sess.run(0, clock.n_steps)
         res = sess.results()

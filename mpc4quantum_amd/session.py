@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .exit_condition import require_device_exit
 
 _DTYPES = {
     _lib.F_MODELS: np.complex128, _lib.F_X0: np.complex128, _lib.F_X_TARG: np.complex128, _lib.F_U_TARG: np.float64,
@@ -114,6 +115,21 @@ class EnsembleSession:
         sc = None if scales is None else np.ascontiguousarray(scales, dtype=np.float64)
         _lib.check(self._L.m4q_session_build_models(self._h, float(dt), g.ctypes.data_as(_lib._dp), per,
                                                     sc.ctypes.data_as(_lib._dp) if sc is not None else None))
+
+    def set_exit_condition(self, cond):
+        """Have the kernel end each member with exit code 1 once its QuadraticExit fires (m4q_session_set_exit); None clears it.
+        Applies to the launches that follow; needs a device plant."""
+        L = self._L
+        if cond is None:
+            _lib.check(L.m4q_session_set_exit(self._h, 0, None, None, 0, None, 0))
+            return
+        require_device_exit(cond, "EnsembleSession.set_exit_condition")
+        cond.check(self.B, self.problem.dim_x)
+        W = np.ascontiguousarray(cond.W, dtype=np.complex128)
+        f = np.ascontiguousarray(cond.target, dtype=np.complex128)
+        thr = np.ascontiguousarray(cond.thr, dtype=np.float64).reshape(-1)
+        _lib.check(L.m4q_session_set_exit(self._h, cond.mode, W.ctypes.data_as(_lib._dp), f.ctypes.data_as(_lib._dp),
+                                          int(f.ndim == 2), thr.ctypes.data_as(_lib._dp), int(cond.thr.ndim == 1)))
 
     def run(self, step_begin=0, step_end=None):
         _lib.check(self._L.m4q_session_run(self._h, int(step_begin), int(self.problem.n_steps if step_end is None else step_end)))
