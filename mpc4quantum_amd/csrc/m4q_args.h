@@ -20,6 +20,27 @@ namespace m4q {
 
 struct cplx;
 
+// QP semantics flags (mirrored in include/m4q.h: M4Q_QP_*; the last two are internal, set by the host)
+enum : int {
+  QP_REF_LQR = 1,   // reproduce lqr.py as written (no Delta, xbar_{t+1}==xbar_t, cost built on xbar, absolute cost)
+  QP_DU_BAND = 2,   // clip the first control to u_prev +- du as well (optimize.py:29-30)
+  QP_EXACT_BOX = 4, // solve the box-constrained QP to optimality (projected Newton) instead of clipping the Riccati rollout
+  QP_TARG_CONST = 256,   // internal (set by the host when every column of X_targ is the same): xbar_t does not depend on t
+  QP_NO_TILE = 512,      // internal (the session may not take PATH_TILE: the exact traceless kernel holds both forms of the pinned sweep)
+};
+
+// Arithmetic paths of the closed loop (m4q_session_path returns these values; session.path_detail() indexes by them)
+enum Path : int {
+  PATH_COMPLEX = 0,     // complex recursion on vec(rho): any model
+  PATH_REAL = 1,        // real recursion in the Hermitian operator basis (n coordinates)
+  PATH_TRACELESS = 2,   // real recursion on the n - 1 traceless coordinates
+  PATH_TILE = 3,        // PATH_TRACELESS with the backward sweep (clipped) / the pinned sweep (exact) on matrix-core tiles
+  PATH_SG = 4,          // PATH_TRACELESS, clipped solve, on shared generators instead of per-member models
+};
+// Coordinate systems the recursion's inputs are held in
+enum Coords : int { COORDS_COMPLEX = 0, COORDS_HERM = 1, COORDS_TRACELESS = 2 };
+constexpr Coords coords_of(Path p) { return p == PATH_COMPLEX ? COORDS_COMPLEX : p == PATH_REAL ? COORDS_HERM : COORDS_TRACELESS; }
+
 // Arrays marked S are complex (cplx) on the general path and double on the real path (models that preserve
 // Hermiticity, expressed in the Hermitian operator basis of m4q_mpc.h); the host picks the kernel.
 struct MpcArgs {
@@ -44,7 +65,7 @@ struct MpcArgs {
   M4Q_P(int) head_done;                           // [B] set when an instance's head item (steps < 2) has been published; zeroed likewise
   unsigned long long deadline_ticks;        // watchdog: the launch abandons itself (queue[1] = 1) once s_memrealtime (100 MHz) has
                                             // advanced this far since the wavefront started; every wavefront reaches this exit
-  // shared-generator sessions (path 4): dt L_k on the recursion's coordinates, [1 + m][ns][ns] doubles, and the members' scales
+  // shared-generator sessions (PATH_SG): dt L_k on the recursion's coordinates, [1 + m][ns][ns] doubles, and the members' scales
   // [B][1 + m]; the kernel forms A_i = I + s_i0 dt L_0 itself and never reads `models`
   M4Q_P(const double) gens; M4Q_P(const double) scales;
   // exit condition (m4q_session_set_exit; device plants only): exit_mode is 0 (none) or one of EXIT_PREV / EXIT_NEXT with one of
@@ -100,17 +121,17 @@ struct PlantArgs {
 // one entry per compiled (dim_x, dim_u, order)
 struct ShapeOps {
   int nx, nu, order, np, d;
-  int has_tile;                                                     // the tile form of the backward sweep is built for this shape (path 3)
-  int has_sg;                                                       // the shared-generator form of the clipped traceless kernel (path 4)
+  int has_tile;                                                     // the tile form of the backward sweep is built for this shape (PATH_TILE)
+  int has_sg;                                                       // the shared-generator form of the clipped traceless kernel (PATH_SG)
   int plant_only;                                                   // only plant_kernel is built (m4q_shapes.inc): serves m4q_plant_step_batch
-  size_t (*mpc_lds_bytes)(int real_path, int exact_qp);
-  int (*launch_mpc)(const MpcArgs&, int plant_kind, int real_path, int grid, hipStream_t);
+  int (*mpc_lds_bytes)(int plant_kind, Path path, int exact_qp);   // dynamic LDS of the fused kernel's launch
+  int (*launch_mpc)(const MpcArgs&, int plant_kind, Path path, int grid, hipStream_t);
   int (*launch_linearize)(const LinArgs&, hipStream_t);
   int (*launch_qp)(const QpArgs&, hipStream_t);
   int (*launch_plant)(const PlantArgs&, hipStream_t);
-  int (*launch_discretize)(const DiscArgs&, int real_path, hipStream_t);
+  int (*launch_discretize)(const DiscArgs&, Coords coords, hipStream_t);
   int (*power_list)(int32_t* out);
-  int (*occupancy)(int plant_kind, int real_path, int exact_qp);   // resident workgroups per CU of the fused kernel
+  int (*occupancy)(int plant_kind, Path path, int exact_qp);       // resident workgroups per CU of the fused kernel
 };
 
 }  // namespace m4q

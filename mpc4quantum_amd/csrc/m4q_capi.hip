@@ -216,7 +216,7 @@ struct LiftStat {
   bool real_enough() const { return max_im <= 1e-13 * std::max(1.0, max_abs); }
 };
 
-// ---- traceless coordinates (path 2; csrc/m4q_mpc.h): the diagonal slots (a, a) of the Hermitian basis rotated by the orthogonal
+// ---- traceless coordinates (COORDS_TRACELESS; csrc/m4q_mpc.h): the diagonal slots (a, a) of the Hermitian basis rotated by the orthogonal
 // O[a][0] = 1/sqrt(d), O[a][l] = 1/sqrt(l(l+1)) (a < l), -l/sqrt(l(l+1)) (a == l), 0 (a > l); slot (0, 0) becomes the trace
 // coordinate and is dropped when the model leaves it alone.  Works on the REAL arrays the Hermitian lift produced.
 struct Traceless {
@@ -272,6 +272,83 @@ struct DecoupleStat {
   bool ok() const { return worst <= 1e-12 * std::max(1.0, scale); }
 };
 
+// An input on the real coordinate systems, on the host.  [COORDS_HERM]: the real part of its lift to the Hermitian basis, ok when
+// the imaginary part dropped was negligible (LiftStat).  [COORDS_TRACELESS], when asked for and the Hermitian lift is ok: the same
+// on the traceless coordinates, ok when the trace coordinate decouples (DecoupleStat); tau: the range of that coordinate (vectors).
+struct Lift {
+  std::vector<double> v[m4q::COORDS_TRACELESS + 1];
+  bool ok[m4q::COORDS_TRACELESS + 1] = {};
+  double tau[2] = {0, 0};
+};
+
+// count rows of nblk n x n complex blocks side by side (row-major: block p of a row occupies columns [p*n, (p+1)*n)).
+// block0_identity: block 0 must carry the trace coordinate through unchanged (models [A | N_1 ..]); every other block must not
+// touch it.
+Lift lift_blocks(int d, const std::complex<double>* src, size_t count, int nblk, bool block0_identity, bool traceless) {
+  const HermBasis hb(d);
+  const int n = hb.n, ns = n - 1;
+  const long ld = (long)n * nblk, lds = (long)ns * nblk;
+  Lift L;
+  std::vector<double>& out = L.v[m4q::COORDS_HERM];
+  out.resize(count * n * ld);
+  LiftStat st;
+  std::vector<std::complex<double>> tmp((size_t)n * n);
+  for (size_t it = 0; it < count; ++it)
+    for (int p = 0; p < nblk; ++p) {
+      hb.lift_mat(src + it * n * ld + (long)p * n, ld, tmp.data(), n);
+      for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+          st.see(tmp[(size_t)i * n + j]);
+          out[it * n * ld + i * ld + (long)p * n + j] = tmp[(size_t)i * n + j].real();
+        }
+    }
+  L.ok[m4q::COORDS_HERM] = st.real_enough();
+  if (!traceless || !L.ok[m4q::COORDS_HERM]) return L;
+  const Traceless tl(d);
+  std::vector<double>& tout = L.v[m4q::COORDS_TRACELESS];
+  tout.resize(count * ns * lds);
+  std::vector<double> rot((size_t)n * n);
+  DecoupleStat dc;
+  for (size_t it = 0; it < count; ++it)
+    for (int p = 0; p < nblk; ++p) {
+      tl.mat(out.data() + it * n * ld + (long)p * n, ld, rot.data());
+      dc.see_block(rot.data(), n, block0_identity && p == 0);
+      for (int i = 0; i < ns; ++i)
+        for (int j = 0; j < ns; ++j) tout[it * ns * lds + i * lds + (long)p * ns + j] = rot[(size_t)(1 + i) * n + 1 + j];
+    }
+  L.ok[m4q::COORDS_TRACELESS] = dc.ok();
+  return L;
+}
+
+// count complex n-vectors
+Lift lift_vectors(int d, const std::complex<double>* src, size_t count, bool traceless) {
+  const HermBasis hb(d);
+  const int n = hb.n, ns = n - 1;
+  Lift L;
+  std::vector<double>& out = L.v[m4q::COORDS_HERM];
+  out.resize(count * n);
+  LiftStat st;
+  std::vector<std::complex<double>> tmp(n);
+  for (size_t it = 0; it < count; ++it) {
+    hb.lift_vec(src + it * n, tmp.data());
+    for (int i = 0; i < n; ++i) { st.see(tmp[i]); out[it * n + i] = tmp[i].real(); }
+  }
+  L.ok[m4q::COORDS_HERM] = st.real_enough();
+  if (!traceless || !L.ok[m4q::COORDS_HERM]) return L;
+  const Traceless tl(d);
+  std::vector<double>& tout = L.v[m4q::COORDS_TRACELESS];
+  tout.resize(count * ns);
+  std::vector<double> rot(n);
+  for (size_t it = 0; it < count; ++it) {
+    tl.vec(out.data() + it * n, rot.data());
+    for (int i = 0; i < ns; ++i) tout[it * ns + i] = rot[1 + i];
+    L.tau[0] = it ? std::min(L.tau[0], rot[0]) : rot[0];
+    L.tau[1] = it ? std::max(L.tau[1], rot[0]) : rot[0];
+  }
+  L.ok[m4q::COORDS_TRACELESS] = true;
+  return L;
+}
+
 }  // namespace
 
 struct m4q_session {
@@ -282,15 +359,15 @@ struct m4q_session {
   const m4q::ShapeOps* mpc_ops = nullptr;      // launch_mpc / occupancy / mpc_lds_bytes: `shape`, or libm4q_hip_gen.so's for the generator plant
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int grid = 1;                 // resident workgroups of the launch (paths 0-3); the per-row workspace is sized for max(grid, grid_sg)
-  int grid_sg = 0;              // ... of the shared-generator kernel (path 4: two wavefronts per SIMD at d = 4), 0 when not available
+  bool allowed[m4q::PATH_SG + 1] = {};   // [m4q::Path]: the paths the shape, the options and the problem admit (m4q_session_create)
+  int grid = 1;                 // resident workgroups of the launch (PATH_COMPLEX .. PATH_TILE); the per-row workspace is sized for max(grid, grid_sg)
+  int grid_sg = 0;              // ... of the shared-generator kernel (PATH_SG: two wavefronts per SIMD at d = 4)
   // shared-generator form (m4q_session_build_models with ONE generator set, order 1, traceless blocks): dt L_k on the traceless
-  // coordinates [1 + m][n-1][n-1] and the members' scales [B][1 + m]; the kernel of path 4 reads these instead of the models
+  // coordinates [1 + m][n-1][n-1] and the members' scales [B][1 + m]; the kernel of PATH_SG reads these instead of the models
   DevBuf sg_gens, sg_scales;
-  bool sg_ok = false, no_sg = false;
+  bool sg_ok = false;
   DevBuf f[M4Q_F_COUNT];
   DevBuf Cq, Cqf, Cr, Wls, wsXg, wsUg, wsG, queue, head_done;
-  bool no_tile = false;
   size_t fbytes[M4Q_F_COUNT]{};
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;   // (start, stop) of launches not yet read by kernel_ms
   double folded_ms = 0.0;                                    // launches already completed and folded out of `pending`
@@ -299,47 +376,41 @@ struct m4q_session {
   int launches = 0;
   bool costs_dirty = true;
   bool ls_diag = false;
-  // real path: inputs lifted to the Hermitian operator basis at upload time (doubles), and whether each was real there
-  DevBuf r_models, r_x0, r_xtarg, r_Q, r_Qf, r_R;
-  bool herm_ok[M4Q_F_COUNT] = {};
-  // traceless path: the same inputs on the n - 1 traceless coordinates, whether the trace coordinate decouples from each, and
-  // the range of trace coordinates seen in x0 / X_targ (state and target must share ONE trace for the cost to restrict)
-  DevBuf t_models, t_x0, t_xtarg, t_Q, t_Qf;
-  bool tl_ok[M4Q_F_COUNT] = {};
+  // the inputs the recursion reads, on the real coordinate systems ([COORDS_HERM], [COORDS_TRACELESS]; the complex copy is f[]):
+  // lifted at upload time, and whether each qualified there (Lift).  tau_*: the range of trace coordinates seen in x0 / X_targ
+  // (state and target must share ONE trace for the cost to restrict to the traceless coordinates)
+  struct Copy { DevBuf buf; bool ok = false; };
+  Copy copies[m4q::COORDS_TRACELESS + 1][M4Q_F_COUNT];
   double tau_x0[2] = {0, 0}, tau_targ[2] = {0, 0};
-  bool no_traceless = false;
-  bool force_complex = false;
   bool launched = false;        // a closed-loop launch has been enqueued since the watchdog flag was last read
   bool targ_const = false;      // every column of X_targ equals the first (per member, if per-member): xbar does not depend on t
   // exit condition (m4q_session_set_exit): M4Q_EXIT_* bits (0: none), W [n][n] c, target [B|1][n] c, thresholds [B|1]
   int exit_mode = 0;
   bool exit_target_per = false, exit_thr_per = false;
   DevBuf exit_W, exit_target, exit_thr;
-  bool use_real(bool diag) const {
-    return !force_complex && diag && herm_ok[M4Q_F_MODELS] && herm_ok[M4Q_F_X0] && herm_ok[M4Q_F_X_TARG] &&
-           herm_ok[M4Q_F_Q] && herm_ok[M4Q_F_QF] && herm_ok[M4Q_F_R];
-  }
-  bool use_real() const { return use_real(ls_diag); }
-  bool use_traceless(bool diag) const {
-    if (!use_real(diag) || no_traceless || !tl_ok[M4Q_F_MODELS] || !tl_ok[M4Q_F_X0] || !tl_ok[M4Q_F_X_TARG] || !tl_ok[M4Q_F_Q] ||
-        !tl_ok[M4Q_F_QF])
-      return false;
-    const double lo = std::min(tau_x0[0], tau_targ[0]), hi = std::max(tau_x0[1], tau_targ[1]);
-    return hi - lo <= 1e-12 * std::max(1.0, std::fabs(hi));
-  }
-  // 0 complex, 1 real (Hermitian basis), 2 real traceless.  diag: the line-search blocks of the costs are diagonal (known after
-  // the first run; m4q_session_path answers as if they were before that)
-  //                         3 traceless with the backward sweep of the clipped solve / the pinned sweep of the exact solve on
-  //                           matrix-core tiles (constant targets only)
-  //                         4 traceless clipped solve on shared generators (models built by m4q_session_build_models from one
-  //                           generator set; where that kernel is built: d = 4)
-  int path(bool diag) const {
-    if (!use_traceless(diag)) return use_real(diag) ? 1 : 0;
-    if (sg_ok && !no_sg && grid_sg > 0 && !(prob.qp_flags & M4Q_QP_EXACT_BOX) && !(prob.qp_flags & M4Q_QP_REF_LQR)) return 4;
-    return (!no_tile && targ_const) ? 3 : 2;
-  }
-  int path() const { return path(ls_diag); }
   std::vector<double> hQ, hQf, hR;
+
+  // R weighs the controls, which are real on every path: its one real copy ([COORDS_HERM]) serves both real coordinate systems
+  const Copy& copy(int field, m4q::Coords c) const { return copies[field == M4Q_F_R ? m4q::COORDS_HERM : c][field]; }
+  // the device array of input `field` on coordinates c
+  const void* input(int field, m4q::Coords c) const { return c == m4q::COORDS_COMPLEX ? f[field].p : copy(field, c).buf.p; }
+  bool qualified(m4q::Coords c) const {
+    for (int field : {M4Q_F_MODELS, M4Q_F_X0, M4Q_F_X_TARG, M4Q_F_Q, M4Q_F_QF, M4Q_F_R})
+      if (!copy(field, c).ok) return false;
+    return true;
+  }
+  // the first allowed path the uploaded data support.  diag: the line-search blocks of the costs are diagonal (known after the first
+  // run; m4q_session_path answers as if they were before that)
+  m4q::Path path(bool diag) const {
+    const double lo = std::min(tau_x0[0], tau_targ[0]), hi = std::max(tau_x0[1], tau_targ[1]);
+    const bool real = diag && qualified(m4q::COORDS_HERM);
+    const bool traceless = real && qualified(m4q::COORDS_TRACELESS) && hi - lo <= 1e-12 * std::max(1.0, std::fabs(hi));
+    const bool supported[m4q::PATH_SG + 1] = {true, real, traceless, traceless && targ_const, traceless && sg_ok};
+    for (m4q::Path p : {m4q::PATH_SG, m4q::PATH_TILE, m4q::PATH_TRACELESS, m4q::PATH_REAL})
+      if (allowed[p] && supported[p]) return p;
+    return m4q::PATH_COMPLEX;
+  }
+  m4q::Path path() const { return path(ls_diag); }
 };
 
 extern "C" {
@@ -413,13 +484,6 @@ int m4q_session_create(const m4q_problem* p, int32_t B, int32_t device, m4q_sess
       return fail(M4Q_E_UNSUPPORTED, "%s", why.c_str());
     }
   }
-  // (a process plant runs on the complex path alone: V (x) V^* does not keep M Hermitian as a d^2 x d^2 matrix, so the Hermitian lift
-  // of data that happens to pass it would still be wrong after the first plant step)
-  s->force_complex = (p->reserved & 1) != 0 || std::getenv("M4Q_FORCE_COMPLEX") != nullptr || sh->d * sh->d != p->dim_x ||
-                     p->plant_kind == M4Q_PLANT_PROCESS;
-  // (M4Q_QP_REF_LQR builds its cost terms on xbar itself, lqr.py:54-58: the trace coordinate of the target does not drop out)
-  s->no_traceless = (p->reserved & M4Q_OPT_NO_TRACELESS) != 0 || std::getenv("M4Q_NO_TRACELESS") != nullptr ||
-                    (p->qp_flags & M4Q_QP_REF_LQR) != 0;
   if (sh->d * sh->d != p->dim_x && p->plant_kind != M4Q_PLANT_NONE) {
     delete s;
     return fail(M4Q_E_UNSUPPORTED, "dim_x=%d is not a vectorised density matrix: no device plant (use M4Q_PLANT_NONE)", p->dim_x);
@@ -450,36 +514,41 @@ int m4q_session_create(const m4q_problem* p, int32_t B, int32_t device, m4q_sess
   fb[M4Q_F_U_GUESS] = (size_t)B * T * m * 8;
   int rc = 0;
   for (int i = 0; i < M4Q_F_COUNT && !rc; ++i) rc = s->f[i].alloc(fb[i]);
-  // resident grid: as many workgroups as the device holds at once (persistent, quad-strided)
+  // The paths this session may take; the uploaded data choose among them (m4q_session::path).  A process plant runs on the complex
+  // path alone: V (x) V^* does not keep M Hermitian as a d^2 x d^2 matrix, so the Hermitian lift of data that happens to pass it
+  // would still be wrong after the first plant step.  M4Q_QP_REF_LQR builds its cost terms on xbar itself (lqr.py:54-58): the trace
+  // coordinate of the target does not drop out.  The tile form of the sweeps is what a traceless session with a constant target runs
+  // wherever it is built (d = 2, 3 with an order-1 library: include/m4q.h, M4Q_OPT_NO_TILE).
+  const int exact = (p->qp_flags & M4Q_QP_EXACT_BOX) ? 1 : 0;
+  bool* allow = s->allowed;
+  allow[m4q::PATH_COMPLEX] = true;
+  allow[m4q::PATH_REAL] = !(p->reserved & M4Q_OPT_FORCE_COMPLEX) && !std::getenv("M4Q_FORCE_COMPLEX") && sh->d * sh->d == p->dim_x &&
+                          p->plant_kind != M4Q_PLANT_PROCESS;
+  allow[m4q::PATH_TRACELESS] = allow[m4q::PATH_REAL] && !(p->reserved & M4Q_OPT_NO_TRACELESS) && !std::getenv("M4Q_NO_TRACELESS") &&
+                               !(p->qp_flags & M4Q_QP_REF_LQR);
+  allow[m4q::PATH_TILE] = allow[m4q::PATH_TRACELESS] && sh->has_tile && !(p->reserved & M4Q_OPT_NO_TILE) && !std::getenv("M4Q_NO_TILE");
+  allow[m4q::PATH_SG] = allow[m4q::PATH_TRACELESS] && sh->has_sg && !(p->reserved & M4Q_OPT_NO_SG) && !std::getenv("M4Q_NO_SG") &&
+                        !exact && p->order == 1;
+  // resident grid: as many workgroups as the device holds at once (persistent, quad-strided), sized for whichever allowed path keeps
+  // more of them resident; the shared-generator kernel keeps more than the per-member-model kernels of its shape: its own grid
   hipDeviceProp_t prop;
   HIP_TRY_OWNED(s, hipGetDeviceProperties(&prop, s->device));
-  // the grid (and the per-row workspace) is sized for whichever path keeps more workgroups resident
-  const int exact = (p->qp_flags & M4Q_QP_EXACT_BOX) ? 1 : 0;
+  const char* cap = std::getenv("M4Q_WGS_PER_CU");            // tuning experiments: fewer resident workgroups per CU
+  const int cap_v = cap ? std::atoi(cap) : 0;
+  const long nquads = (B + 3) / 4;
+  auto resident = [&](int per_cu) {
+    if (cap_v >= 1 && cap_v < per_cu) per_cu = cap_v;
+    return (int)std::min(nquads, (long)per_cu * prop.multiProcessorCount);
+  };
   const m4q::ShapeOps* mo = s->mpc_ops;
-  int per_cu = std::max(mo->occupancy(p->plant_kind, 0, exact), s->force_complex ? 0 : mo->occupancy(p->plant_kind, 1, exact));
-  // the tile form of the backward sweep is what a traceless session with a constant target runs wherever it is built (d = 2, 3 with an
-  // order-1 library: include/m4q.h, M4Q_OPT_NO_TILE)
-  s->no_tile = !sh->has_tile || (p->reserved & M4Q_OPT_NO_TILE) != 0 || std::getenv("M4Q_NO_TILE") != nullptr;
-  if (!s->force_complex && !s->no_traceless) per_cu = std::max(per_cu, mo->occupancy(p->plant_kind, 2, exact));
-  if (!s->force_complex && !s->no_traceless && !s->no_tile && !exact) per_cu = std::max(per_cu, mo->occupancy(p->plant_kind, 3, 0));
-  if (per_cu < 1) per_cu = 1;
-  if (const char* cap = std::getenv("M4Q_WGS_PER_CU")) {       // tuning experiments: fewer resident workgroups per CU
-    const int v = std::atoi(cap);
-    if (v >= 1 && v < per_cu) per_cu = v;
-  }
-  const int nquads = (B + 3) / 4;
-  long resident = (long)per_cu * prop.multiProcessorCount;
-  s->grid = (int)(nquads < resident ? nquads : resident);
-  // the shared-generator kernel (path 4) keeps more workgroups resident than the per-member-model kernels of its shape: its own grid
-  s->no_sg = !sh->has_sg || (p->reserved & M4Q_OPT_NO_SG) != 0 || std::getenv("M4Q_NO_SG") != nullptr || exact ||
-             s->force_complex || s->no_traceless || p->order != 1;
-  if (!s->no_sg) {
-    int pc = mo->occupancy(p->plant_kind, 4, 0);
-    if (const char* cap = std::getenv("M4Q_WGS_PER_CU")) { const int v = std::atoi(cap); if (v >= 1 && v < pc) pc = v; }
-    if (pc >= 1) {
-      const long res_sg = (long)pc * prop.multiProcessorCount;
-      s->grid_sg = (int)(nquads < res_sg ? nquads : res_sg);
-    }
+  int per_cu = 1;
+  for (m4q::Path q : {m4q::PATH_COMPLEX, m4q::PATH_REAL, m4q::PATH_TRACELESS, m4q::PATH_TILE})
+    if (allow[q]) per_cu = std::max(per_cu, mo->occupancy(p->plant_kind, q, exact));
+  s->grid = resident(per_cu);
+  if (allow[m4q::PATH_SG]) {
+    const int pc = mo->occupancy(p->plant_kind, m4q::PATH_SG, exact);
+    if (pc >= 1) s->grid_sg = resident(pc);
+    else allow[m4q::PATH_SG] = false;
   }
   const size_t rows = (size_t)std::max(s->grid, s->grid_sg) * 4;
   // [Xg rows][Xo rows] and [Ug rows][Uo rows]; the exact QP adds [Xalt rows] and [Ualt rows][working-set rows]
@@ -527,81 +596,6 @@ static int check_watchdog(m4q_session* s) {
   return 0;
 }
 
-// lift one uploaded input to the Hermitian basis: keeps the real part on the device (doubles), remembers whether the
-// imaginary part was negligible.  vec_len = n for vectors; matrices are n x n blocks laid side by side (nblk per row set).
-static int lift_upload(m4q_session* s, int32_t field, const std::complex<double>* src, size_t count_items, bool matrix, int nblk,
-                       DevBuf& dst) {
-  const HermBasis hb(s->shape->d);
-  const int n = hb.n;
-  LiftStat st;
-  std::vector<double> out;
-  if (!matrix) {
-    out.resize(count_items * n);
-    std::vector<std::complex<double>> tmp(n);
-    for (size_t it = 0; it < count_items; ++it) {
-      hb.lift_vec(src + it * n, tmp.data());
-      for (int i = 0; i < n; ++i) { st.see(tmp[i]); out[it * n + i] = tmp[i].real(); }
-    }
-  } else {
-    // count_items matrices of shape n x (n * nblk), row-major: block p occupies columns [p*n, (p+1)*n)
-    const long ld = (long)n * nblk;
-    out.resize(count_items * n * ld);
-    std::vector<std::complex<double>> tmp((size_t)n * n);
-    for (size_t it = 0; it < count_items; ++it)
-      for (int p = 0; p < nblk; ++p) {
-        hb.lift_mat(src + it * n * ld + (long)p * n, ld, tmp.data(), n);
-        for (int i = 0; i < n; ++i)
-          for (int j = 0; j < n; ++j) {
-            st.see(tmp[(size_t)i * n + j]);
-            out[it * n * ld + i * ld + (long)p * n + j] = tmp[(size_t)i * n + j].real();
-          }
-      }
-  }
-  s->herm_ok[field] = st.real_enough();
-  int rc = dst.alloc(out.size() * sizeof(double));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(dst.p, out.data(), out.size() * sizeof(double), hipMemcpyHostToDevice));
-  // ... and on the traceless coordinates
-  s->tl_ok[field] = false;
-  if (!s->herm_ok[field] || s->no_traceless) return 0;
-  const Traceless tl(s->shape->d);
-  const int ns = n - 1;
-  std::vector<double> tout, tmp((size_t)n * n);
-  DevBuf* tdst = field == M4Q_F_MODELS ? &s->t_models : field == M4Q_F_X0 ? &s->t_x0 : field == M4Q_F_X_TARG ? &s->t_xtarg :
-                 field == M4Q_F_Q ? &s->t_Q : &s->t_Qf;
-  if (!matrix) {
-    tout.resize(count_items * ns);
-    double lo = 0.0, hi = 0.0;
-    for (size_t it = 0; it < count_items; ++it) {
-      tl.vec(out.data() + it * n, tmp.data());
-      for (int i = 0; i < ns; ++i) tout[it * ns + i] = tmp[1 + i];
-      lo = it ? std::min(lo, tmp[0]) : tmp[0];
-      hi = it ? std::max(hi, tmp[0]) : tmp[0];
-    }
-    double* range = field == M4Q_F_X0 ? s->tau_x0 : s->tau_targ;
-    range[0] = lo; range[1] = hi;
-    s->tl_ok[field] = true;
-  } else {
-    const long ld = (long)n * nblk, lds = (long)ns * nblk;
-    tout.resize(count_items * ns * lds);
-    DecoupleStat dc;
-    for (size_t it = 0; it < count_items; ++it)
-      for (int p = 0; p < nblk; ++p) {
-        tl.mat(out.data() + it * n * ld + (long)p * n, ld, tmp.data());
-        // models: block 0 must carry the trace coordinate through unchanged, the N_p blocks must not touch it; costs: the cross
-        // terms with the (constant, shared) trace coordinate drop out of the objective's minimiser, nothing to check
-        if (field == M4Q_F_MODELS) dc.see_block(tmp.data(), n, p == 0);
-        for (int i = 0; i < ns; ++i)
-          for (int j = 0; j < ns; ++j) tout[it * ns * lds + i * lds + (long)p * ns + j] = tmp[(size_t)(1 + i) * n + 1 + j];
-      }
-    s->tl_ok[field] = field == M4Q_F_MODELS ? dc.ok() : true;
-  }
-  rc = tdst->alloc(tout.size() * sizeof(double));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(tdst->p, tout.data(), tout.size() * sizeof(double), hipMemcpyHostToDevice));
-  return 0;
-}
-
 int m4q_session_upload(m4q_session* s, int32_t field, const void* host, size_t bytes) {
   if (!s || field < 0 || field >= M4Q_F_COUNT || !host) return fail(M4Q_E_BADARG, "m4q_session_upload: bad argument");
   if (bytes != s->fbytes[field]) return fail(M4Q_E_BADARG, "field %d expects %zu bytes, got %zu", field, s->fbytes[field], bytes);
@@ -610,7 +604,6 @@ int m4q_session_upload(m4q_session* s, int32_t field, const void* host, size_t b
   HIP_TRY(hipStreamSynchronize(s->stream));
   const size_t n = s->prob.dim_x, m = s->prob.dim_u, P = s->shape->np;
   const auto* ch = static_cast<const std::complex<double>*>(host);
-  int rc = 0;
   if (field == M4Q_F_Q) { s->hQ.assign((const double*)host, (const double*)host + 2 * n * n); s->costs_dirty = true; }
   if (field == M4Q_F_QF) { s->hQf.assign((const double*)host, (const double*)host + 2 * n * n); s->costs_dirty = true; }
   if (field == M4Q_F_R) { s->hR.assign((const double*)host, (const double*)host + 2 * m * m); s->costs_dirty = true; }
@@ -622,24 +615,47 @@ int m4q_session_upload(m4q_session* s, int32_t field, const void* host, size_t b
         same = std::memcmp(ch + (it * cols + c) * n, ch + it * cols * n, 16 * n) == 0;
     s->targ_const = same;
   }
-  if (!s->force_complex) {
-    if (field == M4Q_F_MODELS) s->sg_ok = false;            // uploaded models: not (known to be) an ensemble of scaled shared generators
-    if (field == M4Q_F_MODELS) rc = lift_upload(s, field, ch, bytes / (16 * n * n * (1 + P)), true, (int)(1 + P), s->r_models);
-    if (field == M4Q_F_X0) rc = lift_upload(s, field, ch, bytes / (16 * n), false, 1, s->r_x0);
-    if (field == M4Q_F_X_TARG) rc = lift_upload(s, field, ch, bytes / (16 * n), false, 1, s->r_xtarg);
-    if (field == M4Q_F_Q) rc = lift_upload(s, field, ch, 1, true, 1, s->r_Q);
-    if (field == M4Q_F_QF) rc = lift_upload(s, field, ch, 1, true, 1, s->r_Qf);
-    if (field == M4Q_F_R) {
-      // R acts on the (real) controls: the real path needs Im R = 0
+  if (!s->allowed[m4q::PATH_REAL]) return 0;
+  // the inputs the recursion reads, on the real coordinate systems
+  const int d = s->shape->d;
+  const bool tl = s->allowed[m4q::PATH_TRACELESS];
+  Lift L;
+  switch (field) {
+    case M4Q_F_MODELS:
+      s->sg_ok = false;                         // uploaded models: not (known to be) an ensemble of scaled shared generators
+      L = lift_blocks(d, ch, bytes / (16 * n * n * (1 + P)), (int)(1 + P), true, tl);
+      break;
+    case M4Q_F_X0:
+    case M4Q_F_X_TARG:
+      L = lift_vectors(d, ch, bytes / (16 * n), tl);
+      std::copy(L.tau, L.tau + 2, field == M4Q_F_X0 ? s->tau_x0 : s->tau_targ);
+      break;
+    case M4Q_F_Q:
+    case M4Q_F_QF:
+      // the cross terms with the (constant, shared) trace coordinate drop out of the objective's minimiser: nothing to check
+      L = lift_blocks(d, ch, 1, 1, false, tl);
+      L.ok[m4q::COORDS_TRACELESS] = !L.v[m4q::COORDS_TRACELESS].empty();
+      break;
+    case M4Q_F_R: {
+      // R acts on the (real) controls: its real part, and the real paths need Im R = 0
       LiftStat st;
-      std::vector<double> rr(m * m);
-      for (size_t i = 0; i < m * m; ++i) { st.see(ch[i]); rr[i] = ch[i].real(); }
-      s->herm_ok[field] = st.real_enough();
-      rc = s->r_R.alloc(rr.size() * 8);
-      if (!rc) HIP_TRY(hipMemcpy(s->r_R.p, rr.data(), rr.size() * 8, hipMemcpyHostToDevice));
+      L.v[m4q::COORDS_HERM].resize(m * m);
+      for (size_t i = 0; i < m * m; ++i) { st.see(ch[i]); L.v[m4q::COORDS_HERM][i] = ch[i].real(); }
+      L.ok[m4q::COORDS_HERM] = st.real_enough();
+      break;
     }
+    default:
+      return 0;
   }
-  return rc;
+  for (m4q::Coords c : {m4q::COORDS_HERM, m4q::COORDS_TRACELESS}) {
+    m4q_session::Copy& dst = s->copies[c][field];
+    dst.ok = false;
+    if (L.v[c].empty()) continue;
+    if (int rc = dst.buf.alloc(L.v[c].size() * 8)) return rc;
+    HIP_TRY(hipMemcpy(dst.buf.p, L.v[c].data(), L.v[c].size() * 8, hipMemcpyHostToDevice));
+    dst.ok = L.ok[c];
+  }
+  return 0;
 }
 
 int m4q_session_path(const m4q_session* s) {
@@ -727,16 +743,16 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   const m4q_problem& p = s->prob;
   const size_t n = p.dim_x, m = p.dim_u, P = s->shape->np;
   const size_t k = plant_dim(p.plant_kind, p.dim_x);
-  const int path = s->path();
-  const bool real_path = path != 0;
-  const size_t ns = path >= 2 ? n - 1 : n;         // dimension of the recursion
+  const m4q::Path path = s->path();
+  const m4q::Coords coords = m4q::coords_of(path);
+  const size_t ns = coords == m4q::COORDS_TRACELESS ? n - 1 : n;         // dimension of the recursion
   m4q::MpcArgs a{};
   a.B = s->B; a.T = p.horizon; a.n_steps = p.n_steps; a.max_iter = p.max_iter; a.warm_start = p.warm_start;
-  a.flags = p.qp_flags | (s->targ_const ? 256 : 0) | (s->no_tile ? 512 : 0);      // QP_TARG_CONST, QP_NO_TILE (csrc/m4q_mpc.h), internal
+  a.flags = p.qp_flags | (s->targ_const ? m4q::QP_TARG_CONST : 0) | (s->allowed[m4q::PATH_TILE] ? 0 : m4q::QP_NO_TILE);
   a.step_begin = step_begin; a.step_end = step_end;
   a.measure_freq = p.measure_freq > 1 ? p.measure_freq : 1;
   a.dt = p.dt; a.sat = p.sat; a.du = p.du; a.ls_tol = p.ls_tol;
-  a.models = path >= 2 ? s->t_models.p : real_path ? s->r_models.p : s->f[M4Q_F_MODELS].p;
+  a.models = s->input(M4Q_F_MODELS, coords);
   a.gens = (const double*)s->sg_gens.p; a.scales = (const double*)s->sg_scales.p;
   a.exit_mode = s->exit_mode;
   a.exit_W = (const cplx*)s->exit_W.p;
@@ -744,13 +760,11 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   a.exit_thr = (const double*)s->exit_thr.p; a.exit_thr_stride = s->exit_thr_per ? 1 : 0;
   a.model_stride = p.model_per_instance ? (long)(ns * ns * (1 + P)) : 0;
   a.x0c = (const cplx*)s->f[M4Q_F_X0].p;
-  a.x0s = path >= 2 ? s->t_x0.p : real_path ? s->r_x0.p : s->f[M4Q_F_X0].p;
-  a.x_targ = path >= 2 ? s->t_xtarg.p : real_path ? s->r_xtarg.p : s->f[M4Q_F_X_TARG].p;
+  a.x0s = s->input(M4Q_F_X0, coords);
+  a.x_targ = s->input(M4Q_F_X_TARG, coords);
   a.xt_stride = p.target_per_instance ? (long)(p.target_cols * ns) : 0;
   a.u_targ = (const double*)s->f[M4Q_F_U_TARG].p; a.ut_stride = p.target_per_instance ? (long)(p.target_cols * m) : 0;
-  a.Q = path >= 2 ? s->t_Q.p : real_path ? s->r_Q.p : s->f[M4Q_F_Q].p;
-  a.Qf = path >= 2 ? s->t_Qf.p : real_path ? s->r_Qf.p : s->f[M4Q_F_QF].p;
-  a.R = real_path ? s->r_R.p : s->f[M4Q_F_R].p;
+  a.Q = s->input(M4Q_F_Q, coords); a.Qf = s->input(M4Q_F_QF, coords); a.R = s->input(M4Q_F_R, coords);
   a.Cq = (const double*)s->Cq.p; a.Cqf = (const double*)s->Cqf.p; a.Cr = (const double*)s->Cr.p;
   a.Wls = s->ls_diag ? (const double*)s->Wls.p : nullptr;
   a.op0 = (const cplx*)s->f[M4Q_F_OP0].p; a.op0_stride = p.plant_per_instance ? (long)(k * k) : 0;
@@ -799,7 +813,7 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   HIP_TRY(hipEventCreate(&e0));
   HIP_TRY(hipEventCreate(&e1));
   HIP_TRY(hipEventRecord(e0, s->stream));
-  rc = s->mpc_ops->launch_mpc(a, p.plant_kind, path, path == 4 ? s->grid_sg : s->grid, s->stream);
+  rc = s->mpc_ops->launch_mpc(a, p.plant_kind, path, path == m4q::PATH_SG ? s->grid_sg : s->grid, s->stream);
   if (rc) return fail(rc, "mpc kernel launch failed: %s", hipGetErrorString((hipError_t)(-rc)));
   HIP_TRY(hipEventRecord(e1, s->stream));
   s->pending.emplace_back(e0, e1);
@@ -899,8 +913,9 @@ int m4q_session_info(const m4q_session* s, int64_t* hbm_bytes, int32_t* grid, in
   for (int i = 0; i < M4Q_F_COUNT; ++i) tot += (int64_t)s->f[i].bytes;
   tot += (int64_t)(s->wsXg.bytes + s->wsUg.bytes + s->wsG.bytes);
   if (hbm_bytes) *hbm_bytes = tot;
-  if (grid) *grid = s->path() == 4 ? s->grid_sg : s->grid;
-  if (lds_bytes) *lds_bytes = (int32_t)s->mpc_ops->mpc_lds_bytes(s->path(), (s->prob.qp_flags & M4Q_QP_EXACT_BOX) != 0);
+  const m4q::Path path = s->path();
+  if (grid) *grid = path == m4q::PATH_SG ? s->grid_sg : s->grid;
+  if (lds_bytes) *lds_bytes = s->mpc_ops->mpc_lds_bytes(s->prob.plant_kind, path, (s->prob.qp_flags & M4Q_QP_EXACT_BOX) != 0);
   return 0;
 }
 
@@ -1058,7 +1073,7 @@ int m4q_discretize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order,
   if ((rc = t.up(nullptr, (size_t)B * n * n * (1 + P) * C, &d_m))) return rc;
   a.gens = d_g; a.gen_stride = gen_per_instance ? (long)((1 + m) * n * n) : 0;
   a.scales = (const double*)d_s; a.models = d_m;
-  rc = sh->launch_discretize(a, 0, nullptr);
+  rc = sh->launch_discretize(a, m4q::COORDS_COMPLEX, nullptr);
   if (rc) return fail(rc, "discretize launch failed");
   HIP_TRY(hipDeviceSynchronize());
   return down(models, d_m, (size_t)B * n * n * (1 + P) * C);
@@ -1085,68 +1100,41 @@ int m4q_session_build_models(m4q_session* s, double dt, const double* generators
   if (scales && (rc = t.up(scales, (size_t)s->B * (1 + m) * 8, &d_s))) return rc;
   a.gens = d_g; a.gen_stride = gen_per_instance ? (long)((1 + m) * n * n) : 0;
   a.scales = (const double*)d_s; a.models = s->f[M4Q_F_MODELS].p;
-  rc = s->shape->launch_discretize(a, 0, s->stream);
+  rc = s->shape->launch_discretize(a, m4q::COORDS_COMPLEX, s->stream);
   if (rc) return fail(rc, "discretize launch failed");
-  s->herm_ok[M4Q_F_MODELS] = false;
   s->sg_ok = false;
-  if (!s->force_complex) {
-    // the same expansion in the Hermitian operator basis: lift the generators (few, or one set per member)
-    const HermBasis hb(s->shape->d);
-    const auto* g = reinterpret_cast<const std::complex<double>*>(generators);
-    std::vector<std::complex<double>> tmp(n * n);
-    std::vector<double> lifted(nset * (1 + m) * n * n);
-    LiftStat st;
-    for (size_t q = 0; q < nset * (1 + m); ++q) {
-      hb.lift_mat(g + q * n * n, (long)n, tmp.data(), (long)n);
-      for (size_t e = 0; e < n * n; ++e) { st.see(tmp[e]); lifted[q * n * n + e] = tmp[e].real(); }
-    }
-    s->tl_ok[M4Q_F_MODELS] = false;
-    if (st.real_enough()) {
+  s->copies[m4q::COORDS_HERM][M4Q_F_MODELS].ok = s->copies[m4q::COORDS_TRACELESS][M4Q_F_MODELS].ok = false;
+  if (s->allowed[m4q::PATH_REAL]) {
+    // the same expansion on the real coordinate systems: lift the generators (few, or one set per member).  Generators that leave
+    // the trace coordinate alone (row 0 and column 0 of O^T G O zero: trace-preserving and unital, every -i[H, .] is) have
+    // block-diagonal products, so the expansion of their (n-1) x (n-1) blocks IS the traceless block of the model
+    const Lift L = lift_blocks(s->shape->d, reinterpret_cast<const std::complex<double>*>(generators), nset * (1 + m), 1, false,
+                               s->allowed[m4q::PATH_TRACELESS]);
+    for (m4q::Coords c : {m4q::COORDS_HERM, m4q::COORDS_TRACELESS}) {
+      if (!L.ok[c]) continue;
+      const size_t k = c == m4q::COORDS_HERM ? n : n - 1;
+      m4q_session::Copy& dst = s->copies[c][M4Q_F_MODELS];
       void* d_gr;
-      if ((rc = t.up(lifted.data(), lifted.size() * 8, &d_gr))) return rc;
-      if ((rc = s->r_models.alloc(nmodels * n * n * (1 + P) * 8))) return rc;
+      if ((rc = t.up(L.v[c].data(), L.v[c].size() * 8, &d_gr))) return rc;
+      if ((rc = dst.buf.alloc(nmodels * k * k * (1 + P) * 8))) return rc;
       m4q::DiscArgs r = a;
-      r.gens = d_gr; r.models = s->r_models.p;
-      rc = s->shape->launch_discretize(r, 1, s->stream);
+      r.gens = d_gr; r.gen_stride = gen_per_instance ? (long)((1 + m) * k * k) : 0; r.models = dst.buf.p;
+      rc = s->shape->launch_discretize(r, c, s->stream);
       if (rc) return fail(rc, "discretize launch failed");
-      s->herm_ok[M4Q_F_MODELS] = true;
-      if (!s->no_traceless) {
-        // ... and on the traceless coordinates: generators that leave the trace coordinate alone (row 0 and column 0 of O^T G O
-        // zero: trace-preserving and unital, every -i[H, .] is) have block-diagonal products, so the expansion of their
-        // (n-1) x (n-1) blocks IS the traceless block of the model
-        const Traceless tl(s->shape->d);
-        const size_t m1 = n - 1;
-        std::vector<double> blocks(nset * (1 + m) * m1 * m1), rot(n * n);
-        DecoupleStat dc;
-        for (size_t q = 0; q < nset * (1 + m); ++q) {
-          tl.mat(lifted.data() + q * n * n, (long)n, rot.data());
-          dc.see_block(rot.data(), (int)n, false);
-          for (size_t i = 0; i < m1; ++i)
-            for (size_t j2 = 0; j2 < m1; ++j2) blocks[q * m1 * m1 + i * m1 + j2] = rot[(1 + i) * n + 1 + j2];
-        }
-        if (dc.ok()) {
-          void* d_gt;
-          if ((rc = t.up(blocks.data(), blocks.size() * 8, &d_gt))) return rc;
-          if ((rc = s->t_models.alloc(nmodels * m1 * m1 * (1 + P) * 8))) return rc;
-          m4q::DiscArgs q2 = a;
-          q2.gens = d_gt; q2.gen_stride = gen_per_instance ? (long)((1 + m) * m1 * m1) : 0; q2.models = s->t_models.p;
-          rc = s->shape->launch_discretize(q2, 2, s->stream);
-          if (rc) return fail(rc, "discretize launch failed");
-          s->tl_ok[M4Q_F_MODELS] = true;
-          // shared-generator form (path 4): ONE generator set, order 1 - member i's model is [I + dt s_i0 L_0 | dt s_ik L_k]; keep
-          // dt L_k on the traceless coordinates and the scales (ones when none were given)
-          if (!gen_per_instance && p.order == 1 && p.model_per_instance && !s->no_sg) {
-            std::vector<double> g(blocks.size());
-            for (size_t e = 0; e < blocks.size(); ++e) g[e] = dt * blocks[e];
-            std::vector<double> sc((size_t)s->B * (1 + m), 1.0);
-            if (scales) std::copy(scales, scales + sc.size(), sc.begin());
-            if ((rc = s->sg_gens.alloc(g.size() * 8)) || (rc = s->sg_scales.alloc(sc.size() * 8))) return rc;
-            HIP_TRY(hipMemcpy(s->sg_gens.p, g.data(), g.size() * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(s->sg_scales.p, sc.data(), sc.size() * 8, hipMemcpyHostToDevice));
-            s->sg_ok = true;
-          }
-        }
-      }
+      dst.ok = true;
+    }
+    // shared-generator form (PATH_SG): ONE generator set, order 1 - member i's model is [I + dt s_i0 L_0 | dt s_ik L_k]; keep dt L_k
+    // on the traceless coordinates and the scales (ones when none were given)
+    if (L.ok[m4q::COORDS_TRACELESS] && s->allowed[m4q::PATH_SG] && !gen_per_instance && p.model_per_instance) {
+      const std::vector<double>& blocks = L.v[m4q::COORDS_TRACELESS];
+      std::vector<double> g(blocks.size());
+      for (size_t e = 0; e < blocks.size(); ++e) g[e] = dt * blocks[e];
+      std::vector<double> sc((size_t)s->B * (1 + m), 1.0);
+      if (scales) std::copy(scales, scales + sc.size(), sc.begin());
+      if ((rc = s->sg_gens.alloc(g.size() * 8)) || (rc = s->sg_scales.alloc(sc.size() * 8))) return rc;
+      HIP_TRY(hipMemcpy(s->sg_gens.p, g.data(), g.size() * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(s->sg_scales.p, sc.data(), sc.size() * 8, hipMemcpyHostToDevice));
+      s->sg_ok = true;
     }
   }
   HIP_TRY(hipStreamSynchronize(s->stream));

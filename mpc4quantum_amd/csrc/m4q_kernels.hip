@@ -51,7 +51,7 @@ constexpr bool HAS_TILE = SQUARE && ORDER == 1 && NX - 1 <= 8;
 // the shared-generator form of the clipped traceless kernel (FusedProv<..., SG>, m4q_mpc.h: one set of N_k = dt L_k per workgroup, per
 // member only A_i = I + s_i0 dt L_0 and its scales) is built where the per-member models are what keeps the kernel at one wavefront
 // per SIMD: d = 4 (28.8 KB of models per workgroup against 12.6).  Sessions whose models came from m4q_session_build_models with
-// shared generators run it (path 4); the host asks m4q_shape_*()->has_sg.
+// shared generators run it (PATH_SG); the host asks m4q_shape_*()->has_sg.
 constexpr bool HAS_SG = SQUARE && ORDER == 1 && NX == 16;
 
 // register budget: waves per SIMD the kernels are compiled for (512 / budget VGPRs per lane).  d = 2 was compiled for four until the
@@ -1411,16 +1411,6 @@ __global__ __launch_bounds__(64) void discretize_kernel(DiscArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host-side launchers for this shape
 // ---------------------------------------------------------------------------------------------
-static size_t mpc_lds_bytes(int path, int exact) {
-  if constexpr (HAS_SG) { if (path == 4 && !exact) return mpc_lds_layout_bytes<double, true, false, false, true>(); }
-  if constexpr (SQUARE) {
-    if constexpr (HAS_TILE) { if (path == 3 && !exact) return mpc_lds_layout_bytes<double, true, true>(); }
-    if (path >= 2) return exact ? mpc_lds_layout_bytes<double, true, false, true>() : mpc_lds_layout_bytes<double, true, false>();
-  }
-  if (path) return exact ? mpc_lds_layout_bytes<double, false, false, true>() : mpc_lds_layout_bytes<double>();
-  return mpc_lds_layout_bytes<cplx>();
-}
-
 template <class K>
 static int prep_lds(K kern, size_t bytes) {
   if (bytes > 64 * 1024) {
@@ -1455,6 +1445,11 @@ struct OccupancyOp {
     return e != hipSuccess ? -(int)e : nb;
   }
 };
+struct LdsOp {
+  int unsupported() const { return 0; }
+  template <class S, int PLANT, bool EXACT, bool TL, bool TILE, bool SG = false>
+  int run() const { return (int)mpc_lds_layout_bytes<S, TL, TILE, EXACT, SG>(); }
+};
 
 template <class S, bool EXACT, bool TL, bool TILE, class Op, bool SG = false>
 static int pick_plant(const Op& op, int plant_kind) {
@@ -1481,40 +1476,44 @@ static int pick_plant(const Op& op, int plant_kind) {
   }
 }
 
-// path: 0 complex, 1 real (Hermitian basis, NX coordinates), 2 real traceless (NX - 1 coordinates), 3 traceless with the backward
-// sweep on matrix-core tiles (clipped solve: its own kernel; exact solve: the pinned sweep inside the one exact kernel, chosen by
-// QP_TARG_CONST and QP_NO_TILE in the flags)
+// PATH_TILE: the clipped solve has its own kernel; the exact solve runs its pinned sweep on tiles inside the one exact traceless
+// kernel, chosen by QP_TARG_CONST and QP_NO_TILE in the flags
 template <class Op>
-static int pick_kernel(const Op& op, int plant_kind, int path, int exact, int unsupported) {
+static int pick_kernel(const Op& op, int plant_kind, Path path, int exact, int unsupported) {
   if constexpr (!SQUARE) {
-    if (path || plant_kind != PLANT_NONE) return unsupported;
+    if (path != PATH_COMPLEX || plant_kind != PLANT_NONE) return unsupported;
   }
   if constexpr (HAS_SG) {
-    // path 4: the clipped traceless kernel on shared generators (sessions built by m4q_session_build_models; the host falls back to
-    // path 2 - per-member models - for the exact mode)
-    if (path == 4 && !exact) return pick_plant<double, false, true, false, Op, true>(op, plant_kind);
+    // the clipped traceless kernel on shared generators (sessions built by m4q_session_build_models; the host falls back to
+    // PATH_TRACELESS - per-member models - for the exact mode)
+    if (path == PATH_SG && !exact) return pick_plant<double, false, true, false, Op, true>(op, plant_kind);
   }
-  if (path == 4) path = 2;
+  if (path == PATH_SG) path = PATH_TRACELESS;
   if constexpr (SQUARE) {
-    if constexpr (HAS_TILE) { if (path == 3 && !exact) return pick_plant<double, false, true, true>(op, plant_kind); }
-    if (path >= 2) return exact ? pick_plant<double, true, true, false>(op, plant_kind) : pick_plant<double, false, true, false>(op, plant_kind);
-    if (path == 1) return exact ? pick_plant<double, true, false, false>(op, plant_kind) : pick_plant<double, false, false, false>(op, plant_kind);
+    if constexpr (HAS_TILE) { if (path == PATH_TILE && !exact) return pick_plant<double, false, true, true>(op, plant_kind); }
+    if (coords_of(path) == COORDS_TRACELESS) return exact ? pick_plant<double, true, true, false>(op, plant_kind) : pick_plant<double, false, true, false>(op, plant_kind);
+    if (path == PATH_REAL) return exact ? pick_plant<double, true, false, false>(op, plant_kind) : pick_plant<double, false, false, false>(op, plant_kind);
   }
   return exact ? pick_plant<cplx, true, false, false>(op, plant_kind) : pick_plant<cplx, false, false, false>(op, plant_kind);
 }
 
 #ifndef M4Q_PLANT_ONLY
-static int launch_mpc(const MpcArgs& a, int plant_kind, int path, int grid, hipStream_t s) {
+static int launch_mpc(const MpcArgs& a, int plant_kind, Path path, int grid, hipStream_t s) {
   return pick_kernel(LaunchOp{a, grid, s}, plant_kind, path, (a.flags & QP_EXACT_BOX) != 0, -(int)hipErrorInvalidValue);
 }
 
-static int occupancy(int plant_kind, int path, int exact) {
+static int occupancy(int plant_kind, Path path, int exact) {
   return pick_kernel(OccupancyOp{}, plant_kind, path, exact, 0);
 }
 
+static int mpc_lds_bytes(int plant_kind, Path path, int exact) {
+  return pick_kernel(LdsOp{}, plant_kind, path, exact, 0);
+}
+
 #else
-static int launch_mpc(const MpcArgs&, int, int, int, hipStream_t) { return -(int)hipErrorInvalidValue; }
-static int occupancy(int, int, int) { return 0; }
+static int launch_mpc(const MpcArgs&, int, Path, int, hipStream_t) { return -(int)hipErrorInvalidValue; }
+static int occupancy(int, Path, int) { return 0; }
+static int mpc_lds_bytes(int, Path, int) { return 0; }
 #endif
 
 static int grid_for(int B) {
@@ -1563,24 +1562,24 @@ static int launch_plant(const PlantArgs&, hipStream_t) { return -(int)hipErrorIn
 #endif
 
 #if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
-// path: 0 complex generators, 1 real n x n (lifted to the Hermitian basis), 2 real (n-1) x (n-1) (their traceless blocks)
+// coords: complex generators; real n x n (lifted to the Hermitian basis); real (n-1) x (n-1) (their traceless blocks)
 // (orders 3 and 4 have closed-loop kernels but no device discretisation: their models come from the host, discretize_homogeneous)
-static int launch_discretize(const DiscArgs& a, int path, hipStream_t s) {
-  if (!SQUARE && path) return -(int)hipErrorInvalidValue;
+static int launch_discretize(const DiscArgs& a, Coords coords, hipStream_t s) {
+  if (!SQUARE && coords != COORDS_COMPLEX) return -(int)hipErrorInvalidValue;
   const size_t elems = (size_t)ROWS * (1 + NU) * NX * NX;
   if constexpr (SQUARE) {
-    if (path == 2) {
+    if (coords == COORDS_TRACELESS) {
       hipLaunchKernelGGL((discretize_kernel<double, NX - 1>), dim3(grid_for(a.B)), dim3(64), elems * sizeof(double), s, a);
       return -(int)hipGetLastError();
     }
   }
-  if (path == 1) hipLaunchKernelGGL((discretize_kernel<double, NX>), dim3(grid_for(a.B)), dim3(64), elems * sizeof(double), s, a);
+  if (coords == COORDS_HERM) hipLaunchKernelGGL((discretize_kernel<double, NX>), dim3(grid_for(a.B)), dim3(64), elems * sizeof(double), s, a);
   else hipLaunchKernelGGL((discretize_kernel<cplx, NX>), dim3(grid_for(a.B)), dim3(64), elems * sizeof(cplx), s, a);
   return -(int)hipGetLastError();
 }
 
 #else
-static int launch_discretize(const DiscArgs&, int, hipStream_t) { return -(int)hipErrorInvalidValue; }
+static int launch_discretize(const DiscArgs&, Coords, hipStream_t) { return -(int)hipErrorInvalidValue; }
 #endif
 
 static int power_list(int32_t* out) {

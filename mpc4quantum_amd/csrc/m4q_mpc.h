@@ -6,6 +6,7 @@
 //   line search                 mpc4quantum/mpc.py:101-125
 //   plant step                  mpc4quantum/experiment.py:190-212 (ODE solved exactly: Pade-13 expm)
 #pragma once
+#include "m4q_args.h"
 #include "m4q_device.h"
 
 // Settled by A/B runs and no longer switches (the losing branches are gone from the source; their numbers are in
@@ -27,15 +28,6 @@
 //     config 4 75.5 -> 73.0 ms, config 3 together with tc_xb_once below 36.05 -> 35.6.
 
 namespace m4q {
-
-// QP semantics flags (mirrored in include/m4q.h)
-enum : int {
-  QP_REF_LQR = 1,   // reproduce lqr.py as written (no Delta, xbar_{t+1}==xbar_t, cost built on xbar, absolute cost)
-  QP_DU_BAND = 2,   // clip the first control to u_prev +- du as well (optimize.py:29-30)
-  QP_EXACT_BOX = 4, // solve the box-constrained QP to optimality (projected Newton) instead of clipping the Riccati rollout
-  QP_TARG_CONST = 256,   // internal (set by the host when every column of X_targ is the same): xbar_t does not depend on t
-  QP_NO_TILE = 512,      // internal (M4Q_OPT_NO_TILE in the exact mode, whose kernel holds both forms of the pinned sweep)
-};
 
 // Round 4: vector-memory instructions of the two sweeps (profiles/r04_ab_experiments.txt; every line an A/B on one box).
 // Constant-target backward sweep: xbar loaded once per sweep, not per index.  n = 15 (one wavefront per SIMD): the sweep WITHOUT

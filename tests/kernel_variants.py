@@ -18,7 +18,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mpc4quantum_amd", "csrc")
 
-# session.path_detail() names of the arithmetic paths (m4q_capi.hip, m4q_session::path: 0 .. 4)
+# session.path_detail() names of the arithmetic paths (m4q_args.h, enum Path: PATH_COMPLEX .. PATH_SG = 0 .. 4)
 COMPLEX, REAL, TRACELESS, TILE, SG = "complex", "real", "traceless", "traceless-tile", "traceless-sg"
 # plant kinds (include/m4q.h, _lib.PLANT_*)
 NONE, HAMILTONIAN, GENERATOR, PROCESS = "none", "hamiltonian", "generator", "process"

@@ -21,7 +21,7 @@ def _src(name):
 
 
 # ---------------------------------------------------------------- the mirrors against the sources
-def test_rule_lines_read_as_mirrored():
+def test_rule_lines_read_as_mirrored_by_path_name():
     k = _src("m4q_kernels.hip")
     for line in ("constexpr int DD = (NX == 4) ? 2 : (NX == 9) ? 3 : (NX == 16) ? 4 : 1;",
                  "constexpr bool SQUARE = DD * DD == NX;",
@@ -30,15 +30,19 @@ def test_rule_lines_read_as_mirrored():
                  "constexpr bool HAS_TILE = SQUARE && ORDER == 1 && NX - 1 <= 8;",
                  "constexpr bool HAS_SG = SQUARE && ORDER == 1 && NX == 16;"):
         assert k.count(line) == 1, line
-    # pick_kernel: !SQUARE runs PLANT_NONE on path 0 alone; path 4 only unexact where HAS_SG; path 3 only unexact where HAS_TILE
+    # pick_kernel: !SQUARE runs PLANT_NONE on PATH_COMPLEX alone; PATH_SG only unexact where HAS_SG; PATH_TILE only unexact where
+    # HAS_TILE; everything else on the traceless coordinates (coords_of: PATH_TRACELESS, PATH_TILE, PATH_SG) runs the traceless kernel
     body = k[k.index("static int pick_kernel("):k.index("#ifndef M4Q_PLANT_ONLY\nstatic int launch_mpc")]
-    assert "if (path || plant_kind != PLANT_NONE) return unsupported;" in body
-    assert "if (path == 4 && !exact) return pick_plant<double, false, true, false, Op, true>(op, plant_kind);" in body
-    assert "if (path == 4) path = 2;" in body
-    assert "if constexpr (HAS_TILE) { if (path == 3 && !exact) return pick_plant<double, false, true, true>(op, plant_kind); }" in body
-    assert ("if (path >= 2) return exact ? pick_plant<double, true, true, false>(op, plant_kind) : "
+    assert "if (path != PATH_COMPLEX || plant_kind != PLANT_NONE) return unsupported;" in body
+    assert "if (path == PATH_SG && !exact) return pick_plant<double, false, true, false, Op, true>(op, plant_kind);" in body
+    assert "if (path == PATH_SG) path = PATH_TRACELESS;" in body
+    assert ("if constexpr (HAS_TILE) { if (path == PATH_TILE && !exact) return pick_plant<double, false, true, true>(op, plant_kind); }"
+            in body)
+    assert ("if (coords_of(path) == COORDS_TRACELESS) return exact ? pick_plant<double, true, true, false>(op, plant_kind) : "
             "pick_plant<double, false, true, false>(op, plant_kind);") in body
-    assert ("if (path == 1) return exact ? pick_plant<double, true, false, false>(op, plant_kind) : "
+    assert _src("m4q_args.h").count("constexpr Coords coords_of(Path p) { return p == PATH_COMPLEX ? COORDS_COMPLEX : "
+                                    "p == PATH_REAL ? COORDS_HERM : COORDS_TRACELESS; }") == 1
+    assert ("if (path == PATH_REAL) return exact ? pick_plant<double, true, false, false>(op, plant_kind) : "
             "pick_plant<double, false, false, false>(op, plant_kind);") in body
     assert ("return exact ? pick_plant<cplx, true, false, false>(op, plant_kind) : pick_plant<cplx, false, false, false>(op, "
             "plant_kind);") in body
