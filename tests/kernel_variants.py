@@ -7,7 +7,9 @@ both files to the text these mirrors were written against, so a new shape or a c
 
 closed_loop_cells() is what tests/test_gpu_variant_matrix.py runs one teacher-forced case of each; entry_point_cells() lists the
 single-kernel entry points (linearize, quad_program, discretize, plant_step) per shape.  scenario() gives seeded, well-conditioned
-host inputs for every closed-loop shape in the configs.build dict layout."""
+host inputs for every closed-loop shape in the configs.build dict layout.  pieces() mirrors how one launch cuts a member's run into
+work items (tests/test_gpu_launch_schedule.py); _planned() / _check_planned() plan exits on a member's own stored states and check
+them (tests/test_gpu_exit_condition.py, tests/test_gpu_launch_schedule.py)."""
 import importlib.util
 import itertools
 import os
@@ -27,6 +29,9 @@ PLANT_CODE = {NONE: 0, HAMILTONIAN: 1, GENERATOR: 2, PROCESS: 3}
 # the case sizes of every closed-loop cell: one full wavefront of four rows and one more row; a horizon that is not a multiple of
 # the tile sweep's four and spans two of its blocks; three MPC steps (two of them warm: the line search, then the full step)
 BATCH, HORIZON, STEPS = 5, 7, 3
+# the run of tests/test_gpu_launch_schedule.py: past the last cut of the exact kernel (XCUTS), so that one launch makes every piece
+LONG_STEPS = 14
+XCUTS = (4, 7, 12)
 
 
 # ---------------------------------------------------------------- rule mirrors (m4q_kernels.hip, build.py)
@@ -87,6 +92,18 @@ def exact_paths(nx, order):
     if not square(nx):
         return [COMPLEX]
     return [COMPLEX, REAL, TRACELESS] + ([TILE] if has_tile(nx, order) else [])
+
+
+def pieces(step_begin, step_end, exact):
+    """The work items [begin, end) mpc_kernel makes of one member's run [step_begin, step_end): two_phase (step_begin < 2 and
+    step_end > 2) cuts a head [step_begin, 2) off the rest, and the exact kernel cuts the rest again at every XCUTS[i] below
+    step_end (n_pieces); piece i >= 1 begins at piece_cut(i): 2, XCUTS[0], XCUTS[1], ..."""
+    two_phase = step_begin < 2 and step_end > 2
+    n = 2 if two_phase else 1
+    if exact:
+        n += sum(1 for c in XCUTS if two_phase and step_end > c)
+    cut = (2,) + XCUTS
+    return [(step_begin if i == 0 else cut[i - 1], step_end if i == n - 1 else cut[i]) for i in range(n)]
 
 
 def plants(nx, path, plant_only=False):
@@ -293,3 +310,43 @@ def process_scenario(nu, order, batch=BATCH, horizon=HORIZON, n_steps=STEPS):
     p["gen_op0"] = np.stack([gen(h) for h in p["plant_op0"]])
     p["gen_ops"] = np.stack([gen(h) for h in p["plant_ops"][0]])[None]
     return _tune(p, "process")
+
+
+# ---------------------------------------------------------------- planned exits
+def _planned(xs, state, ns, steps=None):
+    """Per member: the planned exit step k_b - steps[b] if given, else b % (ns + 1) with the last member never - and its target,
+    the state stored at k_b ('prev') or k_b + 1 ('next'); a member planned at ns has a target no step of this kind ever reads."""
+    B, n = xs.shape[0], xs.shape[2]
+    if steps is None:
+        k = np.array([b % (ns + 1) for b in range(B)])
+        k[-1] = ns
+    else:
+        k = np.asarray(steps)
+    target = np.empty((B, n), dtype=complex)
+    for b in range(B):
+        target[b] = xs[b, min(k[b] + (state == "next"), ns)] if k[b] < ns else xs[b, 0] + 10.0
+    return target
+
+
+def _expected_exit(xs, target, state, ns):
+    """First step s whose stored state ('prev': xs[s], 'next': xs[s + 1]) equals the target bit for bit, else None."""
+    for s in range(ns):
+        x = xs[s] if state == "prev" else xs[s + 1]
+        if np.array_equal(x.view(np.float64), target.view(np.float64)):
+            return s
+    return None
+
+
+def _check_planned(ref, got, target, state, ns):
+    B = ref["xs"].shape[0]
+    for b in range(B):
+        s = _expected_exit(ref["xs"][b], target[b], state, ns)
+        if s is None:
+            assert got["exit_codes"][b] == 0 and got["steps_done"][b] == ns, (b, got["exit_codes"][b], got["steps_done"][b])
+            for f in ("xs", "us", "qp_solves"):
+                assert np.array_equal(got[f][b], ref[f][b]), (b, f)
+            continue
+        assert got["exit_codes"][b] == 1 and got["steps_done"][b] == s, (b, s, got["exit_codes"][b], got["steps_done"][b])
+        assert np.array_equal(got["xs"][b, :s + 2], ref["xs"][b, :s + 2]), b          # (step s ran: its entries are stored)
+        assert np.array_equal(got["us"][b, :s + 1], ref["us"][b, :s + 1]), b
+        assert np.array_equal(got["qp_solves"][b, :s + 1], ref["qp_solves"][b, :s + 1]), b

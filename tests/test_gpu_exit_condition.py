@@ -11,6 +11,7 @@ import mpc4quantum_amd as m4q
 from mpc4quantum_amd import _lib, configs
 from mpc4quantum_amd.mpc import open_session
 from tests import kernel_variants as kv
+from tests.kernel_variants import _check_planned, _planned
 from tests.test_gpu_synthesis import _case, _check_vs_reference, _dropin
 from tests.test_gpu_variant_matrix import _open, _scenario
 
@@ -85,42 +86,6 @@ PLANT_CELLS = [c for c in kv.closed_loop_cells() if c.plant != kv.NONE]
 def _results(sess):
     r = sess.results()
     return {k: r[k].copy() for k in ("xs", "us", "exit_codes", "steps_done", "qp_solves")}
-
-
-def _planned(xs, state, ns):
-    """Per member: the planned exit step k_b = b % (ns + 1) (the last member never) and its target, the state stored at k_b
-    ('prev') or k_b + 1 ('next'); a member planned at ns has a target no step of this kind ever reads."""
-    B, n = xs.shape[0], xs.shape[2]
-    k = np.array([b % (ns + 1) for b in range(B)])
-    k[-1] = ns
-    target = np.empty((B, n), dtype=complex)
-    for b in range(B):
-        target[b] = xs[b, min(k[b] + (state == "next"), ns)] if k[b] < ns else xs[b, 0] + 10.0
-    return target
-
-
-def _expected_exit(xs, target, state, ns):
-    """First step s whose stored state ('prev': xs[s], 'next': xs[s + 1]) equals the target bit for bit, else None."""
-    for s in range(ns):
-        x = xs[s] if state == "prev" else xs[s + 1]
-        if np.array_equal(x.view(np.float64), target.view(np.float64)):
-            return s
-    return None
-
-
-def _check_planned(ref, got, target, state, ns):
-    B = ref["xs"].shape[0]
-    for b in range(B):
-        s = _expected_exit(ref["xs"][b], target[b], state, ns)
-        if s is None:
-            assert got["exit_codes"][b] == 0 and got["steps_done"][b] == ns, (b, got["exit_codes"][b], got["steps_done"][b])
-            for f in ("xs", "us", "qp_solves"):
-                assert np.array_equal(got[f][b], ref[f][b]), (b, f)
-            continue
-        assert got["exit_codes"][b] == 1 and got["steps_done"][b] == s, (b, s, got["exit_codes"][b], got["steps_done"][b])
-        assert np.array_equal(got["xs"][b, :s + 2], ref["xs"][b, :s + 2]), b          # (step s ran: its entries are stored)
-        assert np.array_equal(got["us"][b, :s + 1], ref["us"][b, :s + 1]), b
-        assert np.array_equal(got["qp_solves"][b, :s + 1], ref["qp_solves"][b, :s + 1]), b
 
 
 @pytest.mark.parametrize("cell", PLANT_CELLS, ids=kv.cell_id)

@@ -57,12 +57,15 @@ def _oracle(cell, exact):
     return _ORACLE[key]
 
 
-def _open(cell, p):
+def _open(cell, p, model_per_instance=None):
+    """A session of the cell's kernel on scenario p (model_per_instance: default, whether p holds one model per member)."""
     B, n, m = p["batch"], p["dim_x"], p["dim_u"]
     per_plant = cell.plant == kv.PROCESS                 # detuned members: one d x d Hamiltonian each
     op0, ops, _ = _plant_ops(p, kv.HAMILTONIAN if per_plant else cell.plant)
+    if model_per_instance is None:
+        model_per_instance = p["models"].shape[0] > 1
     sess = m4q.EnsembleSession(B, n, m, p["order"], p["horizon"], p["n_steps"], p["dt"], p["sat"], p["du"],
-                               plant_kind=kv.PLANT_CODE[cell.plant], model_per_instance=p["models"].shape[0] > 1,
+                               plant_kind=kv.PLANT_CODE[cell.plant], model_per_instance=model_per_instance,
                                plant_per_instance=per_plant, target_cols=p["n_steps"] + p["horizon"] + 1,
                                force_complex=cell.path == kv.COMPLEX, traceless=cell.path != kv.REAL, tile=cell.path == kv.TILE,
                                shared_generators=None if cell.path == kv.SG else False, exact_qp=cell.exact)

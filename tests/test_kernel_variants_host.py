@@ -59,6 +59,45 @@ def test_rule_lines_read_as_mirrored_by_path_name():
     assert '"-DM4Q_VARIANT_GEN"' in b
 
 
+def test_piece_rule_lines_read_as_mirrored():
+    """The cut rule kernel_variants.pieces() mirrors (mpc_kernel: XCUTS, two_phase, the exact kernel's n_pieces loop, piece_cut and
+    the item's [row_begin, row_end)), by exact text."""
+    k = _src("m4q_kernels.hip")
+    for text in ("constexpr int XCUTS[] = {4, 7, 12};",
+                 "    two_phase = a->step_begin < 2 && a->step_end > 2;\n",
+                 "    n_pieces = two_phase ? 2 : 1;\n"
+                 "    if constexpr (EXACT) {\n"
+                 "#pragma unroll\n"
+                 "      for (int i = 0; i < NXC; ++i)\n"
+                 "        if (two_phase && a->step_end > XCUTS[i]) ++n_pieces;\n"
+                 "    }\n",
+                 "    int v = 2;\n"
+                 "#pragma unroll\n"
+                 "    for (int k = 0; k < NXC; ++k)\n"
+                 "      if (i == k + 2) v = XCUTS[k];\n"
+                 "    return v;\n",
+                 "          row_begin = ph == 0 ? step_begin : piece_cut(ph);\n"
+                 "          row_end = ph == n_pieces - 1 ? step_end : piece_cut(ph + 1);\n"):
+        assert k.count(text) == 1, text
+
+
+def test_pieces_mirror_the_cut_rule():
+    assert kv.XCUTS == (4, 7, 12) and kv.LONG_STEPS > kv.XCUTS[-1] + 1
+    assert kv.pieces(0, 14, True) == [(0, 2), (2, 4), (4, 7), (7, 12), (12, 14)]
+    assert kv.pieces(0, 14, False) == [(0, 2), (2, 14)]
+    assert kv.pieces(1, 5, True) == [(1, 2), (2, 4), (4, 5)]
+    assert kv.pieces(0, 4, True) == [(0, 2), (2, 4)]
+    assert kv.pieces(3, 14, True) == [(3, 14)]
+    for exact in (False, True):
+        assert kv.pieces(0, 2, exact) == [(0, 2)]
+        # every launch range is tiled by non-empty pieces
+        for b in range(kv.LONG_STEPS):
+            for e in range(b + 1, kv.LONG_STEPS + 1):
+                ps = kv.pieces(b, e, exact)
+                assert ps[0][0] == b and ps[-1][1] == e and all(lo < hi for lo, hi in ps), (b, e, ps)
+                assert all(p[1] == q[0] for p, q in zip(ps, ps[1:])), (b, e, ps)
+
+
 def test_mirrors_agree_with_the_rule_text():
     for nx in (4, 8, 9, 16):
         assert kv.square(nx) == (nx in (4, 9, 16)) and kv.quartic(nx) == (nx == 16)
