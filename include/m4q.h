@@ -245,6 +245,28 @@ M4Q_API int m4q_session_set_codes(m4q_session* s, const int32_t* codes);
 #define M4Q_EXIT_ABOVE 8
 M4Q_API int m4q_session_set_exit(m4q_session* s, int32_t mode, const double* W, const double* target, int32_t target_per_instance,
                                  const double* thr, int32_t thr_per_instance);
+/* measurement noise the closed-loop kernel draws itself (QExperiment.set_sigma, experiment.py:188-212, for whole ensembles): on every
+ * measured step,  xs[b][step + 1] += e(seed, member_base + b, step + 1)  before the state is stored, so every later linearisation,
+ * QP, plant step and exit condition sees it.  The generator is counter-based (Philox4x32-10 -> two 53-bit uniforms -> Box-Muller;
+ * mpc4quantum_amd/noise.py is its normative definition): a draw depends on the seed, the GLOBAL member index, the column of XS and
+ * the component, and on nothing else - not the launch, the split of a run into launches, the resident row or the rank.
+ *   M4Q_NOISE_IID        e = sigma z, z a unit complex normal per component (the reference's noise as written).  It does not keep
+ *                        a density matrix Hermitian: such a session runs the complex path (m4q_session_path 0).
+ *   M4Q_NOISE_HERMITIAN  e = sigma ((Z + Z^H) / 2 - (Re tr Z / d) I) with Z[a][b] = z of component a d + b: Hermitian and
+ *                        traceless, every arithmetic path stays available.  Not for M4Q_PLANT_PROCESS (no density matrix).
+ * sigma: host buffer of 1 or B (sigma_per_instance) entries, finite and >= 0, copied.  Call it before the session's first
+ * m4q_session_run; a later call may change sigma, seed and member_base but not mode (the arithmetic path depends on it).
+ * mode 0 clears the setting.  M4Q_E_BADARG for a null session, another mode, a missing, negative or non-finite sigma, a
+ * M4Q_PLANT_NONE session (its host supplies the states), M4Q_NOISE_HERMITIAN on a process plant, or a forbidden change. */
+#define M4Q_NOISE_IID 1
+#define M4Q_NOISE_HERMITIAN 2
+M4Q_API int m4q_session_set_noise(m4q_session* s, int32_t mode, const double* sigma, int32_t sigma_per_instance, uint64_t seed,
+                                  uint64_t member_base);
+/* the noise m4q_session_set_noise adds to xs[:, state_index] (state_index = step + 1 >= 1) of B members with n-dimensional states,
+ * by the device function the closed loop calls: out [B][n] c (host).  n must be a dim_x with compiled kernels; M4Q_NOISE_HERMITIAN
+ * needs n = d d. */
+M4Q_API int m4q_noise_sample_batch(int32_t B, int32_t n, int32_t mode, const double* sigma, int32_t sigma_per_instance, uint64_t seed,
+                                   uint64_t member_base, int32_t state_index, double* out);
 /* kernel time of the launches since the last call, from HIP events on the session stream */
 M4Q_API int m4q_session_kernel_ms(m4q_session* s, double* total_ms, int32_t* launches);
 /* arithmetic path the uploaded problem will run on: 0 complex, 1 real (Hermitian operator basis, d*d coordinates),

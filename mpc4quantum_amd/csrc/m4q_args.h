@@ -74,6 +74,12 @@ struct MpcArgs {
   int exit_mode;
   M4Q_P(const cplx) exit_W; M4Q_P(const cplx) exit_target; long exit_tstride;
   M4Q_P(const double) exit_thr; long exit_thr_stride;
+  // measurement noise (m4q_session_set_noise; device plants only): noise_mode is 0 (none), NOISE_IID or NOISE_HERMITIAN (m4q_noise.h).
+  // On every measured step xs[b][step + 1] += the draw of (noise_seed, noise_member_base + b, step + 1, component) scaled by the
+  // member's sigma [B|1] (noise_sigma_stride 1 or 0)
+  int noise_mode;
+  M4Q_P(const double) noise_sigma; long noise_sigma_stride;
+  unsigned long long noise_seed, noise_member_base;
 };
 enum : int { EXIT_PREV = 1, EXIT_NEXT = 2, EXIT_BELOW = 4, EXIT_ABOVE = 8 };     // (mirrored in include/m4q.h: M4Q_EXIT_*)
 
@@ -118,6 +124,15 @@ struct PlantArgs {
   M4Q_P(cplx) x_next;
 };
 
+// noise.py's sample() for B members at one state_index (m4q_noise_sample_batch): out [B][n] complex
+struct NoiseArgs {
+  int B, mode;
+  unsigned state_index;
+  unsigned long long seed, member_base;
+  M4Q_P(const double) sigma; long sigma_stride;   // [B|1]
+  M4Q_P(cplx) out;
+};
+
 // one entry per compiled (dim_x, dim_u, order)
 struct ShapeOps {
   int nx, nu, order, np, d;
@@ -132,6 +147,7 @@ struct ShapeOps {
   int (*launch_discretize)(const DiscArgs&, Coords coords, hipStream_t);
   int (*power_list)(int32_t* out);
   int (*occupancy)(int plant_kind, Path path, int exact_qp);       // resident workgroups per CU of the fused kernel
+  int (*launch_noise)(const NoiseArgs&, hipStream_t);             // (depends on dim_x alone)
 };
 
 }  // namespace m4q

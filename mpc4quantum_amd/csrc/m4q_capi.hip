@@ -388,6 +388,12 @@ struct m4q_session {
   int exit_mode = 0;
   bool exit_target_per = false, exit_thr_per = false;
   DevBuf exit_W, exit_target, exit_thr;
+  // measurement noise (m4q_session_set_noise): M4Q_NOISE_* (0: none), sigma [B|1], the generator's seed, the global index of member 0
+  int noise_mode = 0;
+  bool noise_sigma_per = false;
+  DevBuf noise_sigma;
+  uint64_t noise_seed = 0, noise_member_base = 0;
+  bool ran = false;             // m4q_session_run has been called: the noise mode is fixed from here on
   std::vector<double> hQ, hQf, hR;
 
   // R weighs the controls, which are real on every path: its one real copy ([COORDS_HERM]) serves both real coordinate systems
@@ -402,6 +408,7 @@ struct m4q_session {
   // the first allowed path the uploaded data support.  diag: the line-search blocks of the costs are diagonal (known after the first
   // run; m4q_session_path answers as if they were before that)
   m4q::Path path(bool diag) const {
+    if (noise_mode == M4Q_NOISE_IID) return m4q::PATH_COMPLEX;      // independent noise on every component: the state is not Hermitian
     const double lo = std::min(tau_x0[0], tau_targ[0]), hi = std::max(tau_x0[1], tau_targ[1]);
     const bool real = diag && qualified(m4q::COORDS_HERM);
     const bool traceless = real && qualified(m4q::COORDS_TRACELESS) && hi - lo <= 1e-12 * std::max(1.0, std::fabs(hi));
@@ -758,6 +765,9 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   a.exit_W = (const cplx*)s->exit_W.p;
   a.exit_target = (const cplx*)s->exit_target.p; a.exit_tstride = s->exit_target_per ? (long)n : 0;
   a.exit_thr = (const double*)s->exit_thr.p; a.exit_thr_stride = s->exit_thr_per ? 1 : 0;
+  a.noise_mode = s->noise_mode;
+  a.noise_sigma = (const double*)s->noise_sigma.p; a.noise_sigma_stride = s->noise_sigma_per ? 1 : 0;
+  a.noise_seed = s->noise_seed; a.noise_member_base = s->noise_member_base;
   a.model_stride = p.model_per_instance ? (long)(ns * ns * (1 + P)) : 0;
   a.x0c = (const cplx*)s->f[M4Q_F_X0].p;
   a.x0s = s->input(M4Q_F_X0, coords);
@@ -818,6 +828,7 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   HIP_TRY(hipEventRecord(e1, s->stream));
   s->pending.emplace_back(e0, e1);
   s->launched = true;
+  s->ran = true;
   return 0;
 }
 
@@ -848,6 +859,43 @@ int m4q_session_set_exit(m4q_session* s, int32_t mode, const double* W, const do
   s->exit_target_per = target_per_instance != 0;
   s->exit_thr_per = thr_per_instance != 0;
   s->exit_mode = mode;
+  return 0;
+}
+
+static int check_noise_args(const char* who, int32_t mode, const double* sigma, size_t count) {
+  if (mode != 0 && mode != M4Q_NOISE_IID && mode != M4Q_NOISE_HERMITIAN)
+    return fail(M4Q_E_BADARG, "%s: mode %d is not 0, M4Q_NOISE_IID or M4Q_NOISE_HERMITIAN", who, mode);
+  if (mode == 0) return 0;
+  if (!sigma) return fail(M4Q_E_BADARG, "%s: sigma is required", who);
+  for (size_t i = 0; i < count; ++i)
+    if (!std::isfinite(sigma[i]) || sigma[i] < 0.0) return fail(M4Q_E_BADARG, "%s: sigma[%zu] = %g is not finite and >= 0", who, i, sigma[i]);
+  return 0;
+}
+
+int m4q_session_set_noise(m4q_session* s, int32_t mode, const double* sigma, int32_t sigma_per_instance, uint64_t seed,
+                          uint64_t member_base) {
+  if (!s) return fail(M4Q_E_BADARG, "m4q_session_set_noise: null session");
+  const size_t count = sigma_per_instance ? (size_t)s->B : 1;
+  if (int rc = check_noise_args("m4q_session_set_noise", mode, sigma, count)) return rc;
+  if (mode != 0 && s->prob.plant_kind == M4Q_PLANT_NONE)
+    return fail(M4Q_E_BADARG, "m4q_session_set_noise: M4Q_PLANT_NONE sessions take their states from the host, which adds its own noise");
+  if (mode == M4Q_NOISE_HERMITIAN && s->prob.plant_kind == M4Q_PLANT_PROCESS)
+    return fail(M4Q_E_BADARG, "m4q_session_set_noise: M4Q_NOISE_HERMITIAN needs a density-matrix state; the loop state of "
+                "M4Q_PLANT_PROCESS is a process vector (use M4Q_NOISE_IID)");
+  if (s->ran && mode != s->noise_mode)
+    return fail(M4Q_E_BADARG, "m4q_session_set_noise: the mode (%d) cannot change to %d after the session's first run: the arithmetic "
+                "path depends on it (sigma, seed and member_base may)", s->noise_mode, mode);
+  // a launch still in flight may read the buffer about to be replaced
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  s->noise_mode = 0;
+  s->noise_sigma.release();
+  if (mode == 0) return 0;
+  if (int rc = s->noise_sigma.alloc(count * 8)) return rc;
+  HIP_TRY(hipMemcpy(s->noise_sigma.p, sigma, count * 8, hipMemcpyHostToDevice));
+  s->noise_sigma_per = sigma_per_instance != 0;
+  s->noise_seed = seed;
+  s->noise_member_base = member_base;
+  s->noise_mode = mode;
   return 0;
 }
 
@@ -1051,6 +1099,32 @@ int m4q_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t T, i
   if ((rc = down(U_opt, d_uo, (size_t)B * T * m * 8))) return rc;
   if ((rc = down(cost, d_c, (size_t)B * 8))) return rc;
   return down(gains, d_g, (size_t)B * T * (n + 1) * m * C);
+}
+
+int m4q_noise_sample_batch(int32_t B, int32_t n, int32_t mode, const double* sigma, int32_t sigma_per_instance, uint64_t seed,
+                           uint64_t member_base, int32_t state_index, double* out) {
+  if (B <= 0 || n <= 0 || !out || mode == 0 || state_index < 1)
+    return fail(M4Q_E_BADARG, "m4q_noise_sample_batch: bad argument (B, n >= 1, a noise mode, state_index >= 1, out)");
+  if (int rc = check_noise_args("m4q_noise_sample_batch", mode, sigma, sigma_per_instance ? (size_t)B : 1)) return rc;
+  const m4q::ShapeOps* sh = nullptr;
+  for (int nu = 1; nu <= 3 && !sh; ++nu) sh = find_shape_any_order(n, nu, true);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "m4q_noise_sample_batch: no compiled kernel with dim_x=%d", n);
+  if (mode == M4Q_NOISE_HERMITIAN && sh->d * sh->d != n)
+    return fail(M4Q_E_BADARG, "m4q_noise_sample_batch: M4Q_NOISE_HERMITIAN needs n = d d, got n = %d", n);
+  int rc = need_device();
+  if (rc) return rc;
+  Tmp t;
+  void *d_s, *d_o;
+  const size_t sb = (sigma_per_instance ? (size_t)B : 1) * 8, ob = (size_t)B * n * 16;
+  if ((rc = t.up(sigma, sb, &d_s)) || (rc = t.up(nullptr, ob, &d_o))) return rc;
+  m4q::NoiseArgs a{};
+  a.B = B; a.mode = mode; a.state_index = (unsigned)state_index; a.seed = seed; a.member_base = member_base;
+  a.sigma = (const double*)d_s; a.sigma_stride = sigma_per_instance ? 1 : 0;
+  a.out = (cplx*)d_o;
+  rc = sh->launch_noise(a, nullptr);
+  if (rc) return fail(rc, "noise kernel launch failed: %s", hipGetErrorString((hipError_t)(-rc)));
+  HIP_TRY(hipDeviceSynchronize());
+  return down(out, d_o, ob);
 }
 
 int m4q_discretize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, double dt, const double* generators,

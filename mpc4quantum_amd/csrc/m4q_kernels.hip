@@ -6,6 +6,7 @@
 #define M4Q_KERNEL_TU 1
 #include "m4q_args.h"
 #include "m4q_mpc.h"
+#include "m4q_noise.h"
 #include "m4q_tile3.h"
 
 #ifndef M4Q_NX
@@ -978,6 +979,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
             else xc = plant_generator<NX, NU>(xc, ui, op0, ops, dt, jio);
           }
           xn = xc;
+          // measurement noise (m4q_session_set_noise; m4q_noise.h): added to the measured state in complex original-basis form, so
+          // that it is stored, converted and carried like the plant's own result and the exit condition below reads it back.  Lanes
+          // that shadow column NX - 1 draw that column's noise (jio) and store nothing.  Mode 0: one scalar branch.
+          const int nmode = a->noise_mode;
+          if (nmode != 0) {
+            const bool add = ok && measure;
+            const double sg = add ? gld(a->noise_sigma, b * a->noise_sigma_stride) : 0.0;
+            const cplx e = noise_sample(nmode, a->noise_seed, a->noise_member_base + (unsigned long long)b, (unsigned)(step + 1), jio,
+                                        SQUARE ? DD : 0, sg);
+            if (add) xn = cadd(xn, e);
+          }
         }
         double tnew = 0.0;
         S rn = Basis<S, TL>::template to_state<NX, DD>(xn, scratch, j, jj, tnew);
@@ -1321,6 +1333,19 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_kernel(PlantArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The measurement noise of B members at one column of xs (noise.py: MeasurementNoise.sample), one component per lane, by the
+// device function the closed loop calls: a run's noise realisation without the run.
+__global__ __launch_bounds__(64) void noise_sample_kernel(NoiseArgs a) {
+  const long total = (long)a.B * NX;
+  for (long e = blockIdx.x * 64L + threadIdx.x; e < total; e += gridDim.x * 64L) {
+    const long b = e / NX;
+    const int comp = (int)(e - b * NX);
+    const double sg = gld(a.sigma, b * a.sigma_stride);
+    gst(a.out, e, noise_sample(a.mode, a.seed, a.member_base + (unsigned long long)b, a.state_index, comp, SQUARE ? DD : 0, sg));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // discretize_homogeneous for B generator sets (vectorize.py:8-49): Taylor/Dyson expansion of
 // exp(dt (G_0 + sum_k u_k G_k)) to ORDER, every word of operators multiplied out and binned by its control
 // monomial.  One row per instance; generators staged in LDS, products column-owned in registers.
@@ -1557,8 +1582,15 @@ static int launch_plant(const PlantArgs& a, hipStream_t s) {
   }
 }
 
+static int launch_noise(const NoiseArgs& a, hipStream_t s) {
+  const long blocks = ((long)a.B * NX + 63) / 64;
+  hipLaunchKernelGGL(noise_sample_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, s, a);
+  return -(int)hipGetLastError();
+}
+
 #else
 static int launch_plant(const PlantArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
+static int launch_noise(const NoiseArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
 #endif
 
 #if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
@@ -1596,7 +1628,7 @@ static const ShapeOps* shape_ops() {
   constexpr int plant_only = 0;
 #endif
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
-                               launch_discretize, power_list, occupancy};
+                               launch_discretize, power_list, occupancy, launch_noise};
   return &ops;
 }
 

@@ -430,8 +430,10 @@ def mpc_batch_sharded(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0
     transport: an RcclComm (default: RcclComm.from_env()) - the block runs on the rank's GPU with its outputs bound into the
     gather buffer.  Tests pass a host transport and `solver`, a host callable with mpc_batch's signature, whose results take
     the same packed path.  exit_condition (a QuadraticExit) is sliced like the ensemble: each rank's block gets its members' targets
-    and thresholds where those are per member."""
+    and thresholds where those are per member.  noise (a MeasurementNoise) likewise: rank r passes member_base + (first member of
+    its block) and its slice of a per-member sigma, so a member draws the same numbers whatever the world size."""
     from .mpc import check_batch_exit, open_session
+    from .noise import check_batch_noise
     # (before the transport exists: a rank that raises here has joined nothing)
     if models is not None and kw.get("generators") is not None:
         raise ValueError("pass models or generators (and scales), not both")
@@ -440,6 +442,8 @@ def mpc_batch_sharded(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0
                          "takes" % (np.shape(x0)[0], np.shape(kw["scales"])))
     check_batch_exit(kw.get("exit_condition"), np.shape(x0)[0], np.shape(x0)[1], kw.get("plant_kind", _lib.PLANT_HAMILTONIAN),
                      "mpc_batch_sharded")
+    check_batch_noise(kw.get("noise"), np.shape(x0)[0], np.shape(x0)[1], kw.get("plant_kind", _lib.PLANT_HAMILTONIAN),
+                      "mpc_batch_sharded")
     own = transport is None
     if own:
         transport = RcclComm.from_env()
@@ -451,6 +455,9 @@ def mpc_batch_sharded(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0
     if kw.get("exit_condition") is not None:
         kw = dict(kw)
         kw["exit_condition"] = kw["exit_condition"].block(lo, hi, B)
+    if kw.get("noise") is not None:
+        kw = dict(kw)
+        kw["noise"] = kw["noise"].block(lo, hi, B)
     counts = [shard_bounds(B, r, world)[1] - shard_bounds(B, r, world)[0] for r in range(world)]
     rows = max(counts)
     if transport.on_device and min(counts) == 0:

@@ -10,9 +10,12 @@ from abc import ABC, abstractmethod
 import numpy as np
 
 from . import _lib
+from .noise import require_noise
 
 
 class Experiment(ABC):
+    device_noise = None          # a MeasurementNoise mpc() adds on the device (QExperiment.set_noise, QSynthesis.set_noise)
+
     def __init__(self):
         self.ts = None
         self.us = None
@@ -115,6 +118,12 @@ class QExperiment(Experiment):
     def set_sigma(self, sigma):
         self._sigma = sigma
 
+    def set_noise(self, noise):
+        """Measurement noise mpc() adds on the device (a MeasurementNoise, or None): unlike set_sigma - np.random on the host, one
+        launch per MPC step - the closed loop stays fused and the run is reproducible from the seed.  simulate() itself stays
+        noise-free; mpc() refuses an experiment with both this and a non-zero sigma."""
+        self.device_noise = require_noise(noise, "QExperiment.set_noise")
+
     def simulate(self, x0, ts, us):
         """Piecewise-constant control (interp1d kind='previous', mpc.py:258): `us` is a callable of
         time or an (m, len(ts)) array whose column i is held on [ts[i], ts[i+1])."""
@@ -200,6 +209,10 @@ class QSynthesis(Experiment):
             raise ValueError("QSynthesis: collapse operators (c_ops) are not supported - the process plant propagates a unitary's "
                              "process vector U (x) U^*; open-system process maps are out of scope")
         self._prop_args[key] = value
+
+    def set_noise(self, noise):
+        """Measurement noise mpc() adds on the device (a MeasurementNoise of kind "iid", or None): see QExperiment.set_noise."""
+        self.device_noise = require_noise(noise, "QSynthesis.set_noise")
 
     def operators(self):
         """(op0, ops) for the device plant: the d x d Hamiltonians."""

@@ -13,6 +13,7 @@ from .exit_condition import QuadraticExit, require_device_exit
 from .experiment import Experiment, QExperiment, QSynthesis
 from .library import krtimes
 from .linearize import WrapModel
+from .noise import check_batch_noise, require_noise
 from .session import EnsembleSession
 
 
@@ -161,7 +162,13 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
     A QSynthesis experiment (gate synthesis) runs on its process vector with the identity as the loop's lift: x0, the states
     returned and the states exit_condition sees are process vectors vec_r(U (x) U^*).
     exit_condition: any callable exit_condition(x_next, x, u) runs the loop on the host, one launch per MPC step; a QuadraticExit
-    with a native plant or QSynthesis (and no streaming) keeps the loop fused: the kernel evaluates it after every step."""
+    with a native plant or QSynthesis (and no streaming) keeps the loop fused: the kernel evaluates it after every step.
+    Measurement noise: experiment.set_noise(MeasurementNoise(...)) keeps the loop fused - the kernel draws the noise of member
+    `member_base` - and a loop that runs step by step for another reason adds the same draws here, after simulate: the same run
+    either way.  set_sigma alone is the reference's np.random noise on the host path, as before; both on one experiment raise."""
+    noise = require_noise(getattr(experiment, "device_noise", None), "mpc (experiment.device_noise)")
+    if noise is not None and getattr(experiment, "_sigma", 0):
+        raise ValueError("the experiment has both device noise (set_noise) and a non-zero sigma (set_sigma): choose one")
     mf = int(clock.measure_freq)
     x0 = np.asarray(x0, dtype=np.complex128).reshape(-1)
     lift, proj = _loop_maps(experiment)
@@ -175,14 +182,24 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
     cols = min(X_targ.shape[1], ns + T + 1)
     fused = _runs_fused(experiment, exit_condition, streaming)
     kind = experiment.plant_kind if fused else _lib.PLANT_NONE
+    if noise is not None:                        # (stepwise: added to what simulate returns, in the plant's own space)
+        if fused:
+            check_batch_noise(noise, 1, n, kind, "mpc")
+        else:
+            noise.check(1, x0.shape[0])
+    # stepwise with "iid" noise: the states handed back (put_state) are not Hermitian, so the QPs run the complex path, as the fused
+    # session does of its own accord (m4q_session_set_noise)
     sess = EnsembleSession(1, n, dim_u, order, T, ns, clock.dt, sat, du, max_iter, warm_start, qp_flags=qp_flags,
-                           plant_kind=kind, target_cols=cols, measure_freq=mf, exact_qp=exact_qp)
+                           plant_kind=kind, target_cols=cols, measure_freq=mf, exact_qp=exact_qp,
+                           force_complex=noise is not None and noise.kind == "iid" and not fused)
     try:
         op0, ops = experiment.operators() if fused else (None, None)
         sess.load_problem(np.hstack([A_x, A_u])[None], lift_x0[None], X_targ, U_targ, Q, R, Qf, op0, ops)
         if fused:
             if exit_condition is not None:
                 sess.set_exit_condition(exit_condition)
+            if noise is not None:
+                sess.set_noise(noise)
             sess.run(0, ns)
             res = sess.results()
             code, done = int(res["exit_codes"][0]), int(res["steps_done"][0])
@@ -222,7 +239,10 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
                 ts_step = clock.ts_step(step)
                 us_step = np.vstack([us[step - jq] for jq in range(mf)] + [us[step]]).T
                 result = experiment.simulate(xs[step + 1 - mf], ts_step, _HeldControl(ts_step, us_step))   # mpc.py:256-260
-                xs.append(np.asarray(result)[:, -1])
+                x_meas = np.asarray(result)[:, -1]
+                if noise is not None:                    # the draws the fused loop makes for this member and column of xs
+                    x_meas = x_meas + noise.sample([0], step + 1, x_meas.shape[0])[0]
+                xs.append(x_meas)
             else:
                 lx = np.asarray(lift(xs[step])).reshape(-1, 1)                                 # mpc.py:261-267
                 lu = wrapped.lift_u(u.reshape(-1, 1))
@@ -270,15 +290,17 @@ def check_batch_exit(cond, B, n, plant_kind, where):
 def open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_ops, Q, R, Qf, sat, du=None,
                  max_iter=100, warm_start=True, qp_flags=None, plant_kind=_lib.PLANT_HAMILTONIAN, device=-1,
                  force_complex=False, exact_qp=False, traceless=True, tile=None, generators=None, scales=None,
-                 shared_generators=None, exit_condition=None):
+                 shared_generators=None, exit_condition=None, noise=None):
     """An EnsembleSession loaded with mpc_batch's arguments (everything resident in HBM, nothing run yet).
     models = None with generators [1+m, n, n] (or [B, 1+m, n, n]) and optional scales [B, 1+m]: the members' models are built on the
     device (discretize_homogeneous of the scaled generators, vectorize.py:8-49), and a set of SHARED generators at order 1 lets the
     closed loop run on them directly where that kernel exists (d = 4; EnsembleSession(shared_generators=...)).
-    exit_condition: None or a QuadraticExit the kernel evaluates for every member (EnsembleSession.set_exit_condition)."""
+    exit_condition: None or a QuadraticExit the kernel evaluates for every member (EnsembleSession.set_exit_condition).
+    noise: None or a MeasurementNoise the kernel adds to every measured state (EnsembleSession.set_noise)."""
     x0 = np.ascontiguousarray(x0, dtype=np.complex128)
     Bn, n = x0.shape
     check_batch_exit(exit_condition, Bn, n, plant_kind, "open_session")
+    check_batch_noise(noise, Bn, n, plant_kind, "open_session")
     if models is None:
         if generators is None:
             raise TypeError("models is None: pass generators (and scales) to have the models built on the device")
@@ -311,6 +333,8 @@ def open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, pla
         sess.load_problem(models, x0, X_targ, U_targ, Q, R, Qf, op0, ops)
         if exit_condition is not None:
             sess.set_exit_condition(exit_condition)
+        if noise is not None:
+            sess.set_noise(noise)
     except Exception:
         sess.close()
         raise
@@ -320,7 +344,7 @@ def open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, pla
 def mpc_batch(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_ops, Q, R, Qf, sat, du=None,
               max_iter=100, warm_start=True, qp_flags=None, plant_kind=_lib.PLANT_HAMILTONIAN, device=-1,
               force_complex=False, exact_qp=False, traceless=True, tile=None, generators=None, scales=None, shared_generators=None,
-              exit_condition=None):
+              exit_condition=None, noise=None):
     """B independent closed loops in one launch.
     x0 [B, n]; models [B|1, n, n(1+P)] (or None with generators / scales: built on the device, see open_session);
     X_targ (n, cols) / U_targ (m, cols) shared (or [B, ...] each);
@@ -328,10 +352,12 @@ def mpc_batch(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_
     of n = d^4 entries and k = d, the gate's Hamiltonians - that plant always runs the complex path).  Returns a dict: xs [B, n, n_steps+1], us [B, m, n_steps]
     (entries beyond steps_done are not meaningful), exit_codes, steps_done, qp_solves [B, n_steps].
     exit_condition: None or a QuadraticExit, evaluated on the device; a member it stops has exit code 1 and steps_done = the step
-    after which it fired (that step's entries are dropped, as mpc() drops them)."""
+    after which it fired (that step's entries are dropped, as mpc() drops them).
+    noise: None or a MeasurementNoise: measurement noise drawn on the device for every member and measured step (kind "iid" runs
+    the complex path); member b of this call is member noise.member_base + b of the generator."""
     sess = open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_ops, Q, R, Qf, sat, du, max_iter,
                         warm_start, qp_flags, plant_kind, device, force_complex, exact_qp, traceless, tile, generators, scales,
-                        shared_generators, exit_condition)
+                        shared_generators, exit_condition, noise)
     try:
         sess.run(0, clock.n_steps)
         res = sess.results()

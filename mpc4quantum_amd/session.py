@@ -6,6 +6,7 @@ import numpy as np
 
 from . import _lib
 from .exit_condition import require_device_exit
+from .noise import check_batch_noise
 
 _DTYPES = {
     _lib.F_MODELS: np.complex128, _lib.F_X0: np.complex128, _lib.F_X_TARG: np.complex128, _lib.F_U_TARG: np.float64,
@@ -130,6 +131,19 @@ class EnsembleSession:
         thr = np.ascontiguousarray(cond.thr, dtype=np.float64).reshape(-1)
         _lib.check(L.m4q_session_set_exit(self._h, cond.mode, W.ctypes.data_as(_lib._dp), f.ctypes.data_as(_lib._dp),
                                           int(f.ndim == 2), thr.ctypes.data_as(_lib._dp), int(cond.thr.ndim == 1)))
+
+    def set_noise(self, noise):
+        """Have the kernel add a MeasurementNoise to every measured state before it is stored (m4q_session_set_noise); None clears
+        it.  Set it before the first run: later calls may change sigma, seed and member_base, not the kind.  Needs a device plant;
+        kind "iid" runs the complex path.  Like the exit condition it is a setting of the session, not part of state(): a
+        checkpoint restored into a fresh session continues the same run once that session is given the same noise."""
+        if noise is None:
+            _lib.check(self._L.m4q_session_set_noise(self._h, 0, None, 0, 0, 0))
+            return
+        check_batch_noise(noise, self.B, self.problem.dim_x, self.problem.plant_kind, "EnsembleSession.set_noise")
+        sg = np.ascontiguousarray(noise.sigma, dtype=np.float64).reshape(-1)
+        _lib.check(self._L.m4q_session_set_noise(self._h, noise.mode, sg.ctypes.data_as(_lib._dp), int(noise.sigma.ndim == 1),
+                                                 noise.seed, noise.member_base))
 
     def run(self, step_begin=0, step_end=None):
         _lib.check(self._L.m4q_session_run(self._h, int(step_begin), int(self.problem.n_steps if step_end is None else step_end)))
