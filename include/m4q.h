@@ -174,6 +174,30 @@ M4Q_API int m4q_plant_step_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
                          const double* u, const double* op0, const double* ops, int32_t plant_per_instance,
                          double* x_next);
 
+/* Open-loop rollouts: a known control sequence applied to B members over N steps in ONE launch (QExperiment.simulate /
+ * DMDc.predict along a sequence, for an ensemble).  The state stays in registers from x0 to the last step.
+ * x0 [B][n] c; u [B|1][N][m] r (u_per_instance 0: one sequence shared by the ensemble); u_scale [B][m] r or NULL: member b sees
+ * u_scale[b][k] u[t][k], formed on the device in fp64.
+ * Outputs, each optional: xs_mode 0 none, 1 the final state xs [B][n] c, 2 the whole trajectory xs [B][N+1][n] c (column 0 = x0 as
+ * given); q_mode 0 / 1 / 2 likewise the figure q = Re((x - f)^H W (x - f)) as q [B] or [B][N+1] r, with W [n][n] c shared and
+ * target f [B|1][n] c (both NULL when q_mode is 0).
+ * M4Q_E_BADARG: B or N < 1, a missing required array, a mode outside 0-2, both modes 0, q_mode != 0 without W or target, (plant) a
+ * plant_kind that is no device plant, M4Q_PLANT_PROCESS with n not a fourth power.  M4Q_E_UNSUPPORTED: no compiled shape, a plant
+ * rollout with n not a square, a model rollout on a plant-only shape.  Arguments are checked before the device is asked for.
+ *
+ * m4q_plant_rollout_batch: step t is the held-control step of m4q_plant_step_batch over dts[t] (dts [N] r: a non-uniform time grid
+ * works); op0 / ops as there. */
+M4Q_API int m4q_plant_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                            const double* x0, const double* u, int32_t u_per_instance, const double* u_scale, const double* op0,
+                            const double* ops, int32_t plant_per_instance, const double* W, const double* target,
+                            int32_t target_per_instance, int32_t xs_mode, double* xs, int32_t q_mode, double* q);
+/* m4q_model_rollout_batch: step t is x+ = A [x ; lift_u(u_t) (x) x] (model.py:81-93), what the closed loop applies on a step it does
+ * not measure; models [B|1][n][n(1+P)] c.  Complex arithmetic whatever the model. */
+M4Q_API int m4q_model_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* u,
+                            int32_t u_per_instance, const double* u_scale, const double* models, int32_t model_per_instance,
+                            const double* W, const double* target, int32_t target_per_instance, int32_t xs_mode, double* xs,
+                            int32_t q_mode, double* q);
+
 /* replaces the whole mpc() loop body (mpc.py:161-292) for B closed loops, all n_steps in one launch.
  * models [B|1][n][n(1+P)] c, x0 [B][n] c, X_targ [B|1][cols][n] c, U_targ [B|1][cols][m] r,
  * Q, Qf [n][n] c, R [m][m] c, op0/ops as in m4q_plant_step_batch

@@ -64,6 +64,10 @@ PROTOTYPES = {
     "m4q_discretize_batch": (C.c_int, [_i32, _i32, _i32, _i32, C.c_double, _dp, _i32, _dp, _dp]),
     "m4q_session_build_models": (C.c_int, [_vp, C.c_double, _dp, _i32, _dp]),
     "m4q_plant_step_batch": (C.c_int, [_i32, _i32, _i32, _i32, C.c_double, _dp, _dp, _dp, _dp, _i32, _dp]),
+    "m4q_plant_rollout_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _i32,
+                                          _i32, _dp, _i32, _dp]),
+    "m4q_model_rollout_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _i32, _dp,
+                                          _i32, _dp]),
     "m4q_mpc_batch": (C.c_int, [C.POINTER(Problem), _i32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
                                 _ip, _ip]),
     "m4q_session_create": (C.c_int, [C.POINTER(Problem), _i32, _i32, C.POINTER(_vp)]),

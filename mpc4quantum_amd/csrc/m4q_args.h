@@ -124,6 +124,23 @@ struct PlantArgs {
   M4Q_P(cplx) x_next;
 };
 
+// Open-loop rollouts (m4q_plant_rollout_batch, m4q_model_rollout_batch): N held-control steps of B members in one launch.
+// The member sees u_scale[b][k] u[t][k] (u_scale may be null); the plant advances by dts[t], the model by one of its own steps.
+// xs_mode / q_mode: 0 nothing, 1 the last column ([B][n], [B]), 2 every column ([B][N + 1][n], [B][N + 1]; column 0 = x0).
+// q = Re((x - f)^H W (x - f)), W [n][n] shared, f [B|1][n] (target_stride n or 0)
+struct RollArgs {
+  int B, N, kind, xs_mode, q_mode;
+  M4Q_P(const double) dts;                         // [N] (plant rollout)
+  M4Q_P(const cplx) x0;                            // [B][n]
+  M4Q_P(const double) u; long u_stride;            // [B|1][N][m] (u_stride N m or 0)
+  M4Q_P(const double) u_scale;                     // [B][m] or null
+  M4Q_P(const cplx) op0; long op0_stride;          // plant operators, as PlantArgs
+  M4Q_P(const cplx) ops; long ops_stride;
+  M4Q_P(const cplx) models; long model_stride;     // [B|1][n][n(1+P)], as LinArgs (model rollout)
+  M4Q_P(const cplx) W; M4Q_P(const cplx) target; long target_stride;
+  M4Q_P(cplx) xs; M4Q_P(double) q;
+};
+
 // noise.py's sample() for B members at one state_index (m4q_noise_sample_batch): out [B][n] complex
 struct NoiseArgs {
   int B, mode;
@@ -148,6 +165,8 @@ struct ShapeOps {
   int (*power_list)(int32_t* out);
   int (*occupancy)(int plant_kind, Path path, int exact_qp);       // resident workgroups per CU of the fused kernel
   int (*launch_noise)(const NoiseArgs&, hipStream_t);             // (depends on dim_x alone)
+  int (*launch_plant_rollout)(const RollArgs&, hipStream_t);      // (square shapes, plant-only ones included)
+  int (*launch_model_rollout)(const RollArgs&, hipStream_t);      // (every shape with a model)
 };
 
 }  // namespace m4q

@@ -1248,6 +1248,112 @@ int m4q_plant_step_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_
   return down(x_next, d_o, (size_t)B * n * C);
 }
 
+namespace {
+// the arguments the two rollouts share, checked before a device is asked for
+int check_roll_args(const char* who, int32_t B, int32_t N, const double* x0, const double* u, const double* W, const double* target,
+                    int32_t xs_mode, double* xs, int32_t q_mode, double* q) {
+  if (B < 1 || N < 1) return fail(M4Q_E_BADARG, "%s: B and N must be at least 1 (got %d, %d)", who, B, N);
+  if (!x0 || !u) return fail(M4Q_E_BADARG, "%s: x0 and u are required", who);
+  if (xs_mode < 0 || xs_mode > 2 || q_mode < 0 || q_mode > 2)
+    return fail(M4Q_E_BADARG, "%s: xs_mode and q_mode are 0 (none), 1 (last) or 2 (all), got %d and %d", who, xs_mode, q_mode);
+  if (xs_mode == 0 && q_mode == 0) return fail(M4Q_E_BADARG, "%s: nothing to return (xs_mode and q_mode are both 0)", who);
+  if (xs_mode != 0 && !xs) return fail(M4Q_E_BADARG, "%s: xs_mode %d without xs", who, xs_mode);
+  if (q_mode != 0 && (!q || !W || !target)) return fail(M4Q_E_BADARG, "%s: q_mode %d needs W, target and q", who, q_mode);
+  return 0;
+}
+
+// uploads what the two rollouts share, launches, downloads what was asked for
+struct RollCall {
+  Tmp t;
+  m4q::RollArgs a{};
+  void *d_xs = nullptr, *d_q = nullptr;
+  size_t xs_bytes = 0, q_bytes = 0;
+  int prepare(int32_t B, size_t n, size_t m, int32_t N, const double* x0, const double* u, int32_t u_per_instance, const double* u_scale,
+              const double* W, const double* target, int32_t target_per_instance, int32_t xs_mode, int32_t q_mode) {
+    const size_t C = 16;
+    int rc;
+    a.B = B; a.N = N; a.xs_mode = xs_mode; a.q_mode = q_mode;
+    void *d_x0, *d_u, *d_s, *d_W, *d_f;
+    if ((rc = t.up(x0, (size_t)B * n * C, &d_x0))) return rc;
+    if ((rc = t.up(u, (size_t)(u_per_instance ? B : 1) * N * m * 8, &d_u))) return rc;
+    a.x0 = (const cplx*)d_x0; a.u = (const double*)d_u; a.u_stride = u_per_instance ? (long)((size_t)N * m) : 0;
+    if (u_scale) {
+      if ((rc = t.up(u_scale, (size_t)B * m * 8, &d_s))) return rc;
+      a.u_scale = (const double*)d_s;
+    }
+    if (q_mode != 0) {
+      if ((rc = t.up(W, n * n * C, &d_W))) return rc;
+      if ((rc = t.up(target, (size_t)(target_per_instance ? B : 1) * n * C, &d_f))) return rc;
+      a.W = (const cplx*)d_W; a.target = (const cplx*)d_f; a.target_stride = target_per_instance ? (long)n : 0;
+      q_bytes = (size_t)B * (q_mode == 2 ? (size_t)N + 1 : 1) * 8;
+      if ((rc = t.up(nullptr, q_bytes, &d_q))) return rc;
+      a.q = (double*)d_q;
+    }
+    if (xs_mode != 0) {
+      xs_bytes = (size_t)B * (xs_mode == 2 ? (size_t)N + 1 : 1) * n * C;
+      if ((rc = t.up(nullptr, xs_bytes, &d_xs))) return rc;
+      a.xs = (cplx*)d_xs;
+    }
+    return 0;
+  }
+  int finish(int launch_rc, const char* what, double* xs, double* q) {
+    if (launch_rc) return fail(launch_rc, "%s launch failed", what);
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = down(xs, d_xs, xs_bytes)) return rc;
+    return down(q, d_q, q_bytes);
+  }
+};
+}  // namespace
+
+int m4q_plant_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                            const double* x0, const double* u, int32_t u_per_instance, const double* u_scale, const double* op0,
+                            const double* ops, int32_t plant_per_instance, const double* W, const double* target,
+                            int32_t target_per_instance, int32_t xs_mode, double* xs, int32_t q_mode, double* q) {
+  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d", dim_x, dim_u);
+  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "m4q_plant_rollout_batch: dim_x=%d is not a square, there is no device plant", dim_x);
+  if (int rc = check_roll_args("m4q_plant_rollout_batch", B, N, x0, u, W, target, xs_mode, xs, q_mode, q)) return rc;
+  if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "m4q_plant_rollout_batch: dts, op0 and ops are required");
+  if (plant_kind != M4Q_PLANT_HAMILTONIAN && plant_kind != M4Q_PLANT_GENERATOR && plant_kind != M4Q_PLANT_PROCESS)
+    return fail(M4Q_E_BADARG, "m4q_plant_rollout_batch: plant_kind %d is not a device plant", plant_kind);
+  if (plant_kind == M4Q_PLANT_PROCESS && dim_q(dim_x) == 0)
+    return fail(M4Q_E_BADARG, "M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", dim_x);
+  int rc = need_device();
+  if (rc) return rc;
+  const size_t n = dim_x, m = dim_u, C = 16;
+  const size_t k = plant_dim(plant_kind, dim_x);
+  RollCall c;
+  if ((rc = c.prepare(B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, xs_mode, q_mode))) return rc;
+  c.a.kind = plant_kind;
+  void *d_t, *d_0, *d_k;
+  if ((rc = c.t.up(dts, (size_t)N * 8, &d_t))) return rc;
+  if ((rc = c.t.up(op0, (plant_per_instance ? B : 1) * k * k * C, &d_0))) return rc;
+  if ((rc = c.t.up(ops, (plant_per_instance ? B : 1) * m * k * k * C, &d_k))) return rc;
+  c.a.dts = (const double*)d_t;
+  c.a.op0 = (const cplx*)d_0; c.a.op0_stride = plant_per_instance ? (long)(k * k) : 0;
+  c.a.ops = (const cplx*)d_k; c.a.ops_stride = plant_per_instance ? (long)(m * k * k) : 0;
+  return c.finish(sh->launch_plant_rollout(c.a, nullptr), "plant rollout", xs, q);
+}
+
+int m4q_model_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* u,
+                            int32_t u_per_instance, const double* u_scale, const double* models, int32_t model_per_instance,
+                            const double* W, const double* target, int32_t target_per_instance, int32_t xs_mode, double* xs,
+                            int32_t q_mode, double* q) {
+  const m4q::ShapeOps* sh = find_shape(dim_x, dim_u, order);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no model kernel for dim_x=%d dim_u=%d order=%d", dim_x, dim_u, order);
+  if (int rc = check_roll_args("m4q_model_rollout_batch", B, N, x0, u, W, target, xs_mode, xs, q_mode, q)) return rc;
+  if (!models) return fail(M4Q_E_BADARG, "m4q_model_rollout_batch: models are required");
+  int rc = need_device();
+  if (rc) return rc;
+  const size_t n = dim_x, m = dim_u, P = sh->np, C = 16;
+  RollCall c;
+  if ((rc = c.prepare(B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, xs_mode, q_mode))) return rc;
+  void* d_m;
+  if ((rc = c.t.up(models, (model_per_instance ? B : 1) * n * n * (1 + P) * C, &d_m))) return rc;
+  c.a.models = (const cplx*)d_m; c.a.model_stride = model_per_instance ? (long)(n * n * (1 + P)) : 0;
+  return c.finish(sh->launch_model_rollout(c.a, nullptr), "model rollout", xs, q);
+}
+
 int m4q_mpc_batch(const m4q_problem* p, int32_t B, const double* models, const double* x0, const double* X_targ,
                   const double* U_targ, const double* Q, const double* R, const double* Qf, const double* op0,
                   const double* ops, double* xs, double* us, int32_t* exit_codes, int32_t* steps_done,

@@ -1173,6 +1173,63 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
   }
 }
 
+#ifndef M4Q_VARIANT_GEN
+// ---------------------------------------------------------------------------------------------
+// Open-loop rollouts (RollArgs): what a member stores of column t of its trajectory - the state, and / or the figure
+// q = Re((x - f)^H W (x - f)), row j of W against the DPP broadcast of x - f as the exit condition of mpc_kernel forms it.
+// The modes and t are wave-uniform: branches on them keep all 64 lanes active for the broadcasts; the stores are masked.
+struct RollOut {
+  int N, xs_mode, q_mode;
+  M4Q_GLOBAL cplx* xs; M4Q_GLOBAL double* q;
+  const M4Q_GLOBAL cplx* Wr;        // row j of W
+  cplx f;                           // this lane's entry of the member's f
+  long b;
+  int j;
+  bool st, st0;                     // this lane stores its state entry / its row's figure
+  __device__ __forceinline__ RollOut(const RollArgs& a, long b_, int j_, bool st_, bool st0_)
+      : N(a.N), xs_mode(a.xs_mode), q_mode(a.q_mode), xs(a.xs), q(a.q), Wr(a.W + j_ * NX), f(czero()), b(b_), j(j_), st(st_), st0(st0_) {
+    if (q_mode != 0) f = gld(a.target, b * a.target_stride + j);
+  }
+  __device__ __forceinline__ void put(int t, cplx x) const {
+    const bool last = t == N;
+    if (xs_mode == 2) {
+      if (st) gst(xs, (b * (N + 1) + t) * NX + j, x);
+    } else if (xs_mode == 1 && last) {
+      if (st) gst(xs, b * NX + j, x);
+    }
+    if (q_mode == 2 || (q_mode == 1 && last)) {
+      const cplx d = csub(x, f);
+      cplx y = czero();
+      static_for<0, NX>([&](auto k) { cmac(y, gld(Wr, decltype(k)::value), bcast<decltype(k)::value>(d)); });
+      const double qv = rowsum<NX>(dot_re(d, y));
+      if (st0) gst(q, q_mode == 2 ? b * (N + 1) + t : b, qv);
+    }
+  }
+};
+// the controls of one step as the member sees them: u_scale[b][k] u[t][k], formed here in fp64
+struct RollCtl {
+  const M4Q_GLOBAL double* u;      // the member's (or the shared) sequence [N][NU]
+  double sc[NU], un[NU];
+  int N;
+  __device__ __forceinline__ RollCtl(const RollArgs& a, long b) : u(a.u + b * a.u_stride), N(a.N) {
+#pragma unroll
+    for (int k = 0; k < NU; ++k) {
+      sc[k] = a.u_scale ? gld(a.u_scale, b * NU + k) : 1.0;
+      un[k] = gld(u, k);
+    }
+  }
+  // the controls of step t (fetched one step ago); issues the loads of step t + 1, which the arithmetic of step t then covers
+  __device__ __forceinline__ void take(int t, double (&ut)[NU]) {
+    const int tn = t + 1 < N ? t + 1 : t;
+#pragma unroll
+    for (int k = 0; k < NU; ++k) {
+      ut[k] = sc[k] * un[k];
+      un[k] = gld(u, (long)tn * NU + k);
+    }
+  }
+};
+#endif  // M4Q_VARIANT_GEN
+
 #ifndef M4Q_NO_AUX          // (a plant-only shape - m4q_shapes.inc - builds plant_kernel alone; the generator-plant object none of these)
 // ---------------------------------------------------------------------------------------------
 // WrapModel.get_model_along_traj for B trajectories (linearize.py:61-70)
@@ -1212,6 +1269,45 @@ __global__ __launch_bounds__(64) M4Q_OCC void linearize_kernel(LinArgs a) {
         for (int k = 0; k < NU; ++k) Bo.st<cplx>((t * NX + j) * NU + k, Brow[k]);
         Do.st<cplx>(t * NX + j, dlt);
       }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Open-loop rollout of B models over N steps (model.py:81-93: x+ = A [x ; lift_u(u) (x) x]), one launch: the member's model (or
+// the shared one) staged in LDS as above, the state in registers, each step the call mpc_kernel makes for a step that is not
+// measured.  Complex path.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) M4Q_OCC void model_rollout_kernel(RollArgs a) {
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const LaneGeo L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* mdl = lds + g * MODEL_ELEMS;
+  const int nquads = (a.B + ROWS - 1) / ROWS;
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const long q0 = (long)quad * ROWS;
+    const bool valid = q0 + g < a.B;
+    const unsigned gl = valid ? g : (unsigned)(a.B - 1 - q0);
+    const long b = q0 + gl;
+    wave_sync();
+    stage_model<NX>(mdl, a.models + b * a.model_stride, jj);
+    wave_sync();
+    FusedProv<cplx, NX, NU, ORDER> prov;
+    prov.mdl = mdl;
+    prov.Xg = prov.Ug = gview(a.x0, 0, 0);         // (rows() reads neither)
+    prov.j = j;
+    const RollOut out(a, b, j, valid && L.lane_ok, valid && jj == 0);
+    RollCtl ctl(a, b);
+    cplx x = gld(a.x0, b * NX + j);
+    out.put(0, x);
+    for (int t = 0; t < a.N; ++t) {
+      FusedProv<cplx, NX, NU, ORDER>::Lin lin;
+      ctl.take(t, lin.u);
+      lin.xg = x;
+      cplx pred, Bdummy[NU], ddummy;
+      prov.rows(lin, x, pred, Bdummy, ddummy);      // A x + N (polyu (x) x) = A_t(u) x
+      x = pred;
+      out.put(t + 1, x);
     }
   }
 }
@@ -1329,6 +1425,49 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_kernel(PlantArgs a) {
     else
       xn = plant_generator<NX, NU>(x, u, op0, ops, a.dt, j);
     if (valid && jj < NX) gst(a.x_next, b * NX + j, xn);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Open-loop rollout of B plants over N held-control intervals, one launch (QExperiment.simulate for an ensemble): the state stays
+// in registers from x0 to the last step, each step is the device function plant_kernel calls, over dts[t].
+template <int PLANT>
+__global__ __launch_bounds__(64) M4Q_OCC void plant_rollout_kernel(RollArgs a) {
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const LaneGeo L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* scratch = lds + g * SCRATCH_ELEMS;
+  const int nquads = (a.B + ROWS - 1) / ROWS;
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const long q0 = (long)quad * ROWS;
+    const bool valid = q0 + g < a.B;
+    const unsigned gl = valid ? g : (unsigned)(a.B - 1 - q0);
+    const long b = q0 + gl;
+    const GView op0 = gview(a.op0, q0 * a.op0_stride, gl * (unsigned)a.op0_stride);
+    const GView ops = gview(a.ops, q0 * a.ops_stride, gl * (unsigned)a.ops_stride);
+    const RollOut out(a, b, j, valid && L.lane_ok, valid && jj == 0);
+    RollCtl ctl(a, b);
+    double dtn = gld(a.dts, 0);
+    cplx x = gld(a.x0, b * NX + j);
+    out.put(0, x);
+    for (int t = 0; t < a.N; ++t) {
+      double u[NU];
+      ctl.take(t, u);
+      const double dt = dtn;
+      dtn = gld(a.dts, t + 1 < a.N ? t + 1 : t);
+      // The generator's (1 + m) n operator entries per lane are read again at every step, as plant_kernel reads them at every
+      // launch (L2 hits): hoisted out of the step loop - the offsets are made opaque here to prevent it - they spill (d = 3: 102
+      // VGPRs against 49, d = 4: 68 against 6).  The d or (1 + m) d entries of the other two plants stay in registers.
+      GView o0 = op0, ok = ops;
+      if constexpr (PLANT == PLANT_GENERATOR) asm volatile("" : "+v"(o0.off), "+v"(ok.off));
+      if constexpr (PLANT == PLANT_HAMILTONIAN)
+        x = plant_hamiltonian<NX, NU, DD>(x, u, o0, ok, dt, scratch, j, jj);
+      else if constexpr (PLANT == PLANT_PROCESS)
+        x = plant_process<NX, NU, DQ>(x, u, o0, ok, dt, scratch, j, jj);
+      else
+        x = plant_generator<NX, NU>(x, u, o0, ok, dt, j);
+      out.put(t + 1, x);
+    }
   }
 }
 
@@ -1560,9 +1699,18 @@ static int launch_qp(const QpArgs& a, hipStream_t s) {
   return -(int)hipGetLastError();
 }
 
+static int launch_model_rollout(const RollArgs& a, hipStream_t s) {
+  const size_t lds = sizeof(cplx) * (size_t)(ROWS * MODEL_ELEMS);
+  int rc = prep_lds(model_rollout_kernel, lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(model_rollout_kernel, dim3(grid_for(a.B)), dim3(64), lds, s, a);
+  return -(int)hipGetLastError();
+}
+
 #else
 static int launch_linearize(const LinArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
 static int launch_qp(const QpArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
+static int launch_model_rollout(const RollArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
 #endif
 
 #ifndef M4Q_VARIANT_GEN
@@ -1588,9 +1736,26 @@ static int launch_noise(const NoiseArgs& a, hipStream_t s) {
   return -(int)hipGetLastError();
 }
 
+static int launch_plant_rollout(const RollArgs& a, hipStream_t s) {
+  if constexpr (!SQUARE) {
+    return -(int)hipErrorInvalidValue;
+  } else {
+  const size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
+  if (a.kind == PLANT_HAMILTONIAN)
+    hipLaunchKernelGGL(plant_rollout_kernel<PLANT_HAMILTONIAN>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
+  else if (a.kind == PLANT_PROCESS) {
+    if constexpr (QUARTIC) hipLaunchKernelGGL(plant_rollout_kernel<PLANT_PROCESS>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
+    else return -(int)hipErrorInvalidValue;
+  } else
+    hipLaunchKernelGGL(plant_rollout_kernel<PLANT_GENERATOR>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
+  return -(int)hipGetLastError();
+  }
+}
+
 #else
 static int launch_plant(const PlantArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
 static int launch_noise(const NoiseArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
+static int launch_plant_rollout(const RollArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
 #endif
 
 #if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
@@ -1628,7 +1793,7 @@ static const ShapeOps* shape_ops() {
   constexpr int plant_only = 0;
 #endif
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
-                               launch_discretize, power_list, occupancy, launch_noise};
+                               launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout};
   return &ops;
 }
 

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib
 from .noise import require_noise
+from .rollout import held_controls, plant_rollout_batch
 
 
 class Experiment(ABC):
@@ -65,6 +66,17 @@ def plant_step_batch(x, u, op0, ops, dt, kind=_lib.PLANT_HAMILTONIAN):
     _lib.check(L.m4q_plant_step_batch(Bn, n, m, int(kind), float(dt), _lib.cbuf(x)[1], _lib.rbuf(u)[1], _lib.cbuf(op0)[1],
                                       _lib.cbuf(ops)[1], per, out.ctypes.data_as(_lib._dp)))
     return out
+
+
+def _simulate_batch(exp, x0s, ts, us, op0, u_scale, W, target, keep, figure):
+    """simulate_batch of the three device plants: the plant's own operators() unless per-member op0 [B, k, k] is given."""
+    x0s = np.asarray(x0s, dtype=np.complex128)
+    if x0s.ndim == 1:
+        x0s = x0s[None]
+    own0, ops = exp.operators()
+    u = held_controls(us, ts, len(exp.H1_list), x0s.shape[0])
+    return plant_rollout_batch(x0s, u, own0 if op0 is None else op0, ops, ts, exp.plant_kind, u_scale=u_scale, W=W, target=target,
+                               keep=keep, figure=figure)
 
 
 class QExperiment(Experiment):
@@ -147,6 +159,14 @@ class QExperiment(Experiment):
             noise = np.random.randn(*self.xs.shape) + 1j * np.random.randn(*self.xs.shape)
             return self.xs + noise * self._sigma
         return self.xs
+
+    def simulate_batch(self, x0s, ts, us, op0=None, u_scale=None, W=None, target=None, keep="all", figure="none"):
+        """simulate() for an ensemble in one launch (plant_rollout_batch): x0s [B, n]; `us` as simulate() takes it - a callable of
+        time or an (m, len(ts)) array, one sequence for all members - or (B, m, len(ts)) per member; op0 [B, k, k]: the members' own
+        drift operators in place of this plant's (of operators(): the Lindblad generator when there are collapse operators);
+        u_scale [B, m]: the members' drive-amplitude factors.  Returns the dict of plant_rollout_batch: "xs" [B, len(ts), n] (ensemble
+        axis first) and / or "q".  Noise-free, and no expectation values: e_ops, set_sigma and set_noise act on simulate() and mpc()."""
+        return _simulate_batch(self, x0s, ts, us, op0, u_scale, W, target, keep, figure)
 
 
 class LExperiment(QExperiment):
@@ -264,6 +284,14 @@ class QSynthesis(Experiment):
         self.ts, self.us = ts, us
         self.xs = np.stack(cols, axis=1)
         return self.xs
+
+    def simulate_batch(self, x0s, ts, us, op0=None, u_scale=None, W=None, target=None, keep="all", figure="none"):
+        """simulate() for an ensemble in one launch (plant_rollout_batch): x0s [B, n]; `us` as simulate() takes it - a callable of
+        time or an (m, len(ts)) array, one sequence for all members - or (B, m, len(ts)) per member; op0 [B, k, k]: the members' own
+        drift operators in place of this plant's (d x d Hamiltonians);
+        u_scale [B, m]: the members' drive-amplitude factors.  Returns the dict of plant_rollout_batch: "xs" [B, len(ts), n] (ensemble
+        axis first) and / or "q".  Noise-free, and no expectation values: e_ops, set_sigma and set_noise act on simulate() and mpc()."""
+        return _simulate_batch(self, x0s, ts, us, op0, u_scale, W, target, keep, figure)
 
 
 def split_blocks(bmatrix, nrows, ncols):

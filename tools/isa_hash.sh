@@ -9,7 +9,8 @@ cur=None; h={}
 for line in sys.stdin:
     m=re.match(r'^[0-9a-f]+ <(\S+)>:', line)
     if m: cur=m.group(1); h[cur]=hashlib.sha256(); continue
-    if cur and re.match(r'\s+\S', line):
+    # ('...' is the zero padding up to the next symbol's alignment: it follows what comes after the kernel, not the kernel)
+    if cur and re.match(r'\s+\S', line) and line.strip() != '...':
         # drop addresses / encodings / resolved branch targets: the instruction text only
         h[cur].update(re.sub(r'\s*//.*', '', line).strip().encode()+b'\n')
 for k in sorted(h): print(h[k].hexdigest()[:16], k)
