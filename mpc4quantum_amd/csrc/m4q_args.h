@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "m4q_paths.h"      // enum Path, enum Coords
+
 // Pointer fields of the argument blocks: plain pointers for the host pass; for the device pass the SAME 8 bytes typed as
 // global-address-space pointers, so that a pointer read out of the kernarg segment at its point of use (kargs() in
 // m4q_kernels.hip) still yields global_load / global_store instructions, not flat ones.
@@ -29,16 +31,6 @@ enum : int {
   QP_NO_TILE = 512,      // internal (the session may not take PATH_TILE: the exact traceless kernel holds both forms of the pinned sweep)
 };
 
-// Arithmetic paths of the closed loop (m4q_session_path returns these values; session.path_detail() indexes by them)
-enum Path : int {
-  PATH_COMPLEX = 0,     // complex recursion on vec(rho): any model
-  PATH_REAL = 1,        // real recursion in the Hermitian operator basis (n coordinates)
-  PATH_TRACELESS = 2,   // real recursion on the n - 1 traceless coordinates
-  PATH_TILE = 3,        // PATH_TRACELESS with the backward sweep (clipped) / the pinned sweep (exact) on matrix-core tiles
-  PATH_SG = 4,          // PATH_TRACELESS, clipped solve, on shared generators instead of per-member models
-};
-// Coordinate systems the recursion's inputs are held in
-enum Coords : int { COORDS_COMPLEX = 0, COORDS_HERM = 1, COORDS_TRACELESS = 2 };
 constexpr Coords coords_of(Path p) { return p == PATH_COMPLEX ? COORDS_COMPLEX : p == PATH_REAL ? COORDS_HERM : COORDS_TRACELESS; }
 
 // Arrays marked S are complex (cplx) on the general path and double on the real path (models that preserve

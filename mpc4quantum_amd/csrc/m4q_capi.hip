@@ -11,17 +11,23 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/m4q.h"
 #include "m4q_args.h"
+#include "m4q_lift.h"
 
 namespace m4q {
 struct cplx { double re, im; };
 }
 using m4q::cplx;
+using m4q::lift::Lift;
+using m4q::lift::LiftStat;
+using m4q::lift::lift_blocks;
+using m4q::lift::lift_vectors;
 
 // per-shape registration functions (m4q_kernels.hip compiled once per shape)
 #define M4Q_SHAPE(nx, nu, ord) extern "C" const m4q::ShapeOps* m4q_shape_##nx##_##nu##_##ord();
@@ -126,6 +132,37 @@ size_t plant_dim(int kind, int nx) {
   return kind == M4Q_PLANT_GENERATOR ? (size_t)nx : kind == M4Q_PLANT_PROCESS ? (size_t)dim_q(nx) : (size_t)dim_d(nx);
 }
 
+// An array that is per instance or shared, [B|1][elems]: the elements to allocate and the stride from one member's to the next
+// (0: shared), from one expression - a size and a stride that disagree make a kernel read past its buffer.
+struct Extent {
+  size_t count;
+  long stride;
+  Extent(size_t B, bool per_instance, size_t elems) : count((per_instance ? B : 1) * elems), stride(per_instance ? (long)elems : 0) {}
+};
+
+int need_device() {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n == 0) return fail(M4Q_E_NODEVICE, "no HIP device: %s", hipGetErrorString(e));
+  return 0;
+}
+
+int check_qp_flags(int32_t qp_flags) {
+  if (qp_flags & ~(M4Q_QP_REF_LQR | M4Q_QP_DU_BAND | M4Q_QP_EXACT_BOX))
+    return fail(M4Q_E_BADARG, "qp_flags has bits outside M4Q_QP_REF_LQR | M4Q_QP_DU_BAND | M4Q_QP_EXACT_BOX (0x%x)", qp_flags);
+  if ((qp_flags & M4Q_QP_EXACT_BOX) && (qp_flags & M4Q_QP_REF_LQR))
+    return fail(M4Q_E_BADARG, "M4Q_QP_EXACT_BOX cannot be combined with M4Q_QP_REF_LQR");
+  return 0;
+}
+
+// one of the plants the one-shot entry points step on the device, and a process plant only on a state of d^4 entries.
+// not_a_plant: the caller's message for any other kind (may print the kind with %d)
+int check_device_plant_kind(int32_t kind, int32_t dim_x, const char* not_a_plant) {
+  if (kind != M4Q_PLANT_HAMILTONIAN && kind != M4Q_PLANT_GENERATOR && kind != M4Q_PLANT_PROCESS) return fail(M4Q_E_BADARG, not_a_plant, kind);
+  if (kind == M4Q_PLANT_PROCESS && dim_q(dim_x) == 0) return fail(M4Q_E_BADARG, "M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", dim_x);
+  return 0;
+}
+
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -147,6 +184,53 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
+// The device side of one call: inputs uploaded, outputs allocated now and downloaded by finish(), everything freed with the
+// object.  The first failure sticks: every later call is a no-op that returns null, so an entry point stages all its arrays,
+// asks error() once before it launches and returns what finish() returns.
+class Stage {
+  struct Out { void* host; const void* dev; size_t bytes; };
+  std::deque<DevBuf> bufs;
+  std::vector<Out> outs;
+  int rc = 0;
+  void* device(size_t bytes) {
+    if (rc) return nullptr;
+    bufs.emplace_back();
+    rc = bufs.back().alloc(bytes);
+    return bufs.back().p;
+  }
+
+ public:
+  int error() const { return rc; }
+  // count elements of T copied to the device
+  template <class T>
+  const T* in(const void* host, size_t count) {
+    void* d = device(count * sizeof(T));
+    if (!rc && host && count) {
+      hipError_t e = hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice);
+      if (e != hipSuccess) rc = fail(-(int)e, "hipMemcpy H2D: %s", hipGetErrorString(e));
+    }
+    return rc ? nullptr : static_cast<const T*>(d);
+  }
+  // count elements of T for the kernel to write; finish() copies them to host unless host is null (workspace)
+  template <class T>
+  T* out(void* host, size_t count) {
+    void* d = device(count * sizeof(T));
+    if (!rc && host && count) outs.push_back({host, d, count * sizeof(T)});
+    return static_cast<T*>(d);
+  }
+  // after the launch on the null stream: its return code, the wait for the device, the downloads in the order of the out() calls
+  int finish(int launch_rc, const char* what) {
+    if (rc) return rc;
+    if (launch_rc) return fail(launch_rc, "%s launch failed", what);
+    HIP_TRY(hipDeviceSynchronize());
+    for (const Out& o : outs) {
+      hipError_t e = hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost);
+      if (e != hipSuccess) return fail(-(int)e, "hipMemcpy D2H: %s", hipGetErrorString(e));
+    }
+    return 0;
+  }
+};
+
 // symmetrised real-ified cost block of iqp_line_search (mpc.py:92-93,103-104,112-116)
 void ls_block(const double* M, int k, std::vector<double>& out) {
   const int s = 2 * k;
@@ -162,191 +246,6 @@ void ls_block(const double* M, int k, std::vector<double>& out) {
   out.resize((size_t)s * s);
   for (int i = 0; i < s; ++i)
     for (int j = 0; j < s; ++j) out[(size_t)i * s + j] = 0.5 * (c[(size_t)i * s + j] + c[(size_t)j * s + i]);
-}
-
-
-// ---- Hermitian operator basis of the real path (same convention as csrc/m4q_mpc.h) ----------------
-// slot c = a*d + b:  a == b: rho_aa;  a < b: sqrt2 Re rho_ab;  a > b: sqrt2 Im rho_ab.
-// Column c of the unitary W (x = W r) has at most two entries; (W^H v)_c and (M W)_{.,c} cost O(1).
-struct HermBasis {
-  int d, n;
-  explicit HermBasis(int d_) : d(d_), n(d_ * d_) {}
-  // out = W^H v  (complex n-vector, stride 1)
-  void lift_vec(const std::complex<double>* v, std::complex<double>* out) const {
-    const double rs = 0.70710678118654752440;
-    const std::complex<double> I(0, 1);
-    for (int a = 0; a < d; ++a)
-      for (int b = 0; b < d; ++b) {
-        const int c = a * d + b, ct = b * d + a;
-        if (a == b) out[c] = v[c];
-        else if (a < b) out[c] = (v[c] + v[ct]) * rs;            // conj(1/sqrt2) (x_ab + x_ba)
-        else out[c] = (v[c] - v[ct]) * (-I * rs);                // conj(+i/sqrt2) x_ab + conj(-i/sqrt2) x_ba
-      }
-  }
-  // M (n x n, row-major, leading dimension ld) -> W^H M W, written to out (n x n, leading dimension ldo)
-  void lift_mat(const std::complex<double>* M, long ld, std::complex<double>* out, long ldo) const {
-    const double rs = 0.70710678118654752440;
-    const std::complex<double> I(0, 1);
-    std::vector<std::complex<double>> Y((size_t)n * n);
-    for (int i = 0; i < n; ++i)
-      for (int a = 0; a < d; ++a)
-        for (int b = 0; b < d; ++b) {
-          const int c = a * d + b, ct = b * d + a;
-          const std::complex<double> m1 = M[i * ld + c], m2 = M[i * ld + ct];
-          if (a == b) Y[(size_t)i * n + c] = m1;
-          else if (a < b) Y[(size_t)i * n + c] = (m1 + m2) * rs;
-          else Y[(size_t)i * n + c] = (m1 - m2) * (I * rs);      // W[(a,b),c] = +i/sqrt2, W[(b,a),c] = -i/sqrt2
-        }
-    std::vector<std::complex<double>> col(n), lifted(n);
-    for (int j = 0; j < n; ++j) {
-      for (int i = 0; i < n; ++i) col[i] = Y[(size_t)i * n + j];
-      lift_vec(col.data(), lifted.data());
-      for (int i = 0; i < n; ++i) out[i * ldo + j] = lifted[i];
-    }
-  }
-};
-
-// real part of a lifted array + the size of what was dropped, relative to the array's scale
-struct LiftStat {
-  double max_im = 0.0, max_abs = 0.0;
-  void see(std::complex<double> v) {
-    max_im = std::max(max_im, std::fabs(v.imag()));
-    max_abs = std::max(max_abs, std::abs(v));
-  }
-  bool real_enough() const { return max_im <= 1e-13 * std::max(1.0, max_abs); }
-};
-
-// ---- traceless coordinates (COORDS_TRACELESS; csrc/m4q_mpc.h): the diagonal slots (a, a) of the Hermitian basis rotated by the orthogonal
-// O[a][0] = 1/sqrt(d), O[a][l] = 1/sqrt(l(l+1)) (a < l), -l/sqrt(l(l+1)) (a == l), 0 (a > l); slot (0, 0) becomes the trace
-// coordinate and is dropped when the model leaves it alone.  Works on the REAL arrays the Hermitian lift produced.
-struct Traceless {
-  int d, n;
-  std::vector<double> O;                 // n x n: identity off the diagonal slots
-  explicit Traceless(int d_) : d(d_), n(d_ * d_), O((size_t)d_ * d_ * d_ * d_, 0.0) {
-    for (int c = 0; c < n; ++c) O[(size_t)c * n + c] = 1.0;
-    for (int a = 0; a < d; ++a)
-      for (int l = 0; l < d; ++l) {
-        double v;
-        if (l == 0) v = 1.0 / std::sqrt((double)d);
-        else v = a < l ? 1.0 / std::sqrt((double)l * (l + 1)) : (a == l ? -(double)l / std::sqrt((double)l * (l + 1)) : 0.0);
-        O[(size_t)(a * d + a) * n + (l * d + l)] = v;
-      }
-  }
-  // r (n) -> O^T r: out[0] = trace coordinate, out[1..n) = traceless coordinates
-  void vec(const double* r, double* out) const {
-    for (int c = 0; c < n; ++c) {
-      double acc = 0.0;
-      for (int k = 0; k < n; ++k) acc += O[(size_t)k * n + c] * r[k];
-      out[c] = acc;
-    }
-  }
-  // M (n x n, leading dimension ld) -> O^T M O (n x n, dense, into out)
-  void mat(const double* M, long ld, double* out) const {
-    std::vector<double> Y((size_t)n * n, 0.0);
-    for (int i = 0; i < n; ++i)
-      for (int k = 0; k < n; ++k) {
-        const double m = M[i * ld + k];
-        if (m != 0.0)
-          for (int c = 0; c < n; ++c) Y[(size_t)i * n + c] += m * O[(size_t)k * n + c];
-      }
-    for (int r = 0; r < n; ++r)
-      for (int c = 0; c < n; ++c) {
-        double acc = 0.0;
-        for (int i = 0; i < n; ++i) acc += O[(size_t)i * n + r] * Y[(size_t)i * n + c];
-        out[(size_t)r * n + c] = acc;
-      }
-  }
-};
-
-// how well the trace coordinate decouples: largest entry of row 0 / column 0 off what a decoupled block must hold
-struct DecoupleStat {
-  double worst = 0.0, scale = 0.0;
-  void see_block(const double* M, int n, bool identity_block) {     // M = O^T block O
-    for (int k = 0; k < n; ++k) {
-      const double want = (k == 0 && identity_block) ? 1.0 : 0.0;
-      worst = std::max(worst, std::fabs(M[k] - want));                       // row 0
-      worst = std::max(worst, std::fabs(M[(size_t)k * n] - want));           // column 0
-    }
-    for (int e = 0; e < n * n; ++e) scale = std::max(scale, std::fabs(M[e]));
-  }
-  bool ok() const { return worst <= 1e-12 * std::max(1.0, scale); }
-};
-
-// An input on the real coordinate systems, on the host.  [COORDS_HERM]: the real part of its lift to the Hermitian basis, ok when
-// the imaginary part dropped was negligible (LiftStat).  [COORDS_TRACELESS], when asked for and the Hermitian lift is ok: the same
-// on the traceless coordinates, ok when the trace coordinate decouples (DecoupleStat); tau: the range of that coordinate (vectors).
-struct Lift {
-  std::vector<double> v[m4q::COORDS_TRACELESS + 1];
-  bool ok[m4q::COORDS_TRACELESS + 1] = {};
-  double tau[2] = {0, 0};
-};
-
-// count rows of nblk n x n complex blocks side by side (row-major: block p of a row occupies columns [p*n, (p+1)*n)).
-// block0_identity: block 0 must carry the trace coordinate through unchanged (models [A | N_1 ..]); every other block must not
-// touch it.
-Lift lift_blocks(int d, const std::complex<double>* src, size_t count, int nblk, bool block0_identity, bool traceless) {
-  const HermBasis hb(d);
-  const int n = hb.n, ns = n - 1;
-  const long ld = (long)n * nblk, lds = (long)ns * nblk;
-  Lift L;
-  std::vector<double>& out = L.v[m4q::COORDS_HERM];
-  out.resize(count * n * ld);
-  LiftStat st;
-  std::vector<std::complex<double>> tmp((size_t)n * n);
-  for (size_t it = 0; it < count; ++it)
-    for (int p = 0; p < nblk; ++p) {
-      hb.lift_mat(src + it * n * ld + (long)p * n, ld, tmp.data(), n);
-      for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) {
-          st.see(tmp[(size_t)i * n + j]);
-          out[it * n * ld + i * ld + (long)p * n + j] = tmp[(size_t)i * n + j].real();
-        }
-    }
-  L.ok[m4q::COORDS_HERM] = st.real_enough();
-  if (!traceless || !L.ok[m4q::COORDS_HERM]) return L;
-  const Traceless tl(d);
-  std::vector<double>& tout = L.v[m4q::COORDS_TRACELESS];
-  tout.resize(count * ns * lds);
-  std::vector<double> rot((size_t)n * n);
-  DecoupleStat dc;
-  for (size_t it = 0; it < count; ++it)
-    for (int p = 0; p < nblk; ++p) {
-      tl.mat(out.data() + it * n * ld + (long)p * n, ld, rot.data());
-      dc.see_block(rot.data(), n, block0_identity && p == 0);
-      for (int i = 0; i < ns; ++i)
-        for (int j = 0; j < ns; ++j) tout[it * ns * lds + i * lds + (long)p * ns + j] = rot[(size_t)(1 + i) * n + 1 + j];
-    }
-  L.ok[m4q::COORDS_TRACELESS] = dc.ok();
-  return L;
-}
-
-// count complex n-vectors
-Lift lift_vectors(int d, const std::complex<double>* src, size_t count, bool traceless) {
-  const HermBasis hb(d);
-  const int n = hb.n, ns = n - 1;
-  Lift L;
-  std::vector<double>& out = L.v[m4q::COORDS_HERM];
-  out.resize(count * n);
-  LiftStat st;
-  std::vector<std::complex<double>> tmp(n);
-  for (size_t it = 0; it < count; ++it) {
-    hb.lift_vec(src + it * n, tmp.data());
-    for (int i = 0; i < n; ++i) { st.see(tmp[i]); out[it * n + i] = tmp[i].real(); }
-  }
-  L.ok[m4q::COORDS_HERM] = st.real_enough();
-  if (!traceless || !L.ok[m4q::COORDS_HERM]) return L;
-  const Traceless tl(d);
-  std::vector<double>& tout = L.v[m4q::COORDS_TRACELESS];
-  tout.resize(count * ns);
-  std::vector<double> rot(n);
-  for (size_t it = 0; it < count; ++it) {
-    tl.vec(out.data() + it * n, rot.data());
-    for (int i = 0; i < ns; ++i) tout[it * ns + i] = rot[1 + i];
-    L.tau[0] = it ? std::min(L.tau[0], rot[0]) : rot[0];
-    L.tau[1] = it ? std::max(L.tau[1], rot[0]) : rot[0];
-  }
-  L.ok[m4q::COORDS_TRACELESS] = true;
-  return L;
 }
 
 }  // namespace
@@ -458,10 +357,7 @@ int m4q_session_create(const m4q_problem* p, int32_t B, int32_t device, m4q_sess
   if (p->horizon < 1 || p->n_steps < 1 || p->target_cols < p->horizon + 1 + (p->n_steps > 1 ? p->n_steps - 2 : 0))
     return fail(M4Q_E_BADARG, "horizon/n_steps/target_cols inconsistent (need target_cols >= n_steps + horizon - 1)");
   if (!(p->sat > 0)) return fail(M4Q_E_BADARG, "sat must be positive (the reference crashes on sat=None, mpc.py Q5)");
-  if (p->qp_flags & ~(M4Q_QP_REF_LQR | M4Q_QP_DU_BAND | M4Q_QP_EXACT_BOX))
-    return fail(M4Q_E_BADARG, "qp_flags has bits outside M4Q_QP_REF_LQR | M4Q_QP_DU_BAND | M4Q_QP_EXACT_BOX (0x%x)", p->qp_flags);
-  if ((p->qp_flags & M4Q_QP_EXACT_BOX) && (p->qp_flags & M4Q_QP_REF_LQR))
-    return fail(M4Q_E_BADARG, "M4Q_QP_EXACT_BOX cannot be combined with M4Q_QP_REF_LQR");
+  if (int rc = check_qp_flags(p->qp_flags)) return rc;
   if (p->plant_kind == M4Q_PLANT_PROCESS && dim_q(p->dim_x) == 0)
     return fail(M4Q_E_BADARG, "M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power (the process vector of a d x d unitary has d^4 entries)",
                 p->dim_x);
@@ -474,9 +370,7 @@ int m4q_session_create(const m4q_problem* p, int32_t B, int32_t device, m4q_sess
     if (p->plant_per_instance && (double)B * p->dim_u * kk * kk * 16.0 >= lim)
       return fail(M4Q_E_BADARG, "per-instance plant operators must stay below 4 GiB in total");
   }
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev == 0) return fail(M4Q_E_NODEVICE, "no HIP device: %s", hipGetErrorString(e));
+  if (int rc = need_device()) return rc;
   if (device >= 0) HIP_TRY(hipSetDevice(device));
   m4q_session* s = new m4q_session();
   s->prob = *p;
@@ -502,16 +396,17 @@ int m4q_session_create(const m4q_problem* p, int32_t B, int32_t device, m4q_sess
   const size_t n = p->dim_x, m = p->dim_u, P = sh->np, T = p->horizon, ns = p->n_steps, cols = p->target_cols;
   const size_t k = plant_dim(p->plant_kind, p->dim_x);
   const size_t C = 16;
+  const bool has_plant = p->plant_kind != M4Q_PLANT_NONE;
   size_t* fb = s->fbytes;
-  fb[M4Q_F_MODELS] = (p->model_per_instance ? B : 1) * n * n * (1 + P) * C;
+  fb[M4Q_F_MODELS] = Extent(B, p->model_per_instance, n * n * (1 + P)).count * C;
   fb[M4Q_F_X0] = (size_t)B * n * C;
-  fb[M4Q_F_X_TARG] = (p->target_per_instance ? B : 1) * cols * n * C;
-  fb[M4Q_F_U_TARG] = (p->target_per_instance ? B : 1) * cols * m * 8;
+  fb[M4Q_F_X_TARG] = Extent(B, p->target_per_instance, cols * n).count * C;
+  fb[M4Q_F_U_TARG] = Extent(B, p->target_per_instance, cols * m).count * 8;
   fb[M4Q_F_Q] = n * n * C;
   fb[M4Q_F_QF] = n * n * C;
   fb[M4Q_F_R] = m * m * C;
-  fb[M4Q_F_OP0] = p->plant_kind == M4Q_PLANT_NONE ? 0 : (p->plant_per_instance ? B : 1) * k * k * C;
-  fb[M4Q_F_OPS] = p->plant_kind == M4Q_PLANT_NONE ? 0 : (p->plant_per_instance ? B : 1) * m * k * k * C;
+  fb[M4Q_F_OP0] = has_plant ? Extent(B, p->plant_per_instance, k * k).count * C : 0;
+  fb[M4Q_F_OPS] = has_plant ? Extent(B, p->plant_per_instance, m * k * k).count * C : 0;
   fb[M4Q_F_XS] = (size_t)B * (ns + 1) * n * C;
   fb[M4Q_F_US] = (size_t)B * ns * m * 8;
   fb[M4Q_F_CODES] = (size_t)B * 4;
@@ -763,22 +658,22 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   a.gens = (const double*)s->sg_gens.p; a.scales = (const double*)s->sg_scales.p;
   a.exit_mode = s->exit_mode;
   a.exit_W = (const cplx*)s->exit_W.p;
-  a.exit_target = (const cplx*)s->exit_target.p; a.exit_tstride = s->exit_target_per ? (long)n : 0;
-  a.exit_thr = (const double*)s->exit_thr.p; a.exit_thr_stride = s->exit_thr_per ? 1 : 0;
+  a.exit_target = (const cplx*)s->exit_target.p; a.exit_tstride = Extent(s->B, s->exit_target_per, n).stride;
+  a.exit_thr = (const double*)s->exit_thr.p; a.exit_thr_stride = Extent(s->B, s->exit_thr_per, 1).stride;
   a.noise_mode = s->noise_mode;
-  a.noise_sigma = (const double*)s->noise_sigma.p; a.noise_sigma_stride = s->noise_sigma_per ? 1 : 0;
+  a.noise_sigma = (const double*)s->noise_sigma.p; a.noise_sigma_stride = Extent(s->B, s->noise_sigma_per, 1).stride;
   a.noise_seed = s->noise_seed; a.noise_member_base = s->noise_member_base;
-  a.model_stride = p.model_per_instance ? (long)(ns * ns * (1 + P)) : 0;
+  a.model_stride = Extent(s->B, p.model_per_instance, ns * ns * (1 + P)).stride;
   a.x0c = (const cplx*)s->f[M4Q_F_X0].p;
   a.x0s = s->input(M4Q_F_X0, coords);
   a.x_targ = s->input(M4Q_F_X_TARG, coords);
-  a.xt_stride = p.target_per_instance ? (long)(p.target_cols * ns) : 0;
-  a.u_targ = (const double*)s->f[M4Q_F_U_TARG].p; a.ut_stride = p.target_per_instance ? (long)(p.target_cols * m) : 0;
+  a.xt_stride = Extent(s->B, p.target_per_instance, p.target_cols * ns).stride;
+  a.u_targ = (const double*)s->f[M4Q_F_U_TARG].p; a.ut_stride = Extent(s->B, p.target_per_instance, p.target_cols * m).stride;
   a.Q = s->input(M4Q_F_Q, coords); a.Qf = s->input(M4Q_F_QF, coords); a.R = s->input(M4Q_F_R, coords);
   a.Cq = (const double*)s->Cq.p; a.Cqf = (const double*)s->Cqf.p; a.Cr = (const double*)s->Cr.p;
   a.Wls = s->ls_diag ? (const double*)s->Wls.p : nullptr;
-  a.op0 = (const cplx*)s->f[M4Q_F_OP0].p; a.op0_stride = p.plant_per_instance ? (long)(k * k) : 0;
-  a.ops = (const cplx*)s->f[M4Q_F_OPS].p; a.ops_stride = p.plant_per_instance ? (long)(m * k * k) : 0;
+  a.op0 = (const cplx*)s->f[M4Q_F_OP0].p; a.op0_stride = Extent(s->B, p.plant_per_instance, k * k).stride;
+  a.ops = (const cplx*)s->f[M4Q_F_OPS].p; a.ops_stride = Extent(s->B, p.plant_per_instance, m * k * k).stride;
   if (p.plant_kind == M4Q_PLANT_NONE) { a.op0 = (const cplx*)s->f[M4Q_F_Q].p; a.ops = a.op0; a.op0_stride = a.ops_stride = 0; }
   a.xs = (cplx*)s->f[M4Q_F_XS].p; a.us = (double*)s->f[M4Q_F_US].p;
   a.codes = (int*)s->f[M4Q_F_CODES].p; a.steps_done = (int*)s->f[M4Q_F_STEPS_DONE].p; a.qp_solves = (int*)s->f[M4Q_F_QP_SOLVES].p;
@@ -850,7 +745,7 @@ int m4q_session_set_exit(m4q_session* s, int32_t mode, const double* W, const do
   s->exit_W.release(); s->exit_target.release(); s->exit_thr.release();
   if (mode == 0) return 0;
   const size_t n = s->prob.dim_x, B = s->B, C = 16;
-  const size_t tb = (target_per_instance ? B : 1) * n * C, hb = (thr_per_instance ? B : 1) * 8;
+  const size_t tb = Extent(B, target_per_instance, n).count * C, hb = Extent(B, thr_per_instance, 1).count * 8;
   int rc;
   if ((rc = s->exit_W.alloc(n * n * C)) || (rc = s->exit_target.alloc(tb)) || (rc = s->exit_thr.alloc(hb))) return rc;
   HIP_TRY(hipMemcpy(s->exit_W.p, W, n * n * C, hipMemcpyHostToDevice));
@@ -875,7 +770,7 @@ static int check_noise_args(const char* who, int32_t mode, const double* sigma, 
 int m4q_session_set_noise(m4q_session* s, int32_t mode, const double* sigma, int32_t sigma_per_instance, uint64_t seed,
                           uint64_t member_base) {
   if (!s) return fail(M4Q_E_BADARG, "m4q_session_set_noise: null session");
-  const size_t count = sigma_per_instance ? (size_t)s->B : 1;
+  const size_t count = Extent(s->B, sigma_per_instance, 1).count;
   if (int rc = check_noise_args("m4q_session_set_noise", mode, sigma, count)) return rc;
   if (mode != 0 && s->prob.plant_kind == M4Q_PLANT_NONE)
     return fail(M4Q_E_BADARG, "m4q_session_set_noise: M4Q_PLANT_NONE sessions take their states from the host, which adds its own noise");
@@ -970,65 +865,23 @@ int m4q_session_info(const m4q_session* s, int64_t* hbm_bytes, int32_t* grid, in
 // ------------------------------------------------------------------------------------------
 // one-shot host entry points
 // ------------------------------------------------------------------------------------------
-namespace {
-struct Tmp {
-  std::vector<DevBuf*> bufs;
-  ~Tmp() { for (DevBuf* b : bufs) delete b; }
-  int up(const void* host, size_t bytes, void** out) {
-    DevBuf* b = new DevBuf();
-    bufs.push_back(b);
-    int rc = b->alloc(bytes);
-    if (rc) return rc;
-    if (host && bytes) {
-      hipError_t e = hipMemcpy(b->p, host, bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) return fail(-(int)e, "hipMemcpy H2D: %s", hipGetErrorString(e));
-    }
-    *out = b->p;
-    return 0;
-  }
-};
-int down(void* host, const void* dev, size_t bytes) {
-  if (!host || !bytes) return 0;
-  hipError_t e = hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(-(int)e, "hipMemcpy D2H: %s", hipGetErrorString(e));
-  return 0;
-}
-int need_device() {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n == 0) return fail(M4Q_E_NODEVICE, "no HIP device: %s", hipGetErrorString(e));
-  return 0;
-}
-}  // namespace
-
 int m4q_linearize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t T, const double* models,
                         int32_t model_per_instance, const double* X, const double* U, double* A_ls, double* B_ls,
                         double* Delta_ls) {
   const m4q::ShapeOps* sh = find_shape(dim_x, dim_u, order);
   if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d order=%d", dim_x, dim_u, order);
   if (B <= 0 || T <= 0 || !models || !X || !U || !A_ls || !B_ls || !Delta_ls) return fail(M4Q_E_BADARG, "m4q_linearize_batch: bad argument");
-  int rc = need_device();
-  if (rc) return rc;
-  const size_t n = dim_x, m = dim_u, P = sh->np, C = 16;
-  Tmp t;
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, P = sh->np, BT = (size_t)B * T;
+  const Extent mdl(B, model_per_instance, n * n * (1 + P));
+  Stage st;
   m4q::LinArgs a{};
   a.B = B; a.T = T;
-  a.model_stride = model_per_instance ? (long)(n * n * (1 + P)) : 0;
-  void *d_models, *d_X, *d_U, *d_A, *d_B, *d_D;
-  if ((rc = t.up(models, (model_per_instance ? B : 1) * n * n * (1 + P) * C, &d_models))) return rc;
-  if ((rc = t.up(X, (size_t)B * T * n * C, &d_X))) return rc;
-  if ((rc = t.up(U, (size_t)B * T * m * 8, &d_U))) return rc;
-  if ((rc = t.up(nullptr, (size_t)B * T * n * n * C, &d_A))) return rc;
-  if ((rc = t.up(nullptr, (size_t)B * T * n * m * C, &d_B))) return rc;
-  if ((rc = t.up(nullptr, (size_t)B * T * n * C, &d_D))) return rc;
-  a.models = (const cplx*)d_models; a.X = (const cplx*)d_X; a.U = (const double*)d_U;
-  a.A_ls = (cplx*)d_A; a.B_ls = (cplx*)d_B; a.D_ls = (cplx*)d_D;
-  rc = sh->launch_linearize(a, nullptr);
-  if (rc) return fail(rc, "linearize launch failed");
-  HIP_TRY(hipDeviceSynchronize());
-  if ((rc = down(A_ls, d_A, (size_t)B * T * n * n * C))) return rc;
-  if ((rc = down(B_ls, d_B, (size_t)B * T * n * m * C))) return rc;
-  return down(Delta_ls, d_D, (size_t)B * T * n * C);
+  a.models = st.in<cplx>(models, mdl.count); a.model_stride = mdl.stride;
+  a.X = st.in<cplx>(X, BT * n); a.U = st.in<double>(U, BT * m);
+  a.A_ls = st.out<cplx>(A_ls, BT * n * n); a.B_ls = st.out<cplx>(B_ls, BT * n * m); a.D_ls = st.out<cplx>(Delta_ls, BT * n);
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_linearize(a, nullptr), "linearize");
 }
 
 int m4q_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t T, int32_t qp_flags, double sat, double du,
@@ -1041,90 +894,66 @@ int m4q_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t T, i
   if (B <= 0 || T <= 0 || !x_init || !X_bm || !U_bm || !Q_ls || !R_ls || !A_ls || !B_ls || !X_opt || !U_opt || !cost)
     return fail(M4Q_E_BADARG, "m4q_quad_program_batch: bad argument");
   if (!(sat > 0)) return fail(M4Q_E_BADARG, "sat must be positive");
-  if (qp_flags & ~(M4Q_QP_REF_LQR | M4Q_QP_DU_BAND | M4Q_QP_EXACT_BOX))
-    return fail(M4Q_E_BADARG, "qp_flags has bits outside M4Q_QP_REF_LQR | M4Q_QP_DU_BAND | M4Q_QP_EXACT_BOX (0x%x)", qp_flags);
-  if ((qp_flags & M4Q_QP_EXACT_BOX) && (qp_flags & M4Q_QP_REF_LQR))
-    return fail(M4Q_E_BADARG, "M4Q_QP_EXACT_BOX cannot be combined with M4Q_QP_REF_LQR");
-  int rc = need_device();
-  if (rc) return rc;
-  const size_t n = dim_x, m = dim_u, C = 16;
-  Tmp t;
+  if (int rc = check_qp_flags(qp_flags)) return rc;
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, BT = (size_t)B * T, BT1 = (size_t)B * (T + 1);
+  const Extent xbm(B, bm_per_instance, (size_t)(T + 1) * n), ubm(B, bm_per_instance, (size_t)T * m);
+  Stage st;
   m4q::QpArgs a{};
   a.B = B; a.T = T; a.flags = qp_flags; a.sat = sat; a.du = du;
-  void *d_x, *d_xb, *d_ub, *d_q, *d_r, *d_a, *d_b, *d_d = nullptr, *d_up = nullptr, *d_xo, *d_uo, *d_c, *d_g, *d_it = nullptr;
-  if ((rc = t.up(x_init, (size_t)B * n * C, &d_x))) return rc;
-  if ((rc = t.up(X_bm, (bm_per_instance ? B : 1) * (size_t)(T + 1) * n * C, &d_xb))) return rc;
-  if ((rc = t.up(U_bm, (bm_per_instance ? B : 1) * (size_t)T * m * 8, &d_ub))) return rc;
-  if ((rc = t.up(Q_ls, (size_t)(T + 1) * n * n * C, &d_q))) return rc;
-  if ((rc = t.up(R_ls, (size_t)T * m * m * C, &d_r))) return rc;
-  if ((rc = t.up(A_ls, (size_t)B * T * n * n * C, &d_a))) return rc;
-  if ((rc = t.up(B_ls, (size_t)B * T * n * m * C, &d_b))) return rc;
-  if (Delta_ls && (rc = t.up(Delta_ls, (size_t)B * T * n * C, &d_d))) return rc;
-  if (u_prev && (rc = t.up(u_prev, (size_t)B * m * 8, &d_up))) return rc;
-  if ((rc = t.up(nullptr, (size_t)B * (T + 1) * n * C, &d_xo))) return rc;
-  if ((rc = t.up(nullptr, (size_t)B * T * m * 8, &d_uo))) return rc;
-  if ((rc = t.up(nullptr, (size_t)B * 8, &d_c))) return rc;
-  if ((rc = t.up(nullptr, (size_t)B * T * (n + 1) * m * C, &d_g))) return rc;
-  a.x_init = (const cplx*)d_x;
-  a.X_bm = (const cplx*)d_xb; a.xbm_stride = bm_per_instance ? (long)((T + 1) * n) : 0;
-  a.U_bm = (const double*)d_ub; a.ubm_stride = bm_per_instance ? (long)(T * m) : 0;
-  a.Q_ls = (const cplx*)d_q; a.R_ls = (const cplx*)d_r;
-  a.A_ls = (const cplx*)d_a; a.B_ls = (const cplx*)d_b; a.D_ls = (const cplx*)d_d; a.u_prev = (const double*)d_up;
-  a.X_opt = (cplx*)d_xo; a.U_opt = (double*)d_uo; a.cost = (double*)d_c; a.gains = (cplx*)d_g;
+  a.x_init = st.in<cplx>(x_init, (size_t)B * n);
+  a.X_bm = st.in<cplx>(X_bm, xbm.count); a.xbm_stride = xbm.stride;
+  a.U_bm = st.in<double>(U_bm, ubm.count); a.ubm_stride = ubm.stride;
+  a.Q_ls = st.in<cplx>(Q_ls, (size_t)(T + 1) * n * n); a.R_ls = st.in<cplx>(R_ls, (size_t)T * m * m);
+  a.A_ls = st.in<cplx>(A_ls, BT * n * n); a.B_ls = st.in<cplx>(B_ls, BT * n * m);
+  if (Delta_ls) a.D_ls = st.in<cplx>(Delta_ls, BT * n);
+  if (u_prev) a.u_prev = st.in<double>(u_prev, (size_t)B * m);
+  std::vector<int> sweeps;                                  // diagnostic (M4Q_QP_TRACE): pinned sweeps per instance
   if (qp_flags & M4Q_QP_EXACT_BOX) {
-    void *d_xa, *d_ua, *d_st;
-    if ((double)B * (T + 1) * n * C * 2 >= 4294967296.0)
+    if (st.error()) return st.error();
+    if ((double)BT1 * n * 16 * 2 >= 4294967296.0)
       return fail(M4Q_E_BADARG, "M4Q_QP_EXACT_BOX: batch too large for one call (trajectory workspace must stay below 4 GiB)");
-    if ((rc = t.up(nullptr, 2 * (size_t)B * (T + 1) * n * C, &d_xa))) return rc;
-    if ((rc = t.up(nullptr, 2 * (size_t)B * T * m * 8, &d_ua))) return rc;
-    if ((rc = t.up(nullptr, (size_t)B * T * m * 8, &d_st))) return rc;
-    a.X_alt = (cplx*)d_xa; a.U_alt = (double*)d_ua; a.pin_stat = (double*)d_st;
     if (getenv("M4Q_QP_TRACE")) {
-      if ((rc = t.up(nullptr, (size_t)B * 4, &d_it))) return rc;
-      a.sweep_counts = (int*)d_it;
+      sweeps.resize(B);
+      a.sweep_counts = st.out<int>(sweeps.data(), B);
     }
+    a.X_alt = st.out<cplx>(nullptr, 2 * BT1 * n); a.U_alt = st.out<double>(nullptr, 2 * BT * m);
+    a.pin_stat = st.out<double>(nullptr, BT * m);
   }
-  rc = sh->launch_qp(a, nullptr);
-  if (rc) return fail(rc, "qp launch failed");
-  HIP_TRY(hipDeviceSynchronize());
-  if (d_it) {                                             // diagnostic: Newton iterations per instance
-    std::vector<int> it(B);
-    if ((rc = down(it.data(), d_it, (size_t)B * 4))) return rc;
+  a.X_opt = st.out<cplx>(X_opt, BT1 * n); a.U_opt = st.out<double>(U_opt, BT * m); a.cost = st.out<double>(cost, B);
+  a.gains = st.out<cplx>(gains, BT * (n + 1) * m);          // (workspace when the caller wants no gains)
+  if (st.error()) return st.error();
+  const int rc = st.finish(sh->launch_qp(a, nullptr), "qp");
+  if (!rc && !sweeps.empty()) {
     long sum = 0;
     int mx = 0;
-    for (int v : it) { sum += v; mx = v > mx ? v : mx; }
+    for (int v : sweeps) { sum += v; mx = v > mx ? v : mx; }
     fprintf(stderr, "m4q: exact box QP: %d instances, pinned sweeps mean %.2f max %d\n", B, (double)sum / B, mx);
   }
-  if ((rc = down(X_opt, d_xo, (size_t)B * (T + 1) * n * C))) return rc;
-  if ((rc = down(U_opt, d_uo, (size_t)B * T * m * 8))) return rc;
-  if ((rc = down(cost, d_c, (size_t)B * 8))) return rc;
-  return down(gains, d_g, (size_t)B * T * (n + 1) * m * C);
+  return rc;
 }
 
 int m4q_noise_sample_batch(int32_t B, int32_t n, int32_t mode, const double* sigma, int32_t sigma_per_instance, uint64_t seed,
                            uint64_t member_base, int32_t state_index, double* out) {
   if (B <= 0 || n <= 0 || !out || mode == 0 || state_index < 1)
     return fail(M4Q_E_BADARG, "m4q_noise_sample_batch: bad argument (B, n >= 1, a noise mode, state_index >= 1, out)");
-  if (int rc = check_noise_args("m4q_noise_sample_batch", mode, sigma, sigma_per_instance ? (size_t)B : 1)) return rc;
+  const Extent sg(B, sigma_per_instance, 1);
+  if (int rc = check_noise_args("m4q_noise_sample_batch", mode, sigma, sg.count)) return rc;
   const m4q::ShapeOps* sh = nullptr;
   for (int nu = 1; nu <= 3 && !sh; ++nu) sh = find_shape_any_order(n, nu, true);
   if (!sh) return fail(M4Q_E_UNSUPPORTED, "m4q_noise_sample_batch: no compiled kernel with dim_x=%d", n);
   if (mode == M4Q_NOISE_HERMITIAN && sh->d * sh->d != n)
     return fail(M4Q_E_BADARG, "m4q_noise_sample_batch: M4Q_NOISE_HERMITIAN needs n = d d, got n = %d", n);
-  int rc = need_device();
-  if (rc) return rc;
-  Tmp t;
-  void *d_s, *d_o;
-  const size_t sb = (sigma_per_instance ? (size_t)B : 1) * 8, ob = (size_t)B * n * 16;
-  if ((rc = t.up(sigma, sb, &d_s)) || (rc = t.up(nullptr, ob, &d_o))) return rc;
+  if (int rc = need_device()) return rc;
+  Stage st;
   m4q::NoiseArgs a{};
   a.B = B; a.mode = mode; a.state_index = (unsigned)state_index; a.seed = seed; a.member_base = member_base;
-  a.sigma = (const double*)d_s; a.sigma_stride = sigma_per_instance ? 1 : 0;
-  a.out = (cplx*)d_o;
-  rc = sh->launch_noise(a, nullptr);
-  if (rc) return fail(rc, "noise kernel launch failed: %s", hipGetErrorString((hipError_t)(-rc)));
-  HIP_TRY(hipDeviceSynchronize());
-  return down(out, d_o, ob);
+  a.sigma = st.in<double>(sigma, sg.count); a.sigma_stride = sg.stride;
+  a.out = st.out<cplx>(out, (size_t)B * n);
+  if (st.error()) return st.error();
+  const int rc = sh->launch_noise(a, nullptr);
+  if (rc) return fail(rc, "noise kernel launch failed: %s", hipGetErrorString((hipError_t)(-rc)));    // (this one names the reason)
+  return st.finish(0, "noise kernel");
 }
 
 int m4q_discretize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, double dt, const double* generators,
@@ -1135,22 +964,17 @@ int m4q_discretize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order,
   if (order > 2)
     return fail(M4Q_E_UNSUPPORTED, "m4q_discretize_batch: the device discretisation covers orders 1 and 2 (order %d: use the host "
                 "discretize_homogeneous and upload the models)", order);
-  int rc = need_device();
-  if (rc) return rc;
-  const size_t n = dim_x, m = dim_u, P = sh->np, C = 16;
-  Tmp t;
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, P = sh->np;
+  const Extent gen(B, gen_per_instance, (1 + m) * n * n);
+  Stage st;
   m4q::DiscArgs a{};
   a.B = B; a.dt = dt;
-  void *d_g, *d_s = nullptr, *d_m;
-  if ((rc = t.up(generators, (gen_per_instance ? B : 1) * (1 + m) * n * n * C, &d_g))) return rc;
-  if (scales && (rc = t.up(scales, (size_t)B * (1 + m) * 8, &d_s))) return rc;
-  if ((rc = t.up(nullptr, (size_t)B * n * n * (1 + P) * C, &d_m))) return rc;
-  a.gens = d_g; a.gen_stride = gen_per_instance ? (long)((1 + m) * n * n) : 0;
-  a.scales = (const double*)d_s; a.models = d_m;
-  rc = sh->launch_discretize(a, m4q::COORDS_COMPLEX, nullptr);
-  if (rc) return fail(rc, "discretize launch failed");
-  HIP_TRY(hipDeviceSynchronize());
-  return down(models, d_m, (size_t)B * n * n * (1 + P) * C);
+  a.gens = st.in<cplx>(generators, gen.count); a.gen_stride = gen.stride;
+  if (scales) a.scales = st.in<double>(scales, (size_t)B * (1 + m));
+  a.models = st.out<cplx>(models, (size_t)B * n * n * (1 + P));
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_discretize(a, m4q::COORDS_COMPLEX, nullptr), "discretize");
 }
 
 int m4q_session_build_models(m4q_session* s, double dt, const double* generators, int32_t gen_per_instance,
@@ -1160,21 +984,20 @@ int m4q_session_build_models(m4q_session* s, double dt, const double* generators
   if (p.order > 2)
     return fail(M4Q_E_UNSUPPORTED, "m4q_session_build_models: the device discretisation covers orders 1 and 2 (order %d: build the "
                 "models with the host discretize_homogeneous and upload them)", p.order);
-  const size_t n = p.dim_x, m = p.dim_u, P = s->shape->np, C = 16;
+  const size_t n = p.dim_x, m = p.dim_u, P = s->shape->np;
   const size_t nset = gen_per_instance ? (size_t)s->B : 1;
   const size_t nmodels = p.model_per_instance ? (size_t)s->B : 1;
   if ((gen_per_instance || scales) && !p.model_per_instance)
     return fail(M4Q_E_BADARG, "per-instance generators or scales need model_per_instance = 1");
-  Tmp t;
+  const Extent gen(s->B, gen_per_instance, (1 + m) * n * n);
+  Stage st;                                  // (inputs only: the launches go to the session's stream, the models stay on the device)
   m4q::DiscArgs a{};
   a.B = (int)nmodels; a.dt = dt;
-  void *d_g, *d_s = nullptr;
-  int rc;
-  if ((rc = t.up(generators, nset * (1 + m) * n * n * C, &d_g))) return rc;
-  if (scales && (rc = t.up(scales, (size_t)s->B * (1 + m) * 8, &d_s))) return rc;
-  a.gens = d_g; a.gen_stride = gen_per_instance ? (long)((1 + m) * n * n) : 0;
-  a.scales = (const double*)d_s; a.models = s->f[M4Q_F_MODELS].p;
-  rc = s->shape->launch_discretize(a, m4q::COORDS_COMPLEX, s->stream);
+  a.gens = st.in<cplx>(generators, gen.count); a.gen_stride = gen.stride;
+  if (scales) a.scales = st.in<double>(scales, (size_t)s->B * (1 + m));
+  if (st.error()) return st.error();
+  a.models = s->f[M4Q_F_MODELS].p;
+  int rc = s->shape->launch_discretize(a, m4q::COORDS_COMPLEX, s->stream);
   if (rc) return fail(rc, "discretize launch failed");
   s->sg_ok = false;
   s->copies[m4q::COORDS_HERM][M4Q_F_MODELS].ok = s->copies[m4q::COORDS_TRACELESS][M4Q_F_MODELS].ok = false;
@@ -1188,11 +1011,12 @@ int m4q_session_build_models(m4q_session* s, double dt, const double* generators
       if (!L.ok[c]) continue;
       const size_t k = c == m4q::COORDS_HERM ? n : n - 1;
       m4q_session::Copy& dst = s->copies[c][M4Q_F_MODELS];
-      void* d_gr;
-      if ((rc = t.up(L.v[c].data(), L.v[c].size() * 8, &d_gr))) return rc;
-      if ((rc = dst.buf.alloc(nmodels * k * k * (1 + P) * 8))) return rc;
       m4q::DiscArgs r = a;
-      r.gens = d_gr; r.gen_stride = gen_per_instance ? (long)((1 + m) * k * k) : 0; r.models = dst.buf.p;
+      r.gens = st.in<double>(L.v[c].data(), L.v[c].size());
+      r.gen_stride = Extent(s->B, gen_per_instance, (1 + m) * k * k).stride;
+      if (st.error()) return st.error();
+      if ((rc = dst.buf.alloc(nmodels * k * k * (1 + P) * 8))) return rc;
+      r.models = dst.buf.p;
       rc = s->shape->launch_discretize(r, c, s->stream);
       if (rc) return fail(rc, "discretize launch failed");
       dst.ok = true;
@@ -1220,32 +1044,20 @@ int m4q_plant_step_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_
                          double* x_next) {
   const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
   if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d", dim_x, dim_u);
-  if (B <= 0 || !x || !u || !op0 || !ops || !x_next ||
-      (plant_kind != M4Q_PLANT_HAMILTONIAN && plant_kind != M4Q_PLANT_GENERATOR && plant_kind != M4Q_PLANT_PROCESS))
-    return fail(M4Q_E_BADARG, "m4q_plant_step_batch: bad argument");
-  if (plant_kind == M4Q_PLANT_PROCESS && dim_q(dim_x) == 0)
-    return fail(M4Q_E_BADARG, "M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", dim_x);
-  int rc = need_device();
-  if (rc) return rc;
-  const size_t n = dim_x, m = dim_u, C = 16;
-  const size_t k = plant_dim(plant_kind, dim_x);
-  Tmp t;
+  if (B <= 0 || !x || !u || !op0 || !ops || !x_next) return fail(M4Q_E_BADARG, "m4q_plant_step_batch: bad argument");
+  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_step_batch: bad argument")) return rc;
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x);
+  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  Stage st;
   m4q::PlantArgs a{};
   a.B = B; a.kind = plant_kind; a.dt = dt;
-  void *d_x, *d_u, *d_0, *d_k, *d_o;
-  if ((rc = t.up(x, (size_t)B * n * C, &d_x))) return rc;
-  if ((rc = t.up(u, (size_t)B * m * 8, &d_u))) return rc;
-  if ((rc = t.up(op0, (plant_per_instance ? B : 1) * k * k * C, &d_0))) return rc;
-  if ((rc = t.up(ops, (plant_per_instance ? B : 1) * m * k * k * C, &d_k))) return rc;
-  if ((rc = t.up(nullptr, (size_t)B * n * C, &d_o))) return rc;
-  a.x = (const cplx*)d_x; a.u = (const double*)d_u;
-  a.op0 = (const cplx*)d_0; a.op0_stride = plant_per_instance ? (long)(k * k) : 0;
-  a.ops = (const cplx*)d_k; a.ops_stride = plant_per_instance ? (long)(m * k * k) : 0;
-  a.x_next = (cplx*)d_o;
-  rc = sh->launch_plant(a, nullptr);
-  if (rc) return fail(rc, "plant launch failed");
-  HIP_TRY(hipDeviceSynchronize());
-  return down(x_next, d_o, (size_t)B * n * C);
+  a.x = st.in<cplx>(x, (size_t)B * n); a.u = st.in<double>(u, (size_t)B * m);
+  a.op0 = st.in<cplx>(op0, e0.count); a.op0_stride = e0.stride;
+  a.ops = st.in<cplx>(ops, ek.count); a.ops_stride = ek.stride;
+  a.x_next = st.out<cplx>(x_next, (size_t)B * n);
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_plant(a, nullptr), "plant");
 }
 
 namespace {
@@ -1262,47 +1074,24 @@ int check_roll_args(const char* who, int32_t B, int32_t N, const double* x0, con
   return 0;
 }
 
-// uploads what the two rollouts share, launches, downloads what was asked for
-struct RollCall {
-  Tmp t;
+// stages what the two rollouts share
+m4q::RollArgs stage_roll(Stage& st, int32_t B, size_t n, size_t m, int32_t N, const double* x0, const double* u, int32_t u_per_instance,
+                         const double* u_scale, const double* W, const double* target, int32_t target_per_instance, int32_t xs_mode,
+                         double* xs, int32_t q_mode, double* q) {
+  const Extent eu(B, u_per_instance, (size_t)N * m), ef(B, target_per_instance, n);
   m4q::RollArgs a{};
-  void *d_xs = nullptr, *d_q = nullptr;
-  size_t xs_bytes = 0, q_bytes = 0;
-  int prepare(int32_t B, size_t n, size_t m, int32_t N, const double* x0, const double* u, int32_t u_per_instance, const double* u_scale,
-              const double* W, const double* target, int32_t target_per_instance, int32_t xs_mode, int32_t q_mode) {
-    const size_t C = 16;
-    int rc;
-    a.B = B; a.N = N; a.xs_mode = xs_mode; a.q_mode = q_mode;
-    void *d_x0, *d_u, *d_s, *d_W, *d_f;
-    if ((rc = t.up(x0, (size_t)B * n * C, &d_x0))) return rc;
-    if ((rc = t.up(u, (size_t)(u_per_instance ? B : 1) * N * m * 8, &d_u))) return rc;
-    a.x0 = (const cplx*)d_x0; a.u = (const double*)d_u; a.u_stride = u_per_instance ? (long)((size_t)N * m) : 0;
-    if (u_scale) {
-      if ((rc = t.up(u_scale, (size_t)B * m * 8, &d_s))) return rc;
-      a.u_scale = (const double*)d_s;
-    }
-    if (q_mode != 0) {
-      if ((rc = t.up(W, n * n * C, &d_W))) return rc;
-      if ((rc = t.up(target, (size_t)(target_per_instance ? B : 1) * n * C, &d_f))) return rc;
-      a.W = (const cplx*)d_W; a.target = (const cplx*)d_f; a.target_stride = target_per_instance ? (long)n : 0;
-      q_bytes = (size_t)B * (q_mode == 2 ? (size_t)N + 1 : 1) * 8;
-      if ((rc = t.up(nullptr, q_bytes, &d_q))) return rc;
-      a.q = (double*)d_q;
-    }
-    if (xs_mode != 0) {
-      xs_bytes = (size_t)B * (xs_mode == 2 ? (size_t)N + 1 : 1) * n * C;
-      if ((rc = t.up(nullptr, xs_bytes, &d_xs))) return rc;
-      a.xs = (cplx*)d_xs;
-    }
-    return 0;
+  a.B = B; a.N = N; a.xs_mode = xs_mode; a.q_mode = q_mode;
+  a.x0 = st.in<cplx>(x0, (size_t)B * n);
+  a.u = st.in<double>(u, eu.count); a.u_stride = eu.stride;
+  if (u_scale) a.u_scale = st.in<double>(u_scale, (size_t)B * m);
+  if (q_mode != 0) {
+    a.W = st.in<cplx>(W, n * n);
+    a.target = st.in<cplx>(target, ef.count); a.target_stride = ef.stride;
   }
-  int finish(int launch_rc, const char* what, double* xs, double* q) {
-    if (launch_rc) return fail(launch_rc, "%s launch failed", what);
-    HIP_TRY(hipDeviceSynchronize());
-    if (int rc = down(xs, d_xs, xs_bytes)) return rc;
-    return down(q, d_q, q_bytes);
-  }
-};
+  if (xs_mode != 0) a.xs = st.out<cplx>(xs, (size_t)B * (xs_mode == 2 ? (size_t)N + 1 : 1) * n);
+  if (q_mode != 0) a.q = st.out<double>(q, (size_t)B * (q_mode == 2 ? (size_t)N + 1 : 1));
+  return a;
+}
 }  // namespace
 
 int m4q_plant_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
@@ -1314,25 +1103,18 @@ int m4q_plant_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t pla
   if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "m4q_plant_rollout_batch: dim_x=%d is not a square, there is no device plant", dim_x);
   if (int rc = check_roll_args("m4q_plant_rollout_batch", B, N, x0, u, W, target, xs_mode, xs, q_mode, q)) return rc;
   if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "m4q_plant_rollout_batch: dts, op0 and ops are required");
-  if (plant_kind != M4Q_PLANT_HAMILTONIAN && plant_kind != M4Q_PLANT_GENERATOR && plant_kind != M4Q_PLANT_PROCESS)
-    return fail(M4Q_E_BADARG, "m4q_plant_rollout_batch: plant_kind %d is not a device plant", plant_kind);
-  if (plant_kind == M4Q_PLANT_PROCESS && dim_q(dim_x) == 0)
-    return fail(M4Q_E_BADARG, "M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", dim_x);
-  int rc = need_device();
-  if (rc) return rc;
-  const size_t n = dim_x, m = dim_u, C = 16;
-  const size_t k = plant_dim(plant_kind, dim_x);
-  RollCall c;
-  if ((rc = c.prepare(B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, xs_mode, q_mode))) return rc;
-  c.a.kind = plant_kind;
-  void *d_t, *d_0, *d_k;
-  if ((rc = c.t.up(dts, (size_t)N * 8, &d_t))) return rc;
-  if ((rc = c.t.up(op0, (plant_per_instance ? B : 1) * k * k * C, &d_0))) return rc;
-  if ((rc = c.t.up(ops, (plant_per_instance ? B : 1) * m * k * k * C, &d_k))) return rc;
-  c.a.dts = (const double*)d_t;
-  c.a.op0 = (const cplx*)d_0; c.a.op0_stride = plant_per_instance ? (long)(k * k) : 0;
-  c.a.ops = (const cplx*)d_k; c.a.ops_stride = plant_per_instance ? (long)(m * k * k) : 0;
-  return c.finish(sh->launch_plant_rollout(c.a, nullptr), "plant rollout", xs, q);
+  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_rollout_batch: plant_kind %d is not a device plant")) return rc;
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x);
+  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  Stage st;
+  m4q::RollArgs a = stage_roll(st, B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, xs_mode, xs, q_mode, q);
+  a.kind = plant_kind;
+  a.dts = st.in<double>(dts, N);
+  a.op0 = st.in<cplx>(op0, e0.count); a.op0_stride = e0.stride;
+  a.ops = st.in<cplx>(ops, ek.count); a.ops_stride = ek.stride;
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_plant_rollout(a, nullptr), "plant rollout");
 }
 
 int m4q_model_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* u,
@@ -1343,15 +1125,14 @@ int m4q_model_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t ord
   if (!sh) return fail(M4Q_E_UNSUPPORTED, "no model kernel for dim_x=%d dim_u=%d order=%d", dim_x, dim_u, order);
   if (int rc = check_roll_args("m4q_model_rollout_batch", B, N, x0, u, W, target, xs_mode, xs, q_mode, q)) return rc;
   if (!models) return fail(M4Q_E_BADARG, "m4q_model_rollout_batch: models are required");
-  int rc = need_device();
-  if (rc) return rc;
-  const size_t n = dim_x, m = dim_u, P = sh->np, C = 16;
-  RollCall c;
-  if ((rc = c.prepare(B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, xs_mode, q_mode))) return rc;
-  void* d_m;
-  if ((rc = c.t.up(models, (model_per_instance ? B : 1) * n * n * (1 + P) * C, &d_m))) return rc;
-  c.a.models = (const cplx*)d_m; c.a.model_stride = model_per_instance ? (long)(n * n * (1 + P)) : 0;
-  return c.finish(sh->launch_model_rollout(c.a, nullptr), "model rollout", xs, q);
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, P = sh->np;
+  const Extent mdl(B, model_per_instance, n * n * (1 + P));
+  Stage st;
+  m4q::RollArgs a = stage_roll(st, B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, xs_mode, xs, q_mode, q);
+  a.models = st.in<cplx>(models, mdl.count); a.model_stride = mdl.stride;
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_model_rollout(a, nullptr), "model rollout");
 }
 
 int m4q_mpc_batch(const m4q_problem* p, int32_t B, const double* models, const double* x0, const double* X_targ,

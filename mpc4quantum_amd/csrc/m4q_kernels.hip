@@ -92,6 +92,38 @@ struct LaneGeo {
   }
 };
 
+// The auxiliary kernels stride over quads of members, one member per DPP row: row g of quad `quad` works on member b.  A row past
+// the end of the ensemble repeats the last member (as row gl of the quad, for lane offsets from the quad's first member q0) so that
+// every lane stays active for the broadcasts, and stores nothing (!valid).
+__device__ __forceinline__ int quads_of(int B) { return (B + ROWS - 1) / ROWS; }
+struct QuadRow {
+  long q0;
+  bool valid;
+  unsigned gl;
+  long b;
+  __device__ __forceinline__ QuadRow(int quad, int g, int B)
+      : q0((long)quad * ROWS), valid(q0 + g < B), gl(valid ? g : (unsigned)(B - 1 - q0)), b(q0 + gl) {}
+};
+
+// xn = one held-control step of the device plant PLANT (m4q_mpc.h) from x over dt; scratch: the row's SCRATCH_ELEMS of LDS (the
+// generator needs none).  A macro, not a function: one more inlined call around the plant functions changes the code of every
+// kernel that steps a plant at the shapes with two or three controls (other address arithmetic, two more SGPRs in one of them),
+// and so does a temporary for the result in mpc_kernel.
+#define M4Q_PLANT_STEP(PLANT, xn, x, u, op0, ops, dt, scratch, j, jj)                                                   \
+  do {                                                                                                                  \
+    if constexpr ((PLANT) == PLANT_HAMILTONIAN) xn = plant_hamiltonian<NX, NU, DD>(x, u, op0, ops, dt, scratch, j, jj); \
+    else if constexpr ((PLANT) == PLANT_PROCESS) xn = plant_process<NX, NU, DQ>(x, u, op0, ops, dt, scratch, j, jj);    \
+    else xn = plant_generator<NX, NU>(x, u, op0, ops, dt, j);                                                           \
+  } while (0)
+
+// Re(d^H W d) of a row: Wr is this lane's row of W (N complex), d this lane's entry, read from the others by DPP broadcast
+template <int N>
+__device__ __forceinline__ double quad_figure(cplx d, const M4Q_GLOBAL cplx* Wr) {
+  cplx y = czero();
+  static_for<0, N>([&](auto k) { cmac(y, gld(Wr, decltype(k)::value), bcast<decltype(k)::value>(d)); });
+  return rowsum<N>(dot_re(d, y));
+}
+
 // ---------------------------------------------------------------------------------------------
 // The fused closed loop (replaces mpc.py:161-292).
 //
@@ -974,9 +1006,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
 #pragma unroll
             for (int k = 0; k < NU; ++k)
               ui[k] = (i == 0 || !(ok && measure)) ? uapp[k] : gld(a->us, b * sUs + (long)(step - i) * NU + k);
-            if constexpr (PLANT == PLANT_HAMILTONIAN) xc = plant_hamiltonian<NX, NU, DD>(xc, ui, op0, ops, dt, scratch, jio, jj);
-            else if constexpr (PLANT == PLANT_PROCESS) xc = plant_process<NX, NU, DQ>(xc, ui, op0, ops, dt, scratch, jio, jj);
-            else xc = plant_generator<NX, NU>(xc, ui, op0, ops, dt, jio);
+            M4Q_PLANT_STEP(PLANT, xc, xc, ui, op0, ops, dt, scratch, jio, jj);
           }
           xn = xc;
           // measurement noise (m4q_session_set_noise; m4q_noise.h): added to the measured state in complex original-basis form, so
@@ -1046,6 +1076,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
           const cplx x = !ok ? czero() : (prev && s0 == 0) ? gld(a->x0c, b * NX + jio)
                                                            : gld(a->xs, b * sXs + (long)(prev ? s0 : s0 + 1) * NX + jio);
           const cplx d = csub(x, ok ? gld(a->exit_target, b * a->exit_tstride + jio) : czero());
+          // (quad_figure<NX>, spelled out: through it two exact kernels of the (16, 3, 1) shape compile to other code)
           const M4Q_GLOBAL cplx* Wr = a->exit_W + jio * NX;       // row jio of W (shared, small) against the row's d
           cplx y = czero();
           static_for<0, NX>([&](auto k) { cmac(y, gld(Wr, decltype(k)::value), bcast<decltype(k)::value>(d)); });
@@ -1176,7 +1207,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
 #ifndef M4Q_VARIANT_GEN
 // ---------------------------------------------------------------------------------------------
 // Open-loop rollouts (RollArgs): what a member stores of column t of its trajectory - the state, and / or the figure
-// q = Re((x - f)^H W (x - f)), row j of W against the DPP broadcast of x - f as the exit condition of mpc_kernel forms it.
+// q = Re((x - f)^H W (x - f)) (quad_figure, as the exit condition of mpc_kernel).
 // The modes and t are wave-uniform: branches on them keep all 64 lanes active for the broadcasts; the stores are masked.
 struct RollOut {
   int N, xs_mode, q_mode;
@@ -1198,10 +1229,7 @@ struct RollOut {
       if (st) gst(xs, b * NX + j, x);
     }
     if (q_mode == 2 || (q_mode == 1 && last)) {
-      const cplx d = csub(x, f);
-      cplx y = czero();
-      static_for<0, NX>([&](auto k) { cmac(y, gld(Wr, decltype(k)::value), bcast<decltype(k)::value>(d)); });
-      const double qv = rowsum<NX>(dot_re(d, y));
+      const double qv = quad_figure<NX>(csub(x, f), Wr);
       if (st0) gst(q, q_mode == 2 ? b * (N + 1) + t : b, qv);
     }
   }
@@ -1239,30 +1267,28 @@ __global__ __launch_bounds__(64) M4Q_OCC void linearize_kernel(LinArgs a) {
   const LaneGeo L;
   const int g = L.g, jj = L.jj, j = L.j;
   cplx* mdl = lds + g * MODEL_ELEMS;
-  const int nquads = (a.B + ROWS - 1) / ROWS;
+  const int nquads = quads_of(a.B);
   const unsigned sX = (unsigned)a.T * NX, sU = (unsigned)a.T * NU;
   for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
-    const long q0 = (long)quad * ROWS;
-    const bool valid = q0 + g < a.B;
-    const unsigned gl = valid ? g : (unsigned)(a.B - 1 - q0);
+    const QuadRow r(quad, g, a.B);
     wave_sync();
-    stage_model<NX>(mdl, a.models + (q0 + gl) * a.model_stride, jj);
+    stage_model<NX>(mdl, a.models + r.b * a.model_stride, jj);
     wave_sync();
     FusedProv<cplx, NX, NU, ORDER> prov;
     prov.mdl = mdl;
-    prov.Xg = gview(a.X, q0 * sX, gl * sX);
-    prov.Ug = gview(a.U, q0 * sU, gl * sU);
+    prov.Xg = gview(a.X, r.q0 * sX, r.gl * sX);
+    prov.Ug = gview(a.U, r.q0 * sU, r.gl * sU);
     prov.j = j;
-    const GView Ao = gview(a.A_ls, q0 * sX * NX, gl * sX * NX);
-    const GView Bo = gview(a.B_ls, q0 * sX * NU, gl * sX * NU);
-    const GView Do = gview(a.D_ls, q0 * sX, gl * sX);
+    const GView Ao = gview(a.A_ls, r.q0 * sX * NX, r.gl * sX * NX);
+    const GView Bo = gview(a.B_ls, r.q0 * sX * NU, r.gl * sX * NU);
+    const GView Do = gview(a.D_ls, r.q0 * sX, r.gl * sX);
     for (int t = 0; t < a.T; ++t) {
       const auto lin = prov.fetch(t);
       cplx Ac[NX];
       prov.col(lin, Ac);
       cplx av, Brow[NU], dlt;
       prov.rows(lin, czero(), av, Brow, dlt);
-      if (valid && L.lane_ok) {
+      if (r.valid && L.lane_ok) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) Ao.st<cplx>((t * NX + i) * NX + j, Ac[i]);
 #pragma unroll
@@ -1283,22 +1309,19 @@ __global__ __launch_bounds__(64) M4Q_OCC void model_rollout_kernel(RollArgs a) {
   const LaneGeo L;
   const int g = L.g, jj = L.jj, j = L.j;
   cplx* mdl = lds + g * MODEL_ELEMS;
-  const int nquads = (a.B + ROWS - 1) / ROWS;
+  const int nquads = quads_of(a.B);
   for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
-    const long q0 = (long)quad * ROWS;
-    const bool valid = q0 + g < a.B;
-    const unsigned gl = valid ? g : (unsigned)(a.B - 1 - q0);
-    const long b = q0 + gl;
+    const QuadRow r(quad, g, a.B);
     wave_sync();
-    stage_model<NX>(mdl, a.models + b * a.model_stride, jj);
+    stage_model<NX>(mdl, a.models + r.b * a.model_stride, jj);
     wave_sync();
     FusedProv<cplx, NX, NU, ORDER> prov;
     prov.mdl = mdl;
     prov.Xg = prov.Ug = gview(a.x0, 0, 0);         // (rows() reads neither)
     prov.j = j;
-    const RollOut out(a, b, j, valid && L.lane_ok, valid && jj == 0);
-    RollCtl ctl(a, b);
-    cplx x = gld(a.x0, b * NX + j);
+    const RollOut out(a, r.b, j, r.valid && L.lane_ok, r.valid && jj == 0);
+    RollCtl ctl(a, r.b);
+    cplx x = gld(a.x0, r.b * NX + j);
     out.put(0, x);
     for (int t = 0; t < a.N; ++t) {
       FusedProv<cplx, NX, NU, ORDER>::Lin lin;
@@ -1319,7 +1342,7 @@ __global__ __launch_bounds__(64) M4Q_OCC void qp_kernel(QpArgs a) {
   const LaneGeo L;
   const int g = L.g, jj = L.jj, j = L.j;
   const int T = a.T;
-  const int nquads = (a.B + ROWS - 1) / ROWS;
+  const int nquads = quads_of(a.B);
   CostRef<cplx> cost;
   // (stage costs of the explicit QP stay in global memory: generic pointers the compiler traces back to the kernel argument)
   cost.Q = (const cplx*)a.Q_ls; cost.Qf = (const cplx*)a.Q_ls + (long)T * NX * NX; cost.q_stride = (long)NX * NX;
@@ -1327,54 +1350,51 @@ __global__ __launch_bounds__(64) M4Q_OCC void qp_kernel(QpArgs a) {
   const unsigned sX = (unsigned)(T + 1) * NX, sU = (unsigned)T * NU, sG = (unsigned)T * (NX + 1) * NU;
   const unsigned sA = (unsigned)T * NX * NX, sB = (unsigned)T * NX * NU, sD = (unsigned)T * NX;
   for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
-    const long q0 = (long)quad * ROWS;
-    const bool valid = q0 + g < a.B;
-    const unsigned gl = valid ? g : (unsigned)(a.B - 1 - q0);
-    const long b = q0 + gl;
+    const QuadRow r(quad, g, a.B);
     ExplicitProv<NX, NU> prov;
-    prov.A_ls = gview(a.A_ls, q0 * sA, gl * sA);
-    prov.B_ls = gview(a.B_ls, q0 * sB, gl * sB);
+    prov.A_ls = gview(a.A_ls, r.q0 * sA, r.gl * sA);
+    prov.B_ls = gview(a.B_ls, r.q0 * sB, r.gl * sB);
     prov.has_delta = a.D_ls != nullptr;
-    prov.D_ls = gview(a.D_ls ? a.D_ls : a.A_ls, q0 * sD, gl * sD);
+    prov.D_ls = gview(a.D_ls ? a.D_ls : a.A_ls, r.q0 * sD, r.gl * sD);
     prov.j = j;
     Window win;
-    win.xbm = gview(a.X_bm, q0 * a.xbm_stride, gl * (unsigned)a.xbm_stride);
-    win.ubm = gview(a.U_bm, q0 * a.ubm_stride, gl * (unsigned)a.ubm_stride);
-    const GView gains = gview(a.gains, q0 * sG, gl * sG);
-    const GView Xo = gview(a.X_opt, q0 * sX, gl * sX);
-    const GView Uo = gview(a.U_opt, q0 * sU, gl * sU);
-    const bool st = valid && L.lane_ok;
+    win.xbm = gview(a.X_bm, r.q0 * a.xbm_stride, r.gl * (unsigned)a.xbm_stride);
+    win.ubm = gview(a.U_bm, r.q0 * a.ubm_stride, r.gl * (unsigned)a.ubm_stride);
+    const GView gains = gview(a.gains, r.q0 * sG, r.gl * sG);
+    const GView Xo = gview(a.X_opt, r.q0 * sX, r.gl * sX);
+    const GView Uo = gview(a.U_opt, r.q0 * sU, r.gl * sU);
+    const bool st = r.valid && L.lane_ok;
     riccati_backward<cplx, NX, NU>(prov, T, win, cost, a.flags, gains, j, st);
     wave_sync();
     double lo0[NU], hi0[NU], u_first[NU];
 #pragma unroll
     for (int k = 0; k < NU; ++k) {
       const bool band = (a.flags & QP_DU_BAND) != 0 && a.u_prev != nullptr;
-      const double up = band ? gld(a.u_prev, b * NU + k) : 0.0;
+      const double up = band ? gld(a.u_prev, r.b * NU + k) : 0.0;
       lo0[k] = band ? up - a.du : -a.sat;
       hi0[k] = band ? up + a.du : a.sat;
     }
-    const cplx x0 = gld(a.x_init, b * NX + j);
+    const cplx x0 = gld(a.x_init, r.b * NX + j);
     const bool exact = (a.flags & QP_EXACT_BOX) != 0;
     // the exact solver ping-pongs between two trajectory pairs of ONE allocation (rows pick theirs by lane offset):
     // X_alt = [B][T+1][n] twice, U_alt likewise; the clipped rollout, its starting point, goes straight into the first
-    const GView Xa = gview(exact ? a.X_alt : a.X_opt, q0 * sX, gl * sX);
-    const GView Ua = gview(exact ? a.U_alt : a.U_opt, q0 * sU, gl * sU);
+    const GView Xa = gview(exact ? a.X_alt : a.X_opt, r.q0 * sX, r.gl * sX);
+    const GView Ua = gview(exact ? a.U_alt : a.U_opt, r.q0 * sU, r.gl * sU);
     const double obj = rollout_forward<cplx, NX, NU, true>(prov, T, x0, win, cost, a.flags, gains, a.sat, lo0, hi0, Xa, Ua, j, st,
                                                               u_first);
     wave_sync();
     double obj_out = obj;
     if (exact) {
-      const GView Xb = gview(a.X_alt, q0 * sX, gl * sX + (unsigned)a.B * sX);
-      const GView Ub = gview(a.U_alt, q0 * sU, gl * sU + (unsigned)a.B * sU);
-      const GView stat = gview(a.pin_stat, q0 * sU, gl * sU);
+      const GView Xb = gview(a.X_alt, r.q0 * sX, r.gl * sX + (unsigned)a.B * sX);
+      const GView Ub = gview(a.U_alt, r.q0 * sU, r.gl * sU + (unsigned)a.B * sU);
+      const GView stat = gview(a.pin_stat, r.q0 * sU, r.gl * sU);
       PinCtx<NU> pin;
       pin.stat = stat;
       pin.box.sat = a.sat;
 #pragma unroll
       for (int k = 0; k < NU; ++k) { pin.lo0[k] = lo0[k]; pin.hi0[k] = hi0[k]; }
       BoxQpRow row;
-      if (valid) row.begin(obj);
+      if (r.valid) row.begin(obj);
       while (__any(row.busy())) box_qp_iterate<cplx, NX, NU>(prov, T, x0, win, cost, a.flags, gains, pin, Xa, Ua, Xb, Ub, row, j, jj, L.lane_ok);
       obj_out = row.Jk;
       const QpStats& stats = row.stats;
@@ -1386,18 +1406,18 @@ __global__ __launch_bounds__(64) M4Q_OCC void qp_kernel(QpArgs a) {
         if (j == 0)
           for (int i = 0; i < T * NU; ++i) Uo.st<double>(i, Us.ld<double>(i));
       }
-      if (valid && jj == 0 && a.sweep_counts) gst(a.sweep_counts, b, stats.sweeps);
+      if (r.valid && jj == 0 && a.sweep_counts) gst(a.sweep_counts, r.b, stats.sweeps);
       wave_sync();
     }
-    if (valid && jj == 0) gst(a.cost, b, obj_out);
+    if (r.valid && jj == 0) gst(a.cost, r.b, obj_out);
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// One held-control plant step for B states (experiment.py:202-212)
 #endif  // M4Q_NO_AUX
 
 #ifndef M4Q_VARIANT_GEN
+// ---------------------------------------------------------------------------------------------
+// One held-control plant step for B states (experiment.py:202-212)
 // ---------------------------------------------------------------------------------------------
 template <int PLANT>
 __global__ __launch_bounds__(64) M4Q_OCC void plant_kernel(PlantArgs a) {
@@ -1405,26 +1425,18 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_kernel(PlantArgs a) {
   const LaneGeo L;
   const int g = L.g, jj = L.jj, j = L.j;
   cplx* scratch = lds + g * SCRATCH_ELEMS;
-  const int nquads = (a.B + ROWS - 1) / ROWS;
+  const int nquads = quads_of(a.B);
   for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
-    const long q0 = (long)quad * ROWS;
-    const bool valid = q0 + g < a.B;
-    const unsigned gl = valid ? g : (unsigned)(a.B - 1 - q0);
-    const long b = q0 + gl;
-    const cplx x = gld(a.x, b * NX + j);
+    const QuadRow r(quad, g, a.B);
+    const cplx x = gld(a.x, r.b * NX + j);
     double u[NU];
 #pragma unroll
-    for (int k = 0; k < NU; ++k) u[k] = gld(a.u, b * NU + k);
-    const GView op0 = gview(a.op0, q0 * a.op0_stride, gl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, q0 * a.ops_stride, gl * (unsigned)a.ops_stride);
+    for (int k = 0; k < NU; ++k) u[k] = gld(a.u, r.b * NU + k);
+    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
+    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
     cplx xn;
-    if constexpr (PLANT == PLANT_HAMILTONIAN)
-      xn = plant_hamiltonian<NX, NU, DD>(x, u, op0, ops, a.dt, scratch, j, jj);
-    else if constexpr (PLANT == PLANT_PROCESS)
-      xn = plant_process<NX, NU, DQ>(x, u, op0, ops, a.dt, scratch, j, jj);
-    else
-      xn = plant_generator<NX, NU>(x, u, op0, ops, a.dt, j);
-    if (valid && jj < NX) gst(a.x_next, b * NX + j, xn);
+    M4Q_PLANT_STEP(PLANT, xn, x, u, op0, ops, a.dt, scratch, j, jj);
+    if (r.valid && jj < NX) gst(a.x_next, r.b * NX + j, xn);
   }
 }
 
@@ -1437,18 +1449,15 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_rollout_kernel(RollArgs a) {
   const LaneGeo L;
   const int g = L.g, jj = L.jj, j = L.j;
   cplx* scratch = lds + g * SCRATCH_ELEMS;
-  const int nquads = (a.B + ROWS - 1) / ROWS;
+  const int nquads = quads_of(a.B);
   for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
-    const long q0 = (long)quad * ROWS;
-    const bool valid = q0 + g < a.B;
-    const unsigned gl = valid ? g : (unsigned)(a.B - 1 - q0);
-    const long b = q0 + gl;
-    const GView op0 = gview(a.op0, q0 * a.op0_stride, gl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, q0 * a.ops_stride, gl * (unsigned)a.ops_stride);
-    const RollOut out(a, b, j, valid && L.lane_ok, valid && jj == 0);
-    RollCtl ctl(a, b);
+    const QuadRow r(quad, g, a.B);
+    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
+    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const RollOut out(a, r.b, j, r.valid && L.lane_ok, r.valid && jj == 0);
+    RollCtl ctl(a, r.b);
     double dtn = gld(a.dts, 0);
-    cplx x = gld(a.x0, b * NX + j);
+    cplx x = gld(a.x0, r.b * NX + j);
     out.put(0, x);
     for (int t = 0; t < a.N; ++t) {
       double u[NU];
@@ -1460,12 +1469,7 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_rollout_kernel(RollArgs a) {
       // VGPRs against 49, d = 4: 68 against 6).  The d or (1 + m) d entries of the other two plants stay in registers.
       GView o0 = op0, ok = ops;
       if constexpr (PLANT == PLANT_GENERATOR) asm volatile("" : "+v"(o0.off), "+v"(ok.off));
-      if constexpr (PLANT == PLANT_HAMILTONIAN)
-        x = plant_hamiltonian<NX, NU, DD>(x, u, o0, ok, dt, scratch, j, jj);
-      else if constexpr (PLANT == PLANT_PROCESS)
-        x = plant_process<NX, NU, DQ>(x, u, o0, ok, dt, scratch, j, jj);
-      else
-        x = plant_generator<NX, NU>(x, u, o0, ok, dt, j);
+      M4Q_PLANT_STEP(PLANT, x, x, u, o0, ok, dt, scratch, j, jj);
       out.put(t + 1, x);
     }
   }
@@ -1484,12 +1488,14 @@ __global__ __launch_bounds__(64) void noise_sample_kernel(NoiseArgs a) {
   }
 }
 
+#endif  // M4Q_VARIANT_GEN
+
+#if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
 // ---------------------------------------------------------------------------------------------
 // discretize_homogeneous for B generator sets (vectorize.py:8-49): Taylor/Dyson expansion of
 // exp(dt (G_0 + sum_k u_k G_k)) to ORDER, every word of operators multiplied out and binned by its control
 // monomial.  One row per instance; generators staged in LDS, products column-owned in registers.
-#endif  // M4Q_VARIANT_GEN
-
+// (orders 3 and 4 have closed-loop kernels but no device discretisation: their models come from the host, discretize_homogeneous)
 // ---------------------------------------------------------------------------------------------
 constexpr int find_monomial(int c0, int c1, int c2) {
   constexpr PowTab<NU, ORDER> tab{};
@@ -1520,10 +1526,11 @@ __global__ __launch_bounds__(64) void discretize_kernel(DiscArgs a) {
   constexpr int GEN_ELEMS = (1 + NU) * NX * NX;
   constexpr int W = NX * (1 + NP);
   S* G = lds + g * GEN_ELEMS;                      // [1+m][n][n] row-major, scaled
-  const int nquads = (a.B + ROWS - 1) / ROWS;
+  const int nquads = quads_of(a.B);
   const M4Q_GLOBAL S* gens = (const M4Q_GLOBAL S*)a.gens;
   M4Q_GLOBAL S* models = (M4Q_GLOBAL S*)a.models;
   for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    // (QuadRow's member, written as one select: as q0 + gl it costs seven of these kernels one or two VGPRs)
     const long q0 = (long)quad * ROWS;
     const bool valid = q0 + g < a.B;
     const long b = valid ? q0 + g : a.B - 1;
@@ -1571,6 +1578,7 @@ __global__ __launch_bounds__(64) void discretize_kernel(DiscArgs a) {
     }
   }
 }
+#endif  // !M4Q_NO_AUX && M4Q_ORDER <= 2
 
 // ---------------------------------------------------------------------------------------------
 // host-side launchers for this shape
@@ -1685,49 +1693,48 @@ static int grid_for(int B) {
   return nquads < 4096 ? (nquads > 0 ? nquads : 1) : 4096;
 }
 
+// an auxiliary kernel over quads of members: grid_for(B) workgroups of one wavefront, `lds` bytes of dynamic LDS
+template <class K, class A>
+static int launch_aux(K kern, const A& a, size_t lds, hipStream_t s) {
+  int rc = prep_lds(kern, lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid_for(a.B)), dim3(64), lds, s, a);
+  return -(int)hipGetLastError();
+}
+[[maybe_unused]] constexpr int UNBUILT = -(int)hipErrorInvalidValue;      // what the launcher of a kernel this object does not hold returns
+
 #ifndef M4Q_NO_AUX
-static int launch_linearize(const LinArgs& a, hipStream_t s) {
-  const size_t lds = sizeof(cplx) * (size_t)(ROWS * MODEL_ELEMS);
-  int rc = prep_lds(linearize_kernel, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(linearize_kernel, dim3(grid_for(a.B)), dim3(64), lds, s, a);
-  return -(int)hipGetLastError();
-}
-
-static int launch_qp(const QpArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(qp_kernel, dim3(grid_for(a.B)), dim3(64), 0, s, a);
-  return -(int)hipGetLastError();
-}
-
-static int launch_model_rollout(const RollArgs& a, hipStream_t s) {
-  const size_t lds = sizeof(cplx) * (size_t)(ROWS * MODEL_ELEMS);
-  int rc = prep_lds(model_rollout_kernel, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(model_rollout_kernel, dim3(grid_for(a.B)), dim3(64), lds, s, a);
-  return -(int)hipGetLastError();
-}
-
+constexpr size_t MODEL_LDS = sizeof(cplx) * (size_t)(ROWS * MODEL_ELEMS);
+static int launch_linearize(const LinArgs& a, hipStream_t s) { return launch_aux(linearize_kernel, a, MODEL_LDS, s); }
+static int launch_qp(const QpArgs& a, hipStream_t s) { return launch_aux(qp_kernel, a, 0, s); }
+static int launch_model_rollout(const RollArgs& a, hipStream_t s) { return launch_aux(model_rollout_kernel, a, MODEL_LDS, s); }
 #else
-static int launch_linearize(const LinArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
-static int launch_qp(const QpArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
-static int launch_model_rollout(const RollArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
+static int launch_linearize(const LinArgs&, hipStream_t) { return UNBUILT; }
+static int launch_qp(const QpArgs&, hipStream_t) { return UNBUILT; }
+static int launch_model_rollout(const RollArgs&, hipStream_t) { return UNBUILT; }
 #endif
 
 #ifndef M4Q_VARIANT_GEN
-static int launch_plant(const PlantArgs& a, hipStream_t s) {
+// the kernel of a.kind among those of one family: kernel_of(ic<PLANT>) names them (plant_kernel, plant_rollout_kernel)
+template <class A, class F>
+static int launch_by_plant(const A& a, hipStream_t s, F kernel_of) {
   if constexpr (!SQUARE) {
-    return -(int)hipErrorInvalidValue;
+    return UNBUILT;
   } else {
-  const size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
-  if (a.kind == PLANT_HAMILTONIAN)
-    hipLaunchKernelGGL(plant_kernel<PLANT_HAMILTONIAN>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
-  else if (a.kind == PLANT_PROCESS) {
-    if constexpr (QUARTIC) hipLaunchKernelGGL(plant_kernel<PLANT_PROCESS>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
-    else return -(int)hipErrorInvalidValue;
-  } else
-    hipLaunchKernelGGL(plant_kernel<PLANT_GENERATOR>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
-  return -(int)hipGetLastError();
+    constexpr size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
+    if (a.kind == PLANT_HAMILTONIAN) return launch_aux(kernel_of(ic<PLANT_HAMILTONIAN>{}), a, lds, s);
+    if (a.kind == PLANT_PROCESS) {
+      if constexpr (QUARTIC) return launch_aux(kernel_of(ic<PLANT_PROCESS>{}), a, lds, s);
+      else return UNBUILT;
+    }
+    return launch_aux(kernel_of(ic<PLANT_GENERATOR>{}), a, lds, s);
   }
+}
+static int launch_plant(const PlantArgs& a, hipStream_t s) {
+  return launch_by_plant(a, s, [](auto plant) { return plant_kernel<decltype(plant)::value>; });
+}
+static int launch_plant_rollout(const RollArgs& a, hipStream_t s) {
+  return launch_by_plant(a, s, [](auto plant) { return plant_rollout_kernel<decltype(plant)::value>; });
 }
 
 static int launch_noise(const NoiseArgs& a, hipStream_t s) {
@@ -1735,48 +1742,25 @@ static int launch_noise(const NoiseArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(noise_sample_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, s, a);
   return -(int)hipGetLastError();
 }
-
-static int launch_plant_rollout(const RollArgs& a, hipStream_t s) {
-  if constexpr (!SQUARE) {
-    return -(int)hipErrorInvalidValue;
-  } else {
-  const size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
-  if (a.kind == PLANT_HAMILTONIAN)
-    hipLaunchKernelGGL(plant_rollout_kernel<PLANT_HAMILTONIAN>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
-  else if (a.kind == PLANT_PROCESS) {
-    if constexpr (QUARTIC) hipLaunchKernelGGL(plant_rollout_kernel<PLANT_PROCESS>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
-    else return -(int)hipErrorInvalidValue;
-  } else
-    hipLaunchKernelGGL(plant_rollout_kernel<PLANT_GENERATOR>, dim3(grid_for(a.B)), dim3(64), lds, s, a);
-  return -(int)hipGetLastError();
-  }
-}
-
 #else
-static int launch_plant(const PlantArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
-static int launch_noise(const NoiseArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
-static int launch_plant_rollout(const RollArgs&, hipStream_t) { return -(int)hipErrorInvalidValue; }
+static int launch_plant(const PlantArgs&, hipStream_t) { return UNBUILT; }
+static int launch_noise(const NoiseArgs&, hipStream_t) { return UNBUILT; }
+static int launch_plant_rollout(const RollArgs&, hipStream_t) { return UNBUILT; }
 #endif
 
 #if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
 // coords: complex generators; real n x n (lifted to the Hermitian basis); real (n-1) x (n-1) (their traceless blocks)
-// (orders 3 and 4 have closed-loop kernels but no device discretisation: their models come from the host, discretize_homogeneous)
 static int launch_discretize(const DiscArgs& a, Coords coords, hipStream_t s) {
-  if (!SQUARE && coords != COORDS_COMPLEX) return -(int)hipErrorInvalidValue;
-  const size_t elems = (size_t)ROWS * (1 + NU) * NX * NX;
+  if (!SQUARE && coords != COORDS_COMPLEX) return UNBUILT;
+  constexpr size_t elems = (size_t)ROWS * (1 + NU) * NX * NX;
   if constexpr (SQUARE) {
-    if (coords == COORDS_TRACELESS) {
-      hipLaunchKernelGGL((discretize_kernel<double, NX - 1>), dim3(grid_for(a.B)), dim3(64), elems * sizeof(double), s, a);
-      return -(int)hipGetLastError();
-    }
+    if (coords == COORDS_TRACELESS) return launch_aux(discretize_kernel<double, NX - 1>, a, elems * sizeof(double), s);
   }
-  if (coords == COORDS_HERM) hipLaunchKernelGGL((discretize_kernel<double, NX>), dim3(grid_for(a.B)), dim3(64), elems * sizeof(double), s, a);
-  else hipLaunchKernelGGL((discretize_kernel<cplx, NX>), dim3(grid_for(a.B)), dim3(64), elems * sizeof(cplx), s, a);
-  return -(int)hipGetLastError();
+  if (coords == COORDS_HERM) return launch_aux(discretize_kernel<double, NX>, a, elems * sizeof(double), s);
+  return launch_aux(discretize_kernel<cplx, NX>, a, elems * sizeof(cplx), s);
 }
-
 #else
-static int launch_discretize(const DiscArgs&, Coords, hipStream_t) { return -(int)hipErrorInvalidValue; }
+static int launch_discretize(const DiscArgs&, Coords, hipStream_t) { return UNBUILT; }
 #endif
 
 static int power_list(int32_t* out) {

@@ -1,6 +1,6 @@
 """AddressSanitizer build of the host side of the C ABI ("Race detection / sanitizers").
 
-m4q_capi.hip - 1,100 lines of pointer / size handling (field tables, bind_output, put_state, the one-shot entry points'
+m4q_capi.hip - 1,350 lines of pointer / size handling (field tables, bind_output, put_state, the one-shot entry points'
 temporary buffers, the communicator) - is compiled host-only with -fsanitize=address, linked with the product's kernel
 objects and tests/asan/capi_driver.cpp, and run with the devices hidden: every entry point on its argument-validation paths and
 on its no-device path (leak check on).  The sanitizer is for host code only: the compile of m4q_capi.hip is host-only and the
