@@ -198,6 +198,33 @@ M4Q_API int m4q_model_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int
                             const double* W, const double* target, int32_t target_per_instance, int32_t xs_mode, double* xs,
                             int32_t q_mode, double* q);
 
+/* DMDc identification for an ensemble in ONE launch: DiscrepDMDc.from_data(X2, X1, krtimes(lift(U1), X1), rcond) = X2 pinv(Z, rcond)
+ * (model.py: DiscrepDMDc.from_data, the fit of the reference's training workflow) for B members and R cut-offs, the models in the layout every other
+ * entry point takes.  mpc4quantum_amd/fit.py (dmdc_fit_reference) is the definition, in NumPy, in the kernel's order of operations.
+ * Member b has E experiments of N steps: xs [B][E][N+1][n] c, u [B|1][E][N][m] r (u_per_instance 0: one set shared by the ensemble),
+ * u_scale [B][m] r or NULL: the member saw u_scale[b][k] u[e][t][k], formed on the device in fp64 as the rollouts form it.
+ * Every snapshot (e, t) gives z = [x_t ; lift(u_t) (x) x_t] (the monomials of m4q_power_list without the constant, Kronecker row
+ * p n + j; nz = n (1 + P)).  G = sum z z^H and C = sum x_{t+1} z^H are accumulated (e outer, t inner), G = V diag(lam) V^H comes from
+ * cyclic-by-rows Jacobi with complex Hermitian rotations (a rotation is skipped when |g_pq| <= eps sqrt(g_pp g_qq), the iteration
+ * stops after a sweep without rotations, 30 sweeps at the most), and for each rconds[r] the eigenpairs with
+ * lam > rconds[r]^2 max(lam) give A_r = C V_k diag(lam_k)^-1 V_k^H: numpy's pinv cuts the singular values s = sqrt(lam) at
+ * s > rcond max(s).  The decomposition is done once; every cut-off costs one truncated product.
+ * rconds [R], 1 <= R <= M4Q_FIT_MAX_RCONDS, each in [M4Q_FIT_RCOND_MIN, 1) = [1e-7, 1): below that the cut-off rcond^2 lies in the
+ * Gram matrix's own rounding floor (~ nz eps) and the rank cannot be decided from G - fit with rcond = 1e-15 on the host
+ * (DiscrepDMDc.from_data, an SVD of the data themselves).
+ * -> models [R][B][n][n(1+P)] c; ranks [R][B] (the eigenpairs kept) or NULL; svals [B][nz] r or NULL: the singular values of the
+ * stacked data, descending, s_k = sqrt(sum |v_k^H z|^2) - lam_k = v_k^H G v_k taken from the snapshots themselves in a second pass
+ * over them, so a vanishing singular value comes back at ~eps s_0 and not at sqrt of G's rounding floor; status [B]: 0 ok, 1 the Jacobi iteration hit its cap (the models are written from
+ * the last iterate), 3 non-finite data (zero models and singular values, rank 0).
+ * M4Q_E_BADARG: B, E, N or R < 1, R > 16, an rcond outside the range (or NaN), a missing xs, u, rconds, models or status.
+ * M4Q_E_UNSUPPORTED: no compiled shape, a plant-only shape, a shape whose LDS layout (2 nz^2 + n nz complex numbers) exceeds one
+ * workgroup's 160 KiB - (16, 1, 4), nz = 80.  Arguments are checked before the device is asked for. */
+#define M4Q_FIT_MAX_RCONDS 16
+#define M4Q_FIT_RCOND_MIN 1e-7
+M4Q_API int m4q_dmdc_fit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs,
+                       const double* u, int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R,
+                       double* models, int32_t* ranks, double* svals, int32_t* status);
+
 /* replaces the whole mpc() loop body (mpc.py:161-292) for B closed loops, all n_steps in one launch.
  * models [B|1][n][n(1+P)] c, x0 [B][n] c, X_targ [B|1][cols][n] c, U_targ [B|1][cols][m] r,
  * Q, Qf [n][n] c, R [m][m] c, op0/ops as in m4q_plant_step_batch

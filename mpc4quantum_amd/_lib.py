@@ -68,6 +68,7 @@ PROTOTYPES = {
                                           _i32, _dp, _i32, _dp]),
     "m4q_model_rollout_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _i32, _dp,
                                           _i32, _dp]),
+    "m4q_dmdc_fit_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _ip]),
     "m4q_mpc_batch": (C.c_int, [C.POINTER(Problem), _i32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
                                 _ip, _ip]),
     "m4q_session_create": (C.c_int, [C.POINTER(Problem), _i32, _i32, C.POINTER(_vp)]),

@@ -133,6 +133,21 @@ struct RollArgs {
   M4Q_P(cplx) xs; M4Q_P(double) q;
 };
 
+// m4q_dmdc_fit_batch: the truncated least-squares DMDc fit of B members from E experiments of N steps each (m4q_fit.h; fit.py is
+// the definition).  The member sees u_scale[b][k] u[e][t][k], as in the rollouts.  rconds live in device memory: the kernel indexes
+// them at run time.
+struct FitArgs {
+  int B, E, N, R;
+  M4Q_P(const cplx) xs;                            // [B][E][N + 1][n]
+  M4Q_P(const double) u; long u_stride;            // [B|1][E][N][m] (u_stride E N m or 0)
+  M4Q_P(const double) u_scale;                     // [B][m] or null
+  M4Q_P(const double) rconds;                      // [R]
+  M4Q_P(cplx) models;                              // [R][B][n][n(1+P)]
+  M4Q_P(int) ranks;                                // [R][B] or null
+  M4Q_P(double) svals;                             // [B][n(1+P)] or null
+  M4Q_P(int) status;                               // [B]: 0 ok, 1 the Jacobi iteration hit its cap, 3 non-finite data
+};
+
 // noise.py's sample() for B members at one state_index (m4q_noise_sample_batch): out [B][n] complex
 struct NoiseArgs {
   int B, mode;
@@ -159,6 +174,8 @@ struct ShapeOps {
   int (*launch_noise)(const NoiseArgs&, hipStream_t);             // (depends on dim_x alone)
   int (*launch_plant_rollout)(const RollArgs&, hipStream_t);      // (square shapes, plant-only ones included)
   int (*launch_model_rollout)(const RollArgs&, hipStream_t);      // (every shape with a model)
+  int fit_lds_bytes;                                              // dynamic LDS of dmdc_fit_kernel; 0: the shape has none (no model, or
+  int (*launch_fit)(const FitArgs&, hipStream_t);                 // its layout does not fit one workgroup's LDS)
 };
 
 }  // namespace m4q

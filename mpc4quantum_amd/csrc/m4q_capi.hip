@@ -1135,6 +1135,39 @@ int m4q_model_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t ord
   return st.finish(sh->launch_model_rollout(a, nullptr), "model rollout");
 }
 
+int m4q_dmdc_fit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs, const double* u,
+                       int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R, double* models, int32_t* ranks,
+                       double* svals, int32_t* status) {
+  const m4q::ShapeOps* sh = find_shape(dim_x, dim_u, order);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no model kernel for dim_x=%d dim_u=%d order=%d", dim_x, dim_u, order);
+  if (sh->fit_lds_bytes == 0)
+    return fail(M4Q_E_UNSUPPORTED, "m4q_dmdc_fit_batch: the Gram data of dim_x=%d dim_u=%d order=%d (nz = %d) do not fit one workgroup's "
+                "LDS; fit such models on the host (DiscrepDMDc.from_data)", dim_x, dim_u, order, dim_x * (1 + sh->np));
+  if (B < 1 || E < 1 || N < 1) return fail(M4Q_E_BADARG, "m4q_dmdc_fit_batch: B, E and N must be at least 1 (got %d, %d, %d)", B, E, N);
+  if (R < 1 || R > M4Q_FIT_MAX_RCONDS) return fail(M4Q_E_BADARG, "m4q_dmdc_fit_batch: R must be 1..%d, got %d", M4Q_FIT_MAX_RCONDS, R);
+  if (!xs || !u || !rconds || !models || !status) return fail(M4Q_E_BADARG, "m4q_dmdc_fit_batch: xs, u, rconds, models and status are required");
+  for (int r = 0; r < R; ++r)
+    if (!(rconds[r] >= M4Q_FIT_RCOND_MIN && rconds[r] < 1.0))
+      return fail(M4Q_E_BADARG, "m4q_dmdc_fit_batch: rconds[%d] = %g is outside [%g, 1): below that the cut-off lies in the Gram matrix's "
+                  "rounding floor (fit on the host with DiscrepDMDc.from_data)", r, rconds[r], M4Q_FIT_RCOND_MIN);
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, nz = n * (1 + (size_t)sh->np);
+  const Extent eu(B, u_per_instance, (size_t)E * N * m);
+  Stage st;
+  m4q::FitArgs a{};
+  a.B = B; a.E = E; a.N = N; a.R = R;
+  a.xs = st.in<cplx>(xs, (size_t)B * E * ((size_t)N + 1) * n);
+  a.u = st.in<double>(u, eu.count); a.u_stride = eu.stride;
+  if (u_scale) a.u_scale = st.in<double>(u_scale, (size_t)B * m);
+  a.rconds = st.in<double>(rconds, R);
+  a.models = st.out<cplx>(models, (size_t)R * B * n * nz);
+  if (ranks) a.ranks = st.out<int>(ranks, (size_t)R * B);
+  if (svals) a.svals = st.out<double>(svals, (size_t)B * nz);
+  a.status = st.out<int>(status, B);
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_fit(a, nullptr), "DMDc fit");
+}
+
 int m4q_mpc_batch(const m4q_problem* p, int32_t B, const double* models, const double* x0, const double* X_targ,
                   const double* U_targ, const double* Q, const double* R, const double* Qf, const double* op0,
                   const double* ops, double* xs, double* us, int32_t* exit_codes, int32_t* steps_done,

@@ -6,6 +6,7 @@
 #define M4Q_KERNEL_TU 1
 #include "m4q_args.h"
 #include "m4q_mpc.h"
+#include "m4q_fit.h"
 #include "m4q_noise.h"
 #include "m4q_tile3.h"
 
@@ -1336,6 +1337,26 @@ __global__ __launch_bounds__(64) M4Q_OCC void model_rollout_kernel(RollArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// DMDc identification of B members (m4q_dmdc_fit_batch; fit.py: dmdc_fit_reference is the definition): one wavefront per member,
+// grid-stride over members; the Gram data, the eigenvectors and the eigenvalues in dynamic LDS (FitLayout, m4q_fit.h).
+// ---------------------------------------------------------------------------------------------
+template <int NX_, int NU_, int ORDER_>
+__global__ __launch_bounds__(64) void dmdc_fit_kernel(FitArgs a) {
+  using L = FitLayout<NX_, NU_, ORDER_>;
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const int lane = threadIdx.x;
+  for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
+    wave_sync();                                   // the previous member's reads are done
+    const bool finite = fit_accumulate<NX_, NU_, ORDER_>(a, b, lds, lane);
+    bool converged = true;
+    if (uniform(finite)) converged = fit_jacobi<L::NZ, L::PITCH>(lds + L::G, lds + L::V, lane);
+    if (a.svals) fit_svals<NX_, NU_, ORDER_>(a, b, lds, lane, finite);
+    fit_models<NX_, NU_, ORDER_>(a, b, lds, lane, finite);
+    if (lane == 0) gst(a.status, b, !finite ? 3 : converged ? 0 : 1);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // quad_program for B explicit linear time-varying problems (optimize.py:12-60 / lqr.py:14-79)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) M4Q_OCC void qp_kernel(QpArgs a) {
@@ -1708,7 +1729,27 @@ constexpr size_t MODEL_LDS = sizeof(cplx) * (size_t)(ROWS * MODEL_ELEMS);
 static int launch_linearize(const LinArgs& a, hipStream_t s) { return launch_aux(linearize_kernel, a, MODEL_LDS, s); }
 static int launch_qp(const QpArgs& a, hipStream_t s) { return launch_aux(qp_kernel, a, 0, s); }
 static int launch_model_rollout(const RollArgs& a, hipStream_t s) { return launch_aux(model_rollout_kernel, a, MODEL_LDS, s); }
+// (a partial specialisation, so that the kernel is instantiated only for the shapes whose layout fits)
+template <bool FITS, int N_ = NX>
+struct FitLaunch {
+  static int run(const FitArgs&, hipStream_t) { return UNBUILT; }
+};
+template <int N_>
+struct FitLaunch<true, N_> {
+  static int run(const FitArgs& a, hipStream_t s) {
+    constexpr size_t lds = FitLayout<N_, NU, ORDER>::BYTES;
+    int rc = prep_lds(dmdc_fit_kernel<N_, NU, ORDER>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((dmdc_fit_kernel<N_, NU, ORDER>), dim3(a.B < 4096 ? a.B : 4096), dim3(64), lds, s, a);
+    return -(int)hipGetLastError();
+  }
+};
+constexpr bool FIT_FITS = FitLayout<NX, NU, ORDER>::FITS;
+constexpr int FIT_LDS = FIT_FITS ? (int)FitLayout<NX, NU, ORDER>::BYTES : 0;
+static int launch_fit(const FitArgs& a, hipStream_t s) { return FitLaunch<FIT_FITS>::run(a, s); }
 #else
+constexpr int FIT_LDS = 0;
+static int launch_fit(const FitArgs&, hipStream_t) { return UNBUILT; }
 static int launch_linearize(const LinArgs&, hipStream_t) { return UNBUILT; }
 static int launch_qp(const QpArgs&, hipStream_t) { return UNBUILT; }
 static int launch_model_rollout(const RollArgs&, hipStream_t) { return UNBUILT; }
@@ -1777,7 +1818,7 @@ static const ShapeOps* shape_ops() {
   constexpr int plant_only = 0;
 #endif
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
-                               launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout};
+                               launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit};
   return &ops;
 }
 

@@ -1,0 +1,278 @@
+"""Batched DMDc identification: trajectories and controls of B members in, their models out, in ONE launch
+(m4q_dmdc_fit_batch) - `DiscrepDMDc.from_data(X2, X1, krtimes(U1, X1), rcond=...)` for an ensemble and a whole grid of rcond.
+
+This module is the normative definition of what the kernel computes (csrc/m4q_fit.h reproduces it, in the same order of
+operations), as noise.py is for the generator.  Per member, with E experiments of N steps (xs [E, N + 1, n] complex, u [E, N, m]
+real, optional u_scale [m]: the member sees u_scale[k] u[t][k], one fp64 product):
+
+  snapshots   z = [x_t ; lift(u_t) (x) x_t] for every (e, t), e outer, t inner; lift(u) = the non-constant monomials in
+              create_power_list(order, m) order (WrapModel.lift_u), the Kronecker rows as krtimes numbers them (p n + j):
+              nz = n (1 + P).
+  Gram data   G = sum z z^H (nz x nz; the upper triangle is accumulated, the lower is its conjugate, the diagonal real) and
+              C = sum x_{t+1} z^H (n x nz).
+  spectrum    G = V diag(lam) V^H by cyclic-by-rows Jacobi with complex Hermitian rotations (p < q, p outer).  A rotation is
+              skipped when |g_pq|^2 <= eps^2 |g_pp g_qq|; the solver stops after a sweep that skipped every rotation, and after
+              MAX_SWEEPS = 30 sweeps in any case (status 1).
+  models      for each rcond: keep lam_k > rcond^2 max(lam);  A = sum over the kept k, ascending, of (W[:, k] / lam_k) V[:, k]^H
+              with W = C V;  rank = the number kept.  This is Y pinv(Z, rcond): s_k = sqrt(lam_k), and numpy cuts at
+              s > rcond s_max.
+  svals       s_k = sqrt(sum |v_k^H z|^2) over the snapshots in their order, descending: lam_k = v_k^H G v_k taken from the data
+              themselves, a sum of non-negative terms, so a singular value that vanishes comes back at ~eps s_0 and not at
+              sqrt of G's rounding floor (~1e-8 s_0).  The ranks and the models are decided by lam alone.
+
+The decomposition is done once, every rcond costs one truncated product.  rcond must lie in [RCOND_MIN, 1) = [1e-7, 1): below that
+the cut-off rcond^2 sits in the Gram matrix's own rounding floor (~ nz eps relative to max(lam)) and the rank is no longer
+decidable from G.  The host `DiscrepDMDc.from_data` (an SVD of Z itself) remains the path for rcond = 1e-15.
+
+status per member: 0 ok; 1 the Jacobi iteration hit its cap (the models are written from the last iterate); 3 non-finite data
+(G or C has a non-finite entry, which any non-finite sample produces): the models are zero and the rank is 0."""
+import numpy as np
+
+from . import _lib
+from .library import create_power_list, size_of_library
+from .rollout import model_rollout_batch
+
+RCOND_MIN = 1e-7
+MAX_RCONDS = 16
+MAX_SWEEPS = 30
+_EPS = float(np.finfo(np.float64).eps)
+
+
+def lift_controls(u, order):
+    """u [..., m] -> the P non-constant monomials [..., P] in create_power_list order; the powers as repeated products
+    u (u (u ...)), the factors taken over the controls in their order."""
+    u = np.asarray(u, dtype=np.float64)
+    m = u.shape[-1]
+    out = []
+    for powers in create_power_list(order, m)[1:]:
+        v = np.ones(u.shape[:-1])
+        for k in range(m):
+            w = np.ones(u.shape[:-1])
+            for _ in range(int(powers[k])):
+                w = u[..., k] * w
+            v = v * w
+        out.append(v)
+    return np.stack(out, axis=-1)
+
+
+def stack_snapshots(xs, u, order):
+    """One member's Z [nz, E N] and Y = X2 [n, E N] in the (e, t) order of the sums; xs [E, N + 1, n], u [E, N, m] as the member
+    sees them."""
+    E, N1, n = xs.shape
+    pu = lift_controls(u, order)                                                      # [E, N, P]
+    x1 = xs[:, :-1, :]
+    z = np.concatenate([x1[:, :, None, :], pu[:, :, :, None] * x1[:, :, None, :]], axis=2)     # [E, N, 1 + P, n]
+    return z.reshape(E * (N1 - 1), -1).T, xs[:, 1:, :].reshape(E * (N1 - 1), n).T
+
+
+def gram(Z, Y):
+    """G = sum z z^H and C = sum y z^H over the columns in their order."""
+    nz, S = Z.shape
+    G = np.zeros((nz, nz), dtype=np.complex128)
+    C = np.zeros((Y.shape[0], nz), dtype=np.complex128)
+    for s in range(S):
+        G += np.outer(Z[:, s], Z[:, s].conj())
+        C += np.outer(Y[:, s], Z[:, s].conj())
+    iu = np.triu_indices(nz, 1)
+    G[(iu[1], iu[0])] = G[iu].conj()
+    G[np.diag_indices(nz)] = G[np.diag_indices(nz)].real
+    return G, C
+
+
+def jacobi_hermitian(G):
+    """Cyclic-by-rows Jacobi on a Hermitian matrix.  Returns (lam [nz], V [nz, nz], sweeps, converged): G = V diag(lam) V^H;
+    `sweeps` counts every sweep made, the last, all-skipped one included."""
+    G = np.array(G, dtype=np.complex128)
+    nz = G.shape[0]
+    V = np.eye(nz, dtype=np.complex128)
+    others = np.arange(nz)
+    for sweep in range(1, MAX_SWEEPS + 1):
+        rotated = False
+        for p in range(nz - 1):
+            for q in range(p + 1, nz):
+                g = G[p, q]
+                app, aqq = G[p, p].real, G[q, q].real
+                m2 = g.real * g.real + g.imag * g.imag
+                if m2 <= _EPS * _EPS * abs(app * aqq):
+                    continue
+                rotated = True
+                absg = np.sqrt(m2)
+                w = complex(g.real / absg, g.imag / absg)
+                tau = (aqq - app) / (2.0 * absg)
+                t = (1.0 if tau >= 0.0 else -1.0) / (abs(tau) + np.sqrt(1.0 + tau * tau))
+                c = 1.0 / np.sqrt(1.0 + t * t)
+                sw = complex(t * c * w.real, t * c * w.imag)
+                k = others[(others != p) & (others != q)]
+                gp, gq = G[k, p].copy(), G[k, q].copy()
+                G[k, p] = c * gp - sw.conjugate() * gq
+                G[k, q] = sw * gp + c * gq
+                G[p, k] = G[k, p].conj()
+                G[q, k] = G[k, q].conj()
+                G[p, p] = app - t * absg
+                G[q, q] = aqq + t * absg
+                G[p, q] = G[q, p] = 0.0
+                vp, vq = V[:, p].copy(), V[:, q].copy()
+                V[:, p] = c * vp - sw.conjugate() * vq
+                V[:, q] = sw * vp + c * vq
+        if not rotated:
+            return G.diagonal().real.copy(), V, sweep, True
+    return G.diagonal().real.copy(), V, MAX_SWEEPS, False
+
+
+def singular_values(V, Z):
+    """s_k = sqrt(sum over the snapshots, in their order, of |v_k^H z|^2), descending: the Rayleigh quotients v_k^H G v_k taken
+    from the data themselves, every term non-negative (the inner products summed over the rows of V in ascending index)."""
+    nz, S = Z.shape
+    acc = np.zeros(nz)
+    for s in range(S):
+        d = np.zeros(nz, dtype=np.complex128)
+        for j in range(nz):
+            d += V[j, :].conj() * Z[j, s]
+        acc += d.real * d.real + d.imag * d.imag
+    return np.sqrt(np.sort(acc)[::-1])
+
+
+def truncated_models(lam, V, C, rconds):
+    """A [R, n, nz] and rank [R] from the spectrum: the sums run over the kept eigenpairs in ascending index."""
+    W = np.zeros(C.shape, dtype=np.complex128)
+    for j in range(V.shape[0]):
+        W += np.outer(C[:, j], V[j, :])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        Wl = W * (1.0 / lam)[None, :]
+    lmax = lam.max()
+    A = np.zeros((len(rconds),) + C.shape, dtype=np.complex128)
+    rank = np.zeros(len(rconds), dtype=np.int32)
+    for r, rc in enumerate(rconds):
+        keep = lam > (rc * rc) * lmax
+        rank[r] = int(keep.sum())
+        for k in np.nonzero(keep)[0]:
+            A[r] += np.outer(Wl[:, k], V[:, k].conj())
+    return A, rank
+
+
+def _check(xs, us, order, rcond, u_scale):
+    """Shapes and values of a fit call; returns (xs [B, E, N + 1, n], us [B|1, E, N, m], u_per, u_scale, rconds, scalar_rcond)."""
+    order = int(order)
+    if order < 1:
+        raise ValueError("order must be at least 1, got %d" % order)
+    xs = np.ascontiguousarray(xs, dtype=np.complex128)
+    if xs.ndim == 3:
+        xs = xs[:, None]
+    if xs.ndim != 4 or min(xs.shape) < 1 or xs.shape[2] < 2:
+        raise ValueError("xs must be [B, N + 1, n] or [B, E, N + 1, n] with N >= 1, got shape %s" % (xs.shape,))
+    B, E, N1, n = xs.shape
+    N = N1 - 1
+    us = np.ascontiguousarray(us, dtype=np.float64)
+    if us.ndim == 2:
+        us = us[None, None]
+    elif us.ndim == 3:                      # [E, N, m] shared by the ensemble, or - a single experiment - [B, N, m]
+        us = us[None] if (E > 1 or us.shape[0] != B) else us[:, None]
+    if us.ndim != 4 or us.shape[0] not in (1, B) or us.shape[1:3] != (E, N) or us.shape[3] < 1:
+        raise ValueError("us must be [N, m], [E, N, m] (one set for the ensemble) or [B, E, N, m] with B = %d, E = %d, N = %d, "
+                         "got shape %s" % (B, E, N, us.shape))
+    m = us.shape[3]
+    u_per = 1 if (us.shape[0] == B and B > 1) else 0
+    if u_scale is not None:
+        u_scale = np.ascontiguousarray(u_scale, dtype=np.float64)
+        if u_scale.shape != (B, m):
+            raise ValueError("u_scale must be [B, m] = (%d, %d), got %s" % (B, m, u_scale.shape))
+    rc = np.asarray(rcond, dtype=np.float64)
+    scalar = rc.ndim == 0
+    rconds = np.ascontiguousarray(rc.reshape(-1) if rc.ndim <= 1 else rc)
+    if rconds.ndim != 1 or not 1 <= rconds.shape[0] <= MAX_RCONDS:
+        raise ValueError("rcond must be a scalar or a 1-D array of 1 to %d values, got shape %s" % (MAX_RCONDS, rc.shape))
+    if not np.all((rconds >= RCOND_MIN) & (rconds < 1.0)):
+        raise ValueError("rcond must lie in [%g, 1): below that the cut-off is in the Gram matrix's rounding floor (use the host "
+                         "DiscrepDMDc.from_data), got %s" % (RCOND_MIN, rconds))
+    return xs, us, u_per, u_scale, rconds, scalar, order
+
+
+def _result(models, rank, svals, status, scalar):
+    return {"models": models[0] if scalar else models, "rank": rank[0] if scalar else rank, "svals": svals, "status": status}
+
+
+def dmdc_fit_reference(xs, us, order, rcond, u_scale=None):
+    """The definition above in NumPy, member by member.  Arguments and result as dmdc_fit_batch, plus "sweeps" [B]."""
+    xs, us, u_per, u_scale, rconds, scalar, order = _check(xs, us, order, rcond, u_scale)
+    B, E, N1, n = xs.shape
+    nz = n * size_of_library(order, us.shape[3])
+    R = rconds.shape[0]
+    models = np.zeros((R, B, n, nz), dtype=np.complex128)
+    rank = np.zeros((R, B), dtype=np.int32)
+    svals = np.zeros((B, nz))
+    status = np.zeros(B, dtype=np.int32)
+    sweeps = np.zeros(B, dtype=np.int32)
+    for b in range(B):
+        u = us[b if u_per else 0]
+        if u_scale is not None:
+            u = u_scale[b] * u
+        with np.errstate(all="ignore"):
+            Z, Y = stack_snapshots(xs[b], u, order)
+            G, C = gram(Z, Y)
+        if not (np.all(np.isfinite(G)) and np.all(np.isfinite(C))):
+            status[b] = 3
+            continue
+        lam, V, sweeps[b], converged = jacobi_hermitian(G)
+        status[b] = 0 if converged else 1
+        models[:, b], rank[:, b] = truncated_models(lam, V, C, rconds)
+        svals[b] = singular_values(V, Z)
+    out = _result(models, rank, svals, status, scalar)
+    out["sweeps"] = sweeps
+    return out
+
+
+def dmdc_fit_batch(xs, us, order, rcond, u_scale=None):
+    """Fit B DMDc models on the device in one launch.
+
+    xs [B, N + 1, n] or [B, E, N + 1, n] complex: E experiments of N steps per member; us [N, m] / [E, N, m] (shared by the
+    ensemble), [B, N, m] (E = 1) or [B, E, N, m]; u_scale [B, m]: member b saw u_scale[b] * us; rcond a scalar or up to 16 values
+    in [1e-7, 1).  Returns a dict: "models" [R, B, n, n (1 + P)] ([B, n, n (1 + P)] for a scalar rcond) in the layout every other
+    entry point takes, "rank" [R, B] ([B]), "svals" [B, nz] (the singular values of the stacked data, descending) and "status" [B]
+    (0 ok, 1 the eigen-iteration hit its cap, 3 non-finite data: zero models, rank 0)."""
+    xs, us, u_per, u_scale, rconds, scalar, order = _check(xs, us, order, rcond, u_scale)
+    B, E, N1, n = xs.shape
+    m = us.shape[3]
+    nz = n * size_of_library(order, m)
+    R = rconds.shape[0]
+    models = np.empty((R, B, n, nz), dtype=np.complex128)
+    rank = np.empty((R, B), dtype=np.int32)
+    svals = np.empty((B, nz), dtype=np.float64)
+    status = np.empty(B, dtype=np.int32)
+    dp, ip = _lib._dp, _lib._ip
+    L = _lib.lib()
+    _lib.check(L.m4q_dmdc_fit_batch(B, n, m, order, E, N1 - 1, xs.ctypes.data_as(dp), us.ctypes.data_as(dp), u_per,
+                                    None if u_scale is None else u_scale.ctypes.data_as(dp), rconds.ctypes.data_as(dp), R,
+                                    models.ctypes.data_as(dp), rank.ctypes.data_as(ip), svals.ctypes.data_as(dp),
+                                    status.ctypes.data_as(ip)))
+    return _result(models, rank, svals, status, scalar)
+
+
+def prediction_losses(xs, models, us, order, u_scale=None):
+    """The reference's training loss of every (rcond, member): the spectral norm of X2 - X2_predict, the model rolled from the
+    experiment's first state along its controls, summed over the experiments.  xs [B, E, N + 1, n], models [R, B, n, nz],
+    us [B|1, E, N, m] -> [R, B].  One model_rollout_batch(keep="all") per rcond and experiment; the norms on the host."""
+    R, B = models.shape[:2]
+    E = xs.shape[1]
+    losses = np.zeros((R, B))
+    for r in range(R):
+        for e in range(E):
+            pred = model_rollout_batch(xs[:, e, 0], us[:, e] if us.shape[0] == B and B > 1 else us[0, e], models[r], order,
+                                       u_scale=u_scale, keep="all")["xs"]
+            diff = xs[:, e, 1:] - pred[:, 1:]
+            losses[r] += np.linalg.norm(diff, 2, axis=(1, 2))
+    return losses
+
+
+def train_models_batch(xs, us, order, rconds=np.logspace(-6, -1, 10), u_scale=None):
+    """The reference's hyper-parameter search (its tests/util_training.train_model) for an ensemble: one fit call covers all
+    rconds, every candidate is rolled along the training controls, and each member keeps the model that loses least (the first
+    of equals, as the reference's `loss < smallest_loss`).  Returns a dict: "models" [B, n, nz], "rcond" [B], "index" [B] (into
+    rconds), "losses" [R, B], "status" [B]."""
+    xs4, us4, _, u_scale, rconds, _, order = _check(xs, us, order, np.atleast_1d(rconds), u_scale)
+    fit = dmdc_fit_batch(xs4, us4, order, rconds, u_scale)
+    losses = prediction_losses(xs4, fit["models"], us4, order, u_scale)
+    finite = np.where(np.isfinite(losses), losses, np.inf)
+    index = np.argmin(finite, axis=0)
+    members = np.arange(xs4.shape[0])
+    return {"models": np.ascontiguousarray(fit["models"][index, members]), "rcond": rconds[index], "index": index,
+            "losses": losses, "status": fit["status"]}
