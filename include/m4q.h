@@ -225,6 +225,30 @@ M4Q_API int m4q_dmdc_fit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t 
                        const double* u, int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R,
                        double* models, int32_t* ranks, double* svals, int32_t* status);
 
+/* Recursive DMDc updates for an ensemble in ONE launch: OnlineDMDc.fit_iteration (model.py:216-313, recursive least squares with a
+ * forgetting factor) fed with every snapshot of B members - what mpc(..., streaming=True) does to its model, for an ensemble.
+ * mpc4quantum_amd/online.py (online_dmdc_reference) is the definition, in NumPy, in the kernel's order of operations.
+ * The snapshots are m4q_dmdc_fit_batch's: xs [B][E][N+1][n] c, u [B|1][E][N][m] r, u_scale [B][m] r or NULL, z = [x_t ; lift(u_t) (x) x_t],
+ * y = x_{t+1}, e outer, t inner; counts [B] or NULL: member b takes only t < counts[b] of every experiment (0 <= counts[b] <= N).
+ * State: A [n][nz] from A0 [B|1][n][nz] c, P [nz][nz] from P0 [B|1][nz][nz] c or, with P0 NULL, alpha I (alpha > 0);
+ * discount [B|1] r, each in (0, 1].  One update, sums in ascending index:
+ *   Pz = P z;  w = Pz (M4Q_ONLINE_HERMITIAN: w_j = sum_i conj(z_i) P[i][j]);  gamma = 1 / (1 + sum_j w_j z_j);  r = y - A z;
+ *   A[i][j] += (gamma r_i) w_j;  P[i][j] = (P[i][j] - (gamma Pz_i) w_j) * (1 / discount), the reciprocal formed once per member.
+ * -> models [B][n][nz] c (the layout every other entry point takes); P [B][nz][nz] c or NULL; hist [E N / hist_every][B][n][nz] c
+ * or NULL: A after updates hist_every, 2 hist_every, ... (written only when hist_every > 0; records a member does not reach are
+ * zero); innov [B][E N] r or NULL: sum_i |r_i|^2 of each snapshot before its update, at e N + t (zero beyond counts);
+ * status [B]: 0 ok, 3 a snapshot taken, the final A or the final P holds a non-finite entry (zero A, P and hist).
+ * M4Q_E_BADARG: B, E or N < 1, hist_every < 0, flags with unknown bits, a missing xs, u, A0, discount, models or status, neither P0
+ * nor alpha > 0, a discount outside (0, 1] (or NaN), a count outside [0, N].
+ * M4Q_E_UNSUPPORTED: no compiled shape, a plant-only shape, nz > 64 - (16, 1, 4), nz = 80.  Arguments are checked before the
+ * device is asked for. */
+#define M4Q_ONLINE_HERMITIAN 1
+M4Q_API int m4q_online_dmdc_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs,
+                       const double* u, int32_t u_per_instance, const double* u_scale, const int32_t* counts, const double* A0,
+                       int32_t A0_per_instance, const double* P0, int32_t P0_per_instance, double alpha, const double* discount,
+                       int32_t discount_per_instance, int32_t flags, int32_t hist_every, double* models, double* P, double* hist,
+                       double* innov, int32_t* status);
+
 /* replaces the whole mpc() loop body (mpc.py:161-292) for B closed loops, all n_steps in one launch.
  * models [B|1][n][n(1+P)] c, x0 [B][n] c, X_targ [B|1][cols][n] c, U_targ [B|1][cols][m] r,
  * Q, Qf [n][n] c, R [m][m] c, op0/ops as in m4q_plant_step_batch

@@ -23,6 +23,7 @@ OPT_NO_SG = 16
 PLANT_NONE, PLANT_HAMILTONIAN, PLANT_GENERATOR, PLANT_PROCESS = 0, 1, 2, 3
 EXIT_PREV, EXIT_NEXT, EXIT_BELOW, EXIT_ABOVE = 1, 2, 4, 8
 NOISE_IID, NOISE_HERMITIAN = 1, 2
+ONLINE_HERMITIAN = 1
 E_UNSUPPORTED, E_BADARG, E_NODEVICE, E_TIMEOUT, E_COMM = -1001, -1002, -1003, -1004, -1005
 UNIQUE_ID_BYTES = 128
 
@@ -69,6 +70,8 @@ PROTOTYPES = {
     "m4q_model_rollout_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _i32, _dp,
                                           _i32, _dp]),
     "m4q_dmdc_fit_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _ip]),
+    "m4q_online_dmdc_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _i32, _dp, _i32, C.c_double,
+                                        _dp, _i32, _i32, _i32, _dp, _dp, _dp, _dp, _ip]),
     "m4q_mpc_batch": (C.c_int, [C.POINTER(Problem), _i32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
                                 _ip, _ip]),
     "m4q_session_create": (C.c_int, [C.POINTER(Problem), _i32, _i32, C.POINTER(_vp)]),

@@ -148,6 +148,25 @@ struct FitArgs {
   M4Q_P(int) status;                               // [B]: 0 ok, 1 the Jacobi iteration hit its cap, 3 non-finite data
 };
 
+// m4q_online_dmdc_batch: OnlineDMDc.fit_iteration for every snapshot of B members (m4q_online.h; online.py is the definition).
+// The snapshots are FitArgs'; member b takes the first counts[b] steps of each experiment (N when counts is null).
+struct OnlineArgs {
+  int B, E, N, hist_every;
+  double alpha;                                    // P0 = alpha I when P0 is null
+  M4Q_P(const cplx) xs;                            // [B][E][N + 1][n]
+  M4Q_P(const double) u; long u_stride;            // [B|1][E][N][m] (u_stride E N m or 0)
+  M4Q_P(const double) u_scale;                     // [B][m] or null
+  M4Q_P(const int) counts;                         // [B] or null
+  M4Q_P(const cplx) A0; long A0_stride;            // [B|1][n][nz]
+  M4Q_P(const cplx) P0; long P0_stride;            // [B|1][nz][nz] or null
+  M4Q_P(const double) discount; long discount_stride;     // [B|1]
+  M4Q_P(cplx) models;                              // [B][n][nz]
+  M4Q_P(cplx) P;                                   // [B][nz][nz] or null
+  M4Q_P(cplx) hist;                                // [E N / hist_every][B][n][nz]; null when hist_every is 0
+  M4Q_P(double) innov;                             // [B][E N] or null
+  M4Q_P(int) status;                               // [B]: 0 ok, 3 non-finite data or state
+};
+
 // noise.py's sample() for B members at one state_index (m4q_noise_sample_batch): out [B][n] complex
 struct NoiseArgs {
   int B, mode;
@@ -176,6 +195,8 @@ struct ShapeOps {
   int (*launch_model_rollout)(const RollArgs&, hipStream_t);      // (every shape with a model)
   int fit_lds_bytes;                                              // dynamic LDS of dmdc_fit_kernel; 0: the shape has none (no model, or
   int (*launch_fit)(const FitArgs&, hipStream_t);                 // its layout does not fit one workgroup's LDS)
+  int online_lds_bytes;                                           // ... of online_dmdc_kernel, likewise
+  int (*launch_online)(const OnlineArgs&, int hermitian, hipStream_t);
 };
 
 }  // namespace m4q

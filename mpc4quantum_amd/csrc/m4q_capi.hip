@@ -5,6 +5,7 @@
 #include <rccl/rccl.h>      // types and prototypes only: librccl.so is loaded with dlopen on first use (a CPU-only import never needs it)
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <complex>
 #include <cstdlib>
@@ -1166,6 +1167,54 @@ int m4q_dmdc_fit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, i
   a.status = st.out<int>(status, B);
   if (st.error()) return st.error();
   return st.finish(sh->launch_fit(a, nullptr), "DMDc fit");
+}
+
+int m4q_online_dmdc_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs, const double* u,
+                          int32_t u_per_instance, const double* u_scale, const int32_t* counts, const double* A0, int32_t A0_per_instance,
+                          const double* P0, int32_t P0_per_instance, double alpha, const double* discount, int32_t discount_per_instance,
+                          int32_t flags, int32_t hist_every, double* models, double* P, double* hist, double* innov, int32_t* status) {
+  const m4q::ShapeOps* sh = find_shape(dim_x, dim_u, order);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no model kernel for dim_x=%d dim_u=%d order=%d", dim_x, dim_u, order);
+  if (sh->online_lds_bytes == 0)
+    return fail(M4Q_E_UNSUPPORTED, "m4q_online_dmdc_batch: the state of dim_x=%d dim_u=%d order=%d (nz = %d) does not fit one wavefront "
+                "and one workgroup's LDS; update such models on the host (OnlineDMDc.fit_iteration)", dim_x, dim_u, order,
+                dim_x * (1 + sh->np));
+  if (B < 1 || E < 1 || N < 1) return fail(M4Q_E_BADARG, "m4q_online_dmdc_batch: B, E and N must be at least 1 (got %d, %d, %d)", B, E, N);
+  if (hist_every < 0) return fail(M4Q_E_BADARG, "m4q_online_dmdc_batch: hist_every must not be negative, got %d", hist_every);
+  if (flags & ~M4Q_ONLINE_HERMITIAN) return fail(M4Q_E_BADARG, "m4q_online_dmdc_batch: flags has bits outside M4Q_ONLINE_HERMITIAN (0x%x)", flags);
+  if (!xs || !u || !A0 || !discount || !models || !status)
+    return fail(M4Q_E_BADARG, "m4q_online_dmdc_batch: xs, u, A0, discount, models and status are required");
+  if (!P0 && !(alpha > 0.0 && alpha <= DBL_MAX))
+    return fail(M4Q_E_BADARG, "m4q_online_dmdc_batch: without P0, alpha must be positive and finite (P0 = alpha I), got %g", alpha);
+  for (int b = 0; b < (discount_per_instance ? B : 1); ++b)
+    if (!(discount[b] > 0.0 && discount[b] <= 1.0))
+      return fail(M4Q_E_BADARG, "m4q_online_dmdc_batch: discount[%d] = %g is outside (0, 1]", b, discount[b]);
+  if (counts)
+    for (int b = 0; b < B; ++b)
+      if (counts[b] < 0 || counts[b] > N)
+        return fail(M4Q_E_BADARG, "m4q_online_dmdc_batch: counts[%d] = %d is outside [0, N = %d]", b, counts[b], N);
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, nz = n * (1 + (size_t)sh->np);
+  const Extent eu(B, u_per_instance, (size_t)E * N * m), ea(B, A0_per_instance, n * nz), ep(B, P0_per_instance, nz * nz),
+      ed(B, discount_per_instance, 1);
+  Stage st;
+  m4q::OnlineArgs a{};
+  a.B = B; a.E = E; a.N = N; a.alpha = alpha;
+  a.xs = st.in<cplx>(xs, (size_t)B * E * ((size_t)N + 1) * n);
+  a.u = st.in<double>(u, eu.count); a.u_stride = eu.stride;
+  if (u_scale) a.u_scale = st.in<double>(u_scale, (size_t)B * m);
+  if (counts) a.counts = st.in<int>(counts, B);
+  a.A0 = st.in<cplx>(A0, ea.count); a.A0_stride = ea.stride;
+  if (P0) { a.P0 = st.in<cplx>(P0, ep.count); a.P0_stride = ep.stride; }
+  a.discount = st.in<double>(discount, ed.count); a.discount_stride = ed.stride;
+  a.models = st.out<cplx>(models, (size_t)B * n * nz);
+  if (P) a.P = st.out<cplx>(P, (size_t)B * nz * nz);
+  const size_t H = hist_every > 0 ? ((size_t)E * N) / hist_every : 0;
+  if (hist && H > 0) { a.hist_every = hist_every; a.hist = st.out<cplx>(hist, H * B * n * nz); }
+  if (innov) a.innov = st.out<double>(innov, (size_t)B * E * N);
+  a.status = st.out<int>(status, B);
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_online(a, (flags & M4Q_ONLINE_HERMITIAN) != 0, nullptr), "online DMDc");
 }
 
 int m4q_mpc_batch(const m4q_problem* p, int32_t B, const double* models, const double* x0, const double* X_targ,

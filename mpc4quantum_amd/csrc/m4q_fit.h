@@ -40,10 +40,10 @@ __device__ __forceinline__ void rotate_pair(double c, cplx sw, cplx a, cplx b, c
 
 // The member's snapshots in their order, e outer, t inner: for each, z = [x_t ; lift(u_t) (x) x_t] goes to Z and x_{t+1} to XN in
 // LDS, then body(z) runs with lane l holding z_l.  x_{t+1} (needed for XN now, for z next) and x_{t+2}, u_{t+1} are in flight
-// while snapshot t is worked on.
-template <int NX, int NU, int ORDER, class F>
-__device__ __forceinline__ void fit_stream(const FitArgs& a, long b, cplx* lds, int lane, F body) {
-  using L = FitLayout<NX, NU, ORDER>;
+// while snapshot t is worked on.  Shared by the kernels that read training data (dmdc_fit_kernel, online_dmdc_kernel): L names
+// where Z [NZ] and XN [NX] live in LDS, Args holds xs [B][E][N + 1][n], u, u_stride, u_scale, E and N.
+template <int NX, int NU, int ORDER, class L = FitLayout<NX, NU, ORDER>, class Args = FitArgs, class F>
+__device__ __forceinline__ void fit_stream(const Args& a, long b, cplx* lds, int lane, F body) {
   constexpr int NZ = L::NZ, NP = PowTab<NU, ORDER>::NP;
   cplx* Z = lds + L::Z;
   cplx* XN = lds + L::XN;

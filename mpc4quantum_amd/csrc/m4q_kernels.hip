@@ -7,6 +7,7 @@
 #include "m4q_args.h"
 #include "m4q_mpc.h"
 #include "m4q_fit.h"
+#include "m4q_online.h"
 #include "m4q_noise.h"
 #include "m4q_tile3.h"
 
@@ -1357,6 +1358,26 @@ __global__ __launch_bounds__(64) void dmdc_fit_kernel(FitArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Recursive DMDc updates of B members (m4q_online_dmdc_batch; online.py: online_dmdc_reference is the definition): the frame of
+// dmdc_fit_kernel, the model A and the inverse Gram matrix P in dynamic LDS from the first snapshot to the last (OnlineLayout,
+// m4q_online.h).  HERM_: the conjugated form.
+// ---------------------------------------------------------------------------------------------
+template <int NX_, int NU_, int ORDER_, bool HERM_>
+__global__ __launch_bounds__(64) void online_dmdc_kernel(OnlineArgs a) {
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const int lane = threadIdx.x;
+  for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
+    wave_sync();                                   // the previous member's reads are done
+    online_load<NX_, NU_, ORDER_>(a, b, lds, lane);
+    const int steps = a.counts ? gld(a.counts, b) : a.N;
+    const double inv_discount = 1.0 / gld(a.discount, b * a.discount_stride);
+    const bool data_ok = online_updates<NX_, NU_, ORDER_, HERM_>(a, b, steps, inv_discount, lds, lane);
+    wave_sync();
+    online_store<NX_, NU_, ORDER_>(a, b, steps, data_ok, lds, lane);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // quad_program for B explicit linear time-varying problems (optimize.py:12-60 / lqr.py:14-79)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) M4Q_OCC void qp_kernel(QpArgs a) {
@@ -1747,9 +1768,30 @@ struct FitLaunch<true, N_> {
 constexpr bool FIT_FITS = FitLayout<NX, NU, ORDER>::FITS;
 constexpr int FIT_LDS = FIT_FITS ? (int)FitLayout<NX, NU, ORDER>::BYTES : 0;
 static int launch_fit(const FitArgs& a, hipStream_t s) { return FitLaunch<FIT_FITS>::run(a, s); }
+template <bool FITS, int N_ = NX>
+struct OnlineLaunch {
+  static int run(const OnlineArgs&, int, hipStream_t) { return UNBUILT; }
+};
+template <int N_>
+struct OnlineLaunch<true, N_> {
+  template <bool HERM>
+  static int go(const OnlineArgs& a, hipStream_t s) {
+    constexpr size_t lds = OnlineLayout<N_, NU, ORDER>::BYTES;
+    int rc = prep_lds(online_dmdc_kernel<N_, NU, ORDER, HERM>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((online_dmdc_kernel<N_, NU, ORDER, HERM>), dim3(a.B < 4096 ? a.B : 4096), dim3(64), lds, s, a);
+    return -(int)hipGetLastError();
+  }
+  static int run(const OnlineArgs& a, int hermitian, hipStream_t s) { return hermitian ? go<true>(a, s) : go<false>(a, s); }
+};
+constexpr bool ONLINE_FITS = OnlineLayout<NX, NU, ORDER>::FITS;
+constexpr int ONLINE_LDS = ONLINE_FITS ? (int)OnlineLayout<NX, NU, ORDER>::BYTES : 0;
+static int launch_online(const OnlineArgs& a, int hermitian, hipStream_t s) { return OnlineLaunch<ONLINE_FITS>::run(a, hermitian, s); }
 #else
 constexpr int FIT_LDS = 0;
 static int launch_fit(const FitArgs&, hipStream_t) { return UNBUILT; }
+constexpr int ONLINE_LDS = 0;
+static int launch_online(const OnlineArgs&, int, hipStream_t) { return UNBUILT; }
 static int launch_linearize(const LinArgs&, hipStream_t) { return UNBUILT; }
 static int launch_qp(const QpArgs&, hipStream_t) { return UNBUILT; }
 static int launch_model_rollout(const RollArgs&, hipStream_t) { return UNBUILT; }
@@ -1818,7 +1860,8 @@ static const ShapeOps* shape_ops() {
   constexpr int plant_only = 0;
 #endif
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
-                               launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit};
+                               launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
+                               ONLINE_LDS, launch_online};
   return &ops;
 }
 

@@ -2,8 +2,11 @@
 
 `DMDc` is the read-only container the MPC loop needs (`get_discrete`, `predict`).  `DiscrepDMDc` and `OnlineDMDc`
 are the two streaming refits `mpc(..., streaming=True)` feeds through `fit_iteration` (mpc.py:281-285).  They are
-host-side NumPy on (n x n(1+P)) matrices, as in the reference: the refit is outside the accelerated path (the loop
-linearises the model it was handed at entry, mpc.py:156, quirk Q6), so nothing here touches the GPU."""
+host-side NumPy on (n x n(1+P)) matrices, as in the reference, one model at a time: the loop linearises the model it
+was handed at entry (mpc.py:156, quirk Q6), so the refit never feeds back into a run.  For an ensemble the recursion of
+`OnlineDMDc` also exists on the device (online.py: online_dmdc_batch, stream_models_batch, one launch for all members);
+`OnlineDMDc.from_batch` turns one member of its result back into the host object.  `DiscrepDMDc.fit_iteration`, a
+pseudo-inverse of a growing stack at every step, exists only here."""
 import numpy as np
 
 
@@ -148,6 +151,14 @@ class OnlineDMDc(DMDc, _History):
         Z, dim_u = _stacked_inputs(X, U)
         P0 = np.linalg.pinv(Z @ Z.T)
         return cls(Y.shape[0], X.shape[0], dim_u, P0, Y @ Z.T @ P0, Y=Y, X=X, U=U)
+
+    @classmethod
+    def from_batch(cls, result, b):
+        """Member b of an online_dmdc_batch / stream_models_batch result (online.py) as a host object, which continues with
+        fit_iteration here.  `discount` is the class default: set it to what the batch call used."""
+        A, P = np.array(result["models"][b]), np.array(result["P"][b])
+        n, nz = A.shape
+        return cls(n, n, nz - n, P, A)
 
     def fit_iteration(self, next_y, next_x, next_u=np.array([])):
         y = np.reshape(next_y, (-1, 1))
