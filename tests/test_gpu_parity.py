@@ -301,7 +301,7 @@ def test_qp_mode_vs_independent_kkt_at_the_headline_horizon(r_scale):
 def _scenario_qp(config, order, T, Bn, seed, amp):
     """Linearisation of a reference scenario's model along a perturbed guess: a Hermiticity-preserving LTV problem."""
     rng = np.random.default_rng(seed)
-    p = configs.build(config, batch=Bn, order=order, horizon=T)
+    p = _build_cfg(config, batch=Bn, order=order, horizon=T)          # config: a BASELINE number or a key of _VARIANTS
     n, m = p["x0"].shape[1], p["U_targ"].shape[0]
     A, Bm, D, x0 = [], [], [], []
     for b in range(Bn):
@@ -317,14 +317,49 @@ def _scenario_qp(config, order, T, Bn, seed, amp):
             np.stack(D), p["sat"])
 
 
+def _condensed_gradient(x0, Xb, Ub, Qs, Rs, A, Bm, D, U):
+    """Half the gradient of the condensed objective sum_t e_t^H Q_t e_t + (u_t - ubar_t)^T R_t (u_t - ubar_t) with respect to the
+    controls U [T, m] of ONE member, in plain fp64: the states rolled out from U, then the adjoint recursion
+    lambda_T = Q_T e_T, g_t = R_t (u_t - ubar_t) + Re B_t^H lambda_{t+1}, lambda_t = Q_t e_t + A_t^H lambda_{t+1}."""
+    T = U.shape[0]
+    X = [np.asarray(x0, dtype=complex)]
+    for t in range(T):
+        X.append(A[t] @ X[t] + Bm[t] @ U[t] + D[t])
+    lam = Qs[T] @ (X[T] - Xb[T])
+    g = np.zeros(U.shape)
+    for t in range(T - 1, -1, -1):
+        g[t] = (Rs[t].real @ (U[t] - Ub[t])) + (Bm[t].conj().T @ lam).real
+        lam = Qs[t] @ (X[t] - Xb[t]) + A[t].conj().T @ lam
+    return g
+
+
+def _kkt_residual(g, U, lo, hi):
+    """The largest violation of the box QP's optimality conditions at a feasible U: -g where U sits on its lower bound, g where
+    it sits on its upper bound (a multiplier of the wrong sign), |g| elsewhere.  "On a bound" is within 1e-12 of the width of
+    the box: a control that close to its bound with a multiplier of the right sign gains nothing by moving onto it."""
+    at = 1e-12 * np.maximum(hi - lo, np.abs(hi))
+    on_lo, on_hi = U <= lo + at, U >= hi - at
+    r = np.where(on_lo & on_hi, 0.0, np.where(on_lo, np.maximum(-g, 0.0), np.where(on_hi, np.maximum(g, 0.0), np.abs(g))))
+    return float(r.max())
+
+
 @pytest.mark.parametrize("config,order,T,sat_scale,du", [(1, 1, 10, 1.0, None), (1, 2, 25, 0.3, None), (3, 2, 40, 0.3, None),
-                                                          (3, 2, 20, 0.3, 0.05), (3, 1, 12, 1e3, None), (4, 1, 20, 0.3, None)])
-def test_exact_box_qp_vs_bvls_oracle(config, order, T, sat_scale, du):
+                                                          (3, 2, 20, 0.3, 0.05), (3, 1, 12, 1e3, None), (4, 1, 20, 0.3, None),
+                                                          ("5w", 1, 80, 0.3, None), ("5w", 1, 80, 0.3, 0.05), (5, 2, 80, 0.3, None)])
+def test_exact_box_qp_vs_bvls_oracle(config, order, T, sat_scale, du, record_property):
     """M4Q_QP_EXACT_BOX: the box-constrained QP of optimize.py:27-54 solved to optimality on the device (projected Newton
     on the Riccati factorisation) against an independent solver of the same statement (scipy BVLS on the condensed
-    problem) - tolerance 1e-9 of the bound on the controls, 1e-11 relative on the objective."""
+    problem) - tolerance 1e-9 of the bound on the controls, 1e-11 relative on the objective.  The last three rows are at
+    BASELINE config 5's horizon, T = 80 (20 blocks of the pinned tile sweep, 160 controls in the working set): the
+    well-conditioned variant "5w" with and without the du band, and config 5's order-2 model.
+    Every row is also certified without BVLS: the device's U is feasible (the first column inside the du band where there is
+    one) and satisfies the KKT sign conditions of the box QP on the gradient of the condensed objective (_condensed_gradient,
+    plain NumPy).  The tolerance is not chosen here: the same residual is computed for BVLS's own solution of that QP, and the
+    device's may be at most ten times that (another summation order) plus 1e-12 of the largest gradient entry at U = ubar.
+    A row whose BVLS residual exceeds 1e-8 of that scale would be too ill-conditioned to certify anything; none is."""
     Bn = 5
-    x0, Xb, Ub, Qs, Rs, A, Bm, D, sat = _scenario_qp(config, order, T, Bn, 40 + config, 0.3)
+    base = _VARIANTS[config][0] if config in _VARIANTS else config
+    x0, Xb, Ub, Qs, Rs, A, Bm, D, sat = _scenario_qp(config, order, T, Bn, 40 + base, 0.3)
     sat = sat * sat_scale
     up = 0.02 * np.arange(Bn * Ub.shape[2]).reshape(Bn, -1) if du else None
     X, U, cost, _ = m4q.quad_program_batch(x0, Xb, Ub, Qs, Rs, A, Bm, D, up, sat, du, exact=True)
@@ -332,6 +367,7 @@ def test_exact_box_qp_vs_bvls_oracle(config, order, T, sat_scale, du):
     assert np.abs(U).max() <= sat
     assert np.all(cost <= costc * (1 + 1e-14))                    # never worse than the clipped rollout it starts from
     active = 0
+    worst = [0.0, 0.0, 0.0]                                       # KKT residuals of the device and of BVLS, the gradient scale
     for b in range(Bn):
         Xe, Ue, ce = orc.exact_quad_program(x0[b], Xb[0].T, Ub[0].T, list(Qs), list(Rs), list(A[b]), list(Bm[b]), list(D[b]),
                                             None if up is None else up[b], sat, du)
@@ -341,6 +377,21 @@ def test_exact_box_qp_vs_bvls_oracle(config, order, T, sat_scale, du):
         active += int((np.abs(Ue) >= sat * (1 - 1e-12)).sum())
         if du:
             assert np.all(np.abs(U[b, 0] - up[b]) <= du * (1 + 1e-14))
+        # optimality, independent of BVLS's answer: the KKT signs of the box QP on the fp64 gradient at the device's U
+        lo, hi = np.full(U[b].shape, -sat), np.full(U[b].shape, sat)
+        if du:
+            lo[0], hi[0] = np.maximum(lo[0], up[b] - du), np.minimum(hi[0], up[b] + du)
+        prob = (x0[b], Xb[0], Ub[0], Qs, Rs, A[b], Bm[b], D[b])
+        scale = np.abs(_condensed_gradient(*prob, Ub[0].astype(float))).max()
+        assert np.all(U[b] >= lo - 1e-14 * np.abs(lo)) and np.all(U[b] <= hi + 1e-14 * np.abs(hi))
+        r_dev = _kkt_residual(_condensed_gradient(*prob, U[b]), U[b], lo, hi)
+        r_ref = _kkt_residual(_condensed_gradient(*prob, Ue.T), Ue.T, lo, hi)
+        worst = [max(worst[0], r_dev / scale), max(worst[1], r_ref / scale), max(worst[2], scale)]
+        assert r_ref <= 1e-8 * scale, (b, r_ref, scale)            # the row can be certified at all
+        assert r_dev <= 10 * r_ref + 1e-12 * scale, (b, r_dev, r_ref, scale)
+    record_property("kkt_residual_device_bvls_scale", worst)
+    print("exact box QP cfg %s order %d T %d du %s: KKT residual / max|g(ubar)|: device %.2e, BVLS %.2e (max|g(ubar)| %.2e)"
+          % (config, order, T, du, *worst))
     if sat_scale < 100:
         assert active > 0 and np.abs(U - Uc).max() > 1e-4 * sat   # the bounds matter in these cases
     else:
@@ -883,6 +934,155 @@ def test_closed_loop_exact_stepwise_teacher_forced(cfg, order, batch, path):
         assert len(admitted) <= ns // 4, admitted          # the sensitivity clause is for the odd step, not the rule
     finally:
         sess.close()
+
+
+# ---- the exact mode at BASELINE config 5's horizon, T = 80 ------------------------------------------------------------------------
+# (case, order, members, teacher-forced steps, paths).  The session always plans config 5's 20 steps; the order-2 case stops its
+# teacher-forced loop after 8 (the cold solve, the hard first warm steps, and the kernel's cuts at 2, 4 and 7).
+_T80_EXACT = {"5w": (1, 2, 20, ("tile", "dpp", "real9", "complex")), "5d": (1, 1, 20, ("tile", "complex")),
+              5: (2, 1, 8, ("dpp", "complex"))}
+_T80_SESSION = {"tile": ({}, "traceless-tile"), "dpp": ({"tile": False}, "traceless"), "real9": ({"traceless": False}, "real"),
+                "complex": ({"force_complex": True}, "complex")}
+
+
+@pytest.fixture(scope="module")
+def exact_t80_oracle():
+    """The oracle's exact-mode run (BVLS on every condensed box QP) of a T = 80 case, teacher-forcing trace included: computed
+    once per case and shared by all of its paths (the host solves dominate these tests; nobody modifies what this returns)."""
+    memo = {}
+
+    def get(case):
+        if case not in memo:
+            order, batch, n_tf, _ = _T80_EXACT[case]
+            p = _build_cfg(case, batch=batch, order=order)
+            assert p["horizon"] == 80 and p["n_steps"] == 20
+            n, ns = p["dim_x"], p["n_steps"]
+            xs = np.full((batch, n, ns + 1), np.nan + 0j)
+            us = np.full((batch, p["dim_u"], ns), np.nan)
+            solves = np.zeros((batch, ns), dtype=np.int32)
+            trace = []
+            for b in range(batch):
+                Am = p["models"][b if p["models"].shape[0] > 1 else 0]
+                cnt, tr = [], []
+                (x, u), _, code = orc.mpc(p["x0"][b], p["dim_u"], order, p["X_targ"], p["U_targ"],
+                                          orc.OracleClock(p["dt"], p["horizon"], ns),
+                                          orc.OracleQExperiment(p["plant_op0"][0], list(p["plant_ops"][0])),
+                                          orc.OracleDMDc(n, n, Am.shape[1] - n, Am), p["Q"], p["R"], p["Qf"], sat=p["sat"], du=p["du"],
+                                          qp_mode="exact", count=cnt, trace=tr, stop=n_tf)
+                assert code == 0 and x.shape[1] == n_tf + 1 and u.shape[1] == n_tf
+                xs[b, :, :n_tf + 1], us[b, :, :n_tf], solves[b, :n_tf] = x, u, cnt
+                trace.append(tr)
+            # the case is worth its time only while the bounds are active on what the loop applies
+            assert (np.abs(us[:, :, :n_tf]) >= p["sat"] * (1 - 1e-12)).mean() > 0.1
+            memo[case] = (p, xs, us, solves, trace)
+        return memo[case]
+    return get
+
+
+@pytest.mark.parametrize("case,path", [(c, q) for c in _T80_EXACT for q in _T80_EXACT[c][3]])
+def test_closed_loop_exact_stepwise_teacher_forced_at_t80(case, path, exact_t80_oracle, record_property):
+    """M4Q_QP_EXACT_BOX at BASELINE config 5's horizon (T = 80: 20 blocks of the pinned tile sweep, a per-row workspace twice that
+    of T = 40, 160 controls in the working set), every MPC step started from the ORACLE's state as in
+    test_closed_loop_exact_stepwise_teacher_forced: steps_done and exit codes 0, the oracle's QP-solve counts, us[k] within 1e-9
+    of the bound and xs[k+1] within 1e-9 - FIXED bounds: no case here has a sensitivity clause.
+    "5w" (anharmonicity / 8, R x 100; B = 2, all 20 steps) on the tile sweep, the DPP sweep, the d*d real coordinates and the
+    complex path; "5d" (anharmonicity / 8, controls saturating, many pinned; B = 1, all 20 steps) on tile and complex; config 5
+    itself with the order-2 model (B = 1, steps 0-7 of the 20 the session plans: no tile sweep at order 2) on DPP and complex.
+    The oracle alone, under a 1e-15 perturbation of the guess a step starts from (_oracle_exact_step_sensitivity), moves by at
+    most 7.8e-15 of sat / 1.0e-15 ("5w", all steps), 1.2e-14 / 2.7e-15 ("5d", steps 0-9) and 8.9e-15 / 1.4e-15 (order 2, steps 0-7) on
+    us[k] / xs[k+1]: below 1e-11 everywhere, so nothing is admitted."""
+    order, batch, n_tf, _ = _T80_EXACT[case]
+    p, xs, us, solves, trace = exact_t80_oracle(case)
+    kw, detail = _T80_SESSION[path]
+    ns = p["n_steps"]
+    sess = _session(p, batch, exact_qp=True, **kw)
+    worst = [0.0, 0.0]
+    try:
+        sess.load_problem(p["models"], p["x0"], p["X_targ"], p["U_targ"], p["Q"], p["R"], p["Qf"], p["plant_op0"], p["plant_ops"])
+        assert sess.path_detail() == detail
+        xs_t, us_t = np.swapaxes(xs, 1, 2), np.swapaxes(us, 1, 2)
+        _CASES_RUN.add("exact_stepwise[cfg%s-o%d-B%d-T%d-%s]" % (case, order, batch, p["horizon"], path))
+        for k in range(n_tf):
+            if k > 0:
+                st = {"xs": np.zeros_like(xs_t), "us": np.zeros_like(us_t),
+                      "x_guess": np.stack([trace[b][k][0].T for b in range(batch)]),
+                      "u_guess": np.stack([trace[b][k][1].T for b in range(batch)]),
+                      "exit_codes": np.zeros(batch, dtype=np.int32), "steps_done": np.full(batch, k, dtype=np.int32)}
+                st["xs"][:, :k + 1] = xs_t[:, :k + 1]
+                st["us"][:, :k] = us_t[:, :k]
+                sess.restore(st)
+            sess.run(k, k + 1)
+            got = sess.state()
+            assert np.all(got["steps_done"] == k + 1) and np.all(got["exit_codes"] == 0), k
+            assert np.array_equal(sess.download(_lib.F_QP_SOLVES, (batch, ns))[:, k], solves[:, k]), k
+            eu = np.abs(got["us"][:, k] - us_t[:, k]).max() / p["sat"]
+            ex = np.abs(got["xs"][:, k + 1] - xs_t[:, k + 1]).max()
+            worst = [max(worst[0], eu), max(worst[1], ex)]
+            print("exact T = 80 %s %s step %d: |du| / sat %.2e, |dx| %.2e" % (case, path, k, eu, ex))
+            assert eu <= 1e-9 and ex <= 1e-9, (k, eu, ex)
+    finally:
+        sess.close()
+        record_property("worst_du_over_sat_dx", worst)
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint64) if a.dtype.kind in "fc" else a,
+                                                                        b.view(np.uint64) if b.dtype.kind in "fc" else b)
+
+
+@pytest.mark.parametrize("path", ["tile", "complex"])
+def test_exact_one_launch_at_t80_equals_its_chain_of_steps(path, record_property):
+    """"5w" (T = 80), members 0-4 (one full wavefront of four rows and one more), exact mode, 14 steps - past the exact kernel's
+    last cut, so the one launch run(0, 14) makes all five pieces [0, 2), [2, 4), [4, 7), [7, 12), [12, 14) and hands the 80-column
+    guess from piece to piece on the device.  Against it, on the same session: 14 single-step launches, and run(0, k) + run(k, 14)
+    at and one step beside each of the cuts 2, 4, 7 and 12.  The bounds of tests/test_gpu_launch_schedule.py: identical bits on
+    the complex path; on the tile path identical solve counts, exit codes and steps, us and xs within 1e-10 at every step (a
+    launch boundary hands the guess over through the complex basis, a cut inside a launch does not).  No oracle is involved.
+    On the launch itself: no solve ends at the iteration cap, |u| <= sat, and the du band around the previous step's control."""
+    NS = 14
+    p = _build_cfg("5w", batch=5, n_steps=NS)
+    kw, detail = _T80_SESSION[path]
+
+    def snapshot(sess):
+        r = sess.results()
+        return {f: r[f] for f in ("xs", "us", "qp_solves", "exit_codes", "steps_done")}
+
+    worst = 0.0
+    sess = _session(p, 5, exact_qp=True, **kw)
+    try:
+        sess.load_problem(p["models"], p["x0"], p["X_targ"], p["U_targ"], p["Q"], p["R"], p["Qf"], p["plant_op0"], p["plant_ops"])
+        assert sess.path_detail() == detail
+        sess.run(0, NS)
+        ref = snapshot(sess)
+        n_solves, sweeps, ratio_steps, end_kkt, end_precision, end_cap = sess.qp_stats()
+        assert np.all(ref["exit_codes"] == 0) and np.all(ref["steps_done"] == NS)
+        assert n_solves == ref["qp_solves"].sum() and end_cap == 0 and end_kkt + end_precision == n_solves
+        assert np.abs(ref["us"]).max() <= p["sat"] * (1 + 1e-15)
+        assert np.abs(np.diff(ref["us"], axis=1))[:, 1:].max() <= p["du"] * (1 + 1e-12)     # steps >= 2: banded around us[step-1]
+        assert (np.abs(ref["us"]) >= p["sat"] * (1 - 1e-12)).any()                          # and the box is active in this run
+        chains = []
+        for k in range(NS):
+            sess.run(k, k + 1)
+        chains.append(("single steps", snapshot(sess)))
+        for k in (1, 2, 3, 4, 5, 6, 7, 8, 11, 12, 13):
+            sess.run(0, k)
+            sess.run(k, NS)
+            chains.append(("resumed at %d" % k, snapshot(sess)))
+    finally:
+        sess.close()
+    for what, got in chains:
+        for f in ("qp_solves", "exit_codes", "steps_done"):
+            assert np.array_equal(got[f], ref[f]), (what, f, got[f], ref[f])
+        if path == "complex":
+            assert _same_bits(got["xs"], ref["xs"]) and _same_bits(got["us"], ref["us"]), what
+        else:
+            e = max(max(rel(got["us"][:, k], ref["us"][:, k]) for k in range(NS)),
+                    max(rel(got["xs"][:, k], ref["xs"][:, k]) for k in range(NS + 1)))
+            worst = max(worst, e)
+            assert e <= 1e-10, (what, e)
+    record_property("split_max_rel", worst)
+    print("exact T = 80 5w %s: one launch against %d chains, worst relative difference %.2e" % (path, len(chains), worst))
 
 
 @pytest.mark.parametrize("path", ["complex", "real"])
@@ -1582,6 +1782,13 @@ def test_exact_qp_unconverged_solves_surface_as_exit_code_2():
     assert set(res["exit_codes"].tolist()) <= {0, 2}
     capped = res["exit_codes"] == 2
     assert np.all(res["steps_done"][capped] < p["n_steps"]) and np.all(res["steps_done"][~capped] == p["n_steps"])
+    # what was applied before a member ended, capped or not, is inside the box and the du band around the previous step's control
+    for b in range(256):
+        ub = res["us"][b][:, :res["steps_done"][b]]
+        if ub.shape[1]:
+            assert np.abs(ub).max() <= p["sat"] * (1 + 1e-15), b
+        if ub.shape[1] > 2:
+            assert np.abs(np.diff(ub, axis=1))[:, 1:].max() <= p["du"] * (1 + 1e-12), b
     # the same horizon with clipped solves (the default mode) runs through
     clip = _gpu_batch(p, np.arange(256))
     assert np.all(clip["exit_codes"] == 0)
