@@ -198,6 +198,43 @@ M4Q_API int m4q_model_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int
                             const double* W, const double* target, int32_t target_per_instance, int32_t xs_mode, double* xs,
                             int32_t q_mode, double* q);
 
+/* Control gradients of the open-loop rollouts, for B members in ONE launch: what polishing a pulse against an ensemble (robust GRAPE)
+ * needs.  mpc4quantum_amd/grad.py (plant_rollout_grad_reference, model_rollout_grad_reference, ordered_weighted_sum) is the
+ * definition, in NumPy and SciPy, in the kernels' order of operations.
+ * The arguments up to target_per_instance are the rollouts' own.  Member b sees v[t][k] = u_scale[b][k] u[t][k]; with d_t = x_t - f and
+ * q_t = Re(d_t^H W d_t) (W need not be Hermitian) the objective is J = q_N (q_mode 1) or J = sum_{t=0..N} q_t (q_mode 2).
+ * -> q [B] (q_mode 1) or [B][N+1] (q_mode 2) r, required: the forward pass is the rollouts' own step, so q equals their figure bit
+ *    for bit; grad [B][N][m] r, required: dJ_b/du[t][k], the derivative with respect to the unscaled sequence the caller passed;
+ *    grad_scale [B][m] r or NULL: dJ_b/du_scale[b][k] = sum_t u[t][k] dJ_b/dv[t][k], t ascending.
+ * reduce != 0 (only with u_per_instance 0): grad is [N][m] = sum_b w_b grad[b][t][k] and q_mean [1] = sum_b w_b J_b (required), with
+ * w = weights [B] r (finite, non-negative) or, weights NULL, 1/B.  The order is fixed: members in ascending chunks of 256, a
+ * sequential sum inside a chunk, then a sequential sum of the chunk partials; every product w_b g is rounded before it is added.
+ * The members' gradients then stay on the device: [N][m], q_mean and q are all that is copied back.  Without reduce, weights
+ * are checked and otherwise unused.
+ * The adjoint pass keeps the forward states in a device workspace [B][N+1][n] c, allocated by the call, and recomputes each step's
+ * propagator with its Frechet derivatives from one matrix exponential of the (1 + m) d block matrix (every compiled plant shape
+ * keeps (1 + m) d <= 16).
+ * M4Q_E_BADARG: B or N < 1, a missing x0, u, W, target, q or grad, q_mode outside 1-2, reduce with u_per_instance 1 or without
+ * q_mean, a non-finite or negative weight, (plant) missing dts, op0 or ops, a plant_kind that is no device plant,
+ * M4Q_PLANT_PROCESS with n not a fourth power.  M4Q_E_UNSUPPORTED: no compiled shape, a plant gradient with n not a square, a
+ * model gradient on a plant-only shape, and M4Q_PLANT_GENERATOR: its block matrix has (1 + m) n > 16 columns - dissipative
+ * dynamics go through the gradient of the discretised model (m4q_discretize_batch, then m4q_model_rollout_grad_batch).
+ * Arguments are checked before the device is asked for.
+ *
+ * m4q_plant_rollout_grad_batch: M4Q_PLANT_HAMILTONIAN (n = d^2) and M4Q_PLANT_PROCESS (n = d^4); dts, op0, ops as
+ * m4q_plant_rollout_batch. */
+M4Q_API int m4q_plant_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                                 const double* x0, const double* u, int32_t u_per_instance, const double* u_scale, const double* op0,
+                                 const double* ops, int32_t plant_per_instance, const double* W, const double* target,
+                                 int32_t target_per_instance, int32_t q_mode, const double* weights, int32_t reduce, double* q,
+                                 double* grad, double* grad_scale, double* q_mean);
+/* m4q_model_rollout_grad_batch: the step of m4q_model_rollout_batch; models [B|1][n][n(1+P)] c. */
+M4Q_API int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0,
+                                 const double* u, int32_t u_per_instance, const double* u_scale, const double* models,
+                                 int32_t model_per_instance, const double* W, const double* target, int32_t target_per_instance,
+                                 int32_t q_mode, const double* weights, int32_t reduce, double* q, double* grad, double* grad_scale,
+                                 double* q_mean);
+
 /* DMDc identification for an ensemble in ONE launch: DiscrepDMDc.from_data(X2, X1, krtimes(lift(U1), X1), rcond) = X2 pinv(Z, rcond)
  * (model.py: DiscrepDMDc.from_data, the fit of the reference's training workflow) for B members and R cut-offs, the models in the layout every other
  * entry point takes.  mpc4quantum_amd/fit.py (dmdc_fit_reference) is the definition, in NumPy, in the kernel's order of operations.

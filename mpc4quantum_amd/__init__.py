@@ -6,6 +6,8 @@ from .exit_condition import QuadraticExit  # noqa: F401
 from .experiment import (Experiment, LExperiment, QCoupledExperiment, QExperiment, QExperiment32, QSynthesis,  # noqa: F401
                          isqrt, plant_step_batch, process_dim, split_blocks)
 from .fit import dmdc_fit_batch, dmdc_fit_reference, train_models_batch  # noqa: F401
+from .grad import (model_rollout_grad_batch, model_rollout_grad_reference, ordered_weighted_sum,  # noqa: F401
+                   plant_rollout_grad_batch, plant_rollout_grad_reference)
 from .library import (create_library, create_library_from_list, create_power_list, diff_library, krtimes,  # noqa: F401
                       multinomial_powers, size_of_library)
 from .linearize import WrapModel  # noqa: F401

@@ -133,6 +133,29 @@ struct RollArgs {
   M4Q_P(cplx) xs; M4Q_P(double) q;
 };
 
+// Rollout gradients (m4q_plant_rollout_grad_batch, m4q_model_rollout_grad_batch; m4q_grad.h, grad.py is the definition).
+// The forward pass is the rollout `roll` describes, with xs_mode 2 and xs the workspace [B][N + 1][n] the backward pass reads the
+// states from; q_mode 1: J = q_N, 2: J = sum_t q_t.  grad [B][N][m] = dJ_b/du[t][k]; grad_scale [B][m] = dJ_b/du_scale[b][k] or null.
+// reduce: the launcher then runs grad_reduce_kernel twice - members in chunks of GRAD_CHUNK into partial [chunks][N m + 1], the
+// chunk partials into grad_mean [N][m] and q_mean [1] - with weights [B] (never null when reduce is set).
+constexpr int GRAD_CHUNK = 256;
+struct GradArgs {
+  RollArgs roll;
+  M4Q_P(double) grad; M4Q_P(double) grad_scale;
+  int reduce;
+  M4Q_P(const double) weights;
+  M4Q_P(double) partial; M4Q_P(double) grad_mean; M4Q_P(double) q_mean;
+};
+// One pass of the ordered reduction (m4q_grad.h: grad_reduce): `count` rows in chunks of `chunk`
+struct GradReduceArgs {
+  int count, chunk, nm, q_cols;
+  M4Q_P(const double) vals; long row_stride;
+  M4Q_P(const double) q;
+  M4Q_P(const double) w;                           // [count] or null
+  M4Q_P(double) out; long out_stride;              // element e < nm of chunk c -> out[c out_stride + e]
+  M4Q_P(double) out_last; long last_stride;        // element nm of chunk c -> out_last[c last_stride]
+};
+
 // m4q_dmdc_fit_batch: the truncated least-squares DMDc fit of B members from E experiments of N steps each (m4q_fit.h; fit.py is
 // the definition).  The member sees u_scale[b][k] u[e][t][k], as in the rollouts.  rconds live in device memory: the kernel indexes
 // them at run time.
@@ -197,6 +220,8 @@ struct ShapeOps {
   int (*launch_fit)(const FitArgs&, hipStream_t);                 // its layout does not fit one workgroup's LDS)
   int online_lds_bytes;                                           // ... of online_dmdc_kernel, likewise
   int (*launch_online)(const OnlineArgs&, int hermitian, hipStream_t);
+  int (*launch_plant_grad)(const GradArgs&, hipStream_t);          // (square shapes, plant-only ones included; no generator plant)
+  int (*launch_model_grad)(const GradArgs&, hipStream_t);          // (every shape with a model)
 };
 
 }  // namespace m4q

@@ -1136,6 +1136,94 @@ int m4q_model_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t ord
   return st.finish(sh->launch_model_rollout(a, nullptr), "model rollout");
 }
 
+namespace {
+// the arguments the two rollout gradients share, checked before a device is asked for
+int check_grad_args(const char* who, int32_t B, int32_t N, const double* x0, const double* u, int32_t u_per_instance, const double* W,
+                    const double* target, int32_t q_mode, const double* weights, int32_t reduce, double* q, double* grad, double* q_mean) {
+  if (B < 1 || N < 1) return fail(M4Q_E_BADARG, "%s: B and N must be at least 1 (got %d, %d)", who, B, N);
+  if (!x0 || !u || !W || !target) return fail(M4Q_E_BADARG, "%s: x0, u, W and target are required", who);
+  if (q_mode < 1 || q_mode > 2) return fail(M4Q_E_BADARG, "%s: q_mode is 1 (J = q_N) or 2 (J = sum_t q_t), got %d", who, q_mode);
+  if (!q || !grad) return fail(M4Q_E_BADARG, "%s: q and grad are required", who);
+  if (reduce && u_per_instance) return fail(M4Q_E_BADARG, "%s: reduce needs one control sequence shared by the ensemble (u_per_instance 0)", who);
+  if (reduce && !q_mean) return fail(M4Q_E_BADARG, "%s: reduce needs q_mean", who);
+  if (weights)
+    for (int32_t b = 0; b < B; ++b)
+      if (!std::isfinite(weights[b]) || weights[b] < 0.0) return fail(M4Q_E_BADARG, "%s: weights[%d] = %g is not a finite non-negative number", who, b, weights[b]);
+  return 0;
+}
+
+// stages what the two rollout gradients share: the rollout with every state kept in a workspace, the outputs, the reduction's buffers
+m4q::GradArgs stage_grad(Stage& st, int32_t B, size_t n, size_t m, int32_t N, const double* x0, const double* u, int32_t u_per_instance,
+                         const double* u_scale, const double* W, const double* target, int32_t target_per_instance, int32_t q_mode,
+                         const double* weights, int32_t reduce, double* q, double* grad, double* grad_scale, double* q_mean) {
+  m4q::GradArgs g{};
+  g.roll = stage_roll(st, B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, /*xs_mode=*/2, /*xs=*/nullptr, q_mode, q);
+  const size_t nm = (size_t)N * m;
+  g.grad = st.out<double>(reduce ? nullptr : grad, (size_t)B * nm);       // (with reduce the members' gradients stay on the device)
+  if (grad_scale) g.grad_scale = st.out<double>(grad_scale, (size_t)B * m);
+  g.reduce = reduce ? 1 : 0;
+  if (reduce) {
+    std::vector<double> w;
+    if (weights) w.assign(weights, weights + B);
+    else w.assign((size_t)B, 1.0 / B);
+    g.weights = st.in<double>(w.data(), (size_t)B);
+    g.partial = st.out<double>(nullptr, (((size_t)B + m4q::GRAD_CHUNK - 1) / m4q::GRAD_CHUNK) * (nm + 1));
+    g.grad_mean = st.out<double>(grad, nm);
+    g.q_mean = st.out<double>(q_mean, 1);
+  }
+  return g;
+}
+}  // namespace
+
+int m4q_plant_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                                 const double* x0, const double* u, int32_t u_per_instance, const double* u_scale, const double* op0,
+                                 const double* ops, int32_t plant_per_instance, const double* W, const double* target,
+                                 int32_t target_per_instance, int32_t q_mode, const double* weights, int32_t reduce, double* q,
+                                 double* grad, double* grad_scale, double* q_mean) {
+  const char* who = "m4q_plant_rollout_grad_batch";
+  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d", dim_x, dim_u);
+  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  if (int rc = check_grad_args(who, B, N, x0, u, u_per_instance, W, target, q_mode, weights, reduce, q, grad, q_mean)) return rc;
+  if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, op0 and ops are required", who);
+  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_rollout_grad_batch: plant_kind %d is not a device plant")) return rc;
+  if (plant_kind == M4Q_PLANT_GENERATOR)
+    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no gradient kernel (its block matrix has (1 + m) n > 16 columns): "
+                "take the gradient of the discretised model with m4q_model_rollout_grad_batch", who);
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x);
+  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  Stage st;
+  m4q::GradArgs a = stage_grad(st, B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, q_mode, weights, reduce, q,
+                               grad, grad_scale, q_mean);
+  a.roll.kind = plant_kind;
+  a.roll.dts = st.in<double>(dts, N);
+  a.roll.op0 = st.in<cplx>(op0, e0.count); a.roll.op0_stride = e0.stride;
+  a.roll.ops = st.in<cplx>(ops, ek.count); a.roll.ops_stride = ek.stride;
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_plant_grad(a, nullptr), "plant rollout gradient");
+}
+
+int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* u,
+                                 int32_t u_per_instance, const double* u_scale, const double* models, int32_t model_per_instance,
+                                 const double* W, const double* target, int32_t target_per_instance, int32_t q_mode,
+                                 const double* weights, int32_t reduce, double* q, double* grad, double* grad_scale, double* q_mean) {
+  const char* who = "m4q_model_rollout_grad_batch";
+  const m4q::ShapeOps* sh = find_shape(dim_x, dim_u, order);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no model kernel for dim_x=%d dim_u=%d order=%d", dim_x, dim_u, order);
+  if (int rc = check_grad_args(who, B, N, x0, u, u_per_instance, W, target, q_mode, weights, reduce, q, grad, q_mean)) return rc;
+  if (!models) return fail(M4Q_E_BADARG, "%s: models are required", who);
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, P = sh->np;
+  const Extent mdl(B, model_per_instance, n * n * (1 + P));
+  Stage st;
+  m4q::GradArgs a = stage_grad(st, B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, q_mode, weights, reduce, q,
+                               grad, grad_scale, q_mean);
+  a.roll.models = st.in<cplx>(models, mdl.count); a.roll.model_stride = mdl.stride;
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_model_grad(a, nullptr), "model rollout gradient");
+}
+
 int m4q_dmdc_fit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs, const double* u,
                        int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R, double* models, int32_t* ranks,
                        double* svals, int32_t* status) {

@@ -8,6 +8,7 @@
 #include "m4q_mpc.h"
 #include "m4q_fit.h"
 #include "m4q_online.h"
+#include "m4q_grad.h"
 #include "m4q_noise.h"
 #include "m4q_tile3.h"
 
@@ -1258,6 +1259,45 @@ struct RollCtl {
     }
   }
 };
+
+// Rollout gradients (GradArgs; m4q_grad.h): the controls of step t as the member saw them in the forward pass - the same product
+template <class A>
+__device__ __forceinline__ void grad_controls(const RollCtl& ctl, int t, A& v) {
+#pragma unroll
+  for (int k = 0; k < NU; ++k) v[k] = ctl.sc[k] * gld(ctl.u, (long)t * NU + k);
+}
+// ... what the backward pass leaves of step t: ge[t][k] = Re(lam_{t+1}^H dx_{t+1}/dv_k), parked in the member's grad [N][m]
+__device__ __forceinline__ void grad_park(const GradArgs& ga, long b, int t, const double (&ge)[NU], bool st0) {
+  if (st0) {
+#pragma unroll
+    for (int k = 0; k < NU; ++k) gst(ga.grad, (b * ga.roll.N + t) * NU + k, ge[k]);
+  }
+}
+// ... and the pass over them with t ascending that ends a member: grad[t][k] = u_scale[k] ge[t][k], grad_scale[k] = sum_t u[t][k] ge[t][k]
+__device__ __forceinline__ void grad_finish(const GradArgs& ga, const RollCtl& ctl, long b, bool st0) {
+  wave_sync();
+  double gs[NU];
+#pragma unroll
+  for (int k = 0; k < NU; ++k) gs[k] = 0.0;
+  for (int t = 0; t < ga.roll.N; ++t) {
+#pragma unroll
+    for (int k = 0; k < NU; ++k) {
+      const long idx = (b * ga.roll.N + t) * NU + k;
+      const double gek = gld(ga.grad, idx);
+      double prod = gld(ctl.u, (long)t * NU + k) * gek;      // rounded before the add, as grad.py adds it (the empty asm keeps
+      asm volatile("" : "+v"(prod));                         // the compiler from contracting the two into an FMA)
+      gs[k] = gs[k] + prod;
+      if (st0) gst(ga.grad, idx, ctl.sc[k] * gek);
+    }
+  }
+  if (st0 && ga.grad_scale) {
+#pragma unroll
+    for (int k = 0; k < NU; ++k) gst(ga.grad_scale, b * NU + k, gs[k]);
+  }
+}
+
+// One pass of the ordered ensemble reduction of the gradients (shape-independent)
+__global__ __launch_bounds__(256) void grad_reduce_kernel(GradReduceArgs a) { grad_reduce(a); }
 #endif  // M4Q_VARIANT_GEN
 
 #ifndef M4Q_NO_AUX          // (a plant-only shape - m4q_shapes.inc - builds plant_kernel alone; the generator-plant object none of these)
@@ -1334,6 +1374,63 @@ __global__ __launch_bounds__(64) M4Q_OCC void model_rollout_kernel(RollArgs a) {
       x = pred;
       out.put(t + 1, x);
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Control gradient of an open-loop model rollout (m4q_model_rollout_grad_batch; grad.py: model_rollout_grad_reference is the
+// definition).  The forward pass is model_rollout_kernel's, statement for statement, with every state kept in the workspace
+// a.xs [B][N + 1][n]; the backward pass reads x_t back and takes dx_{t+1}/dv_k from rows() (Brow) and A(v_t)^H lam from col().
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) M4Q_OCC void model_rollout_grad_kernel(GradArgs ga) {
+  const RollArgs& a = ga.roll;
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const LaneGeo L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* mdl = lds + g * MODEL_ELEMS;
+  const int nquads = quads_of(a.B);
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const QuadRow r(quad, g, a.B);
+    wave_sync();
+    stage_model<NX>(mdl, a.models + r.b * a.model_stride, jj);
+    wave_sync();
+    FusedProv<cplx, NX, NU, ORDER> prov;
+    prov.mdl = mdl;
+    prov.Xg = prov.Ug = gview(a.x0, 0, 0);         // (rows() and col() read neither)
+    prov.j = j;
+    const bool st0 = r.valid && jj == 0;
+    const RollOut out(a, r.b, j, r.valid && L.lane_ok, st0);
+    RollCtl ctl(a, r.b);
+    cplx x = gld(a.x0, r.b * NX + j);
+    out.put(0, x);
+    for (int t = 0; t < a.N; ++t) {
+      FusedProv<cplx, NX, NU, ORDER>::Lin lin;
+      ctl.take(t, lin.u);
+      lin.xg = x;
+      cplx pred, Bdummy[NU], ddummy;
+      prov.rows(lin, x, pred, Bdummy, ddummy);
+      x = pred;
+      out.put(t + 1, x);
+    }
+    wave_sync();                                   // the states of this member are in the workspace
+    const M4Q_GLOBAL cplx* xw = a.xs + r.b * (a.N + 1) * NX;
+    cplx lam = figure_grad<NX>(csub(x, out.f), a.W, j);
+    for (int t = a.N - 1; t >= 0; --t) {
+      FusedProv<cplx, NX, NU, ORDER>::Lin lin;
+      grad_controls(ctl, t, lin.u);
+      const cplx xt = gld(xw, (long)t * NX + j);
+      lin.xg = xt;
+      cplx av, Brow[NU], dlt, Ac[NX];
+      prov.rows(lin, czero(), av, Brow, dlt);      // Brow[k] = (df/du_k)_j at (x_t, v_t)
+      prov.col(lin, Ac);                           // column j of A(v_t)
+      double ge[NU];
+#pragma unroll
+      for (int k = 0; k < NU; ++k) ge[k] = rowsum<NX>(dot_re(lam, Brow[k]));
+      lam = matvec_h<NX>(Ac, lam);
+      if (a.q_mode == 2) lam = cadd(lam, figure_grad<NX>(csub(xt, out.f), a.W, j));
+      grad_park(ga, r.b, t, ge, st0);
+    }
+    grad_finish(ga, ctl, r.b, st0);
   }
 }
 
@@ -1514,6 +1611,61 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_rollout_kernel(RollArgs a) {
       M4Q_PLANT_STEP(PLANT, x, x, u, o0, ok, dt, scratch, j, jj);
       out.put(t + 1, x);
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Control gradient of an open-loop plant rollout (m4q_plant_rollout_grad_batch; grad.py: plant_rollout_grad_reference is the
+// definition), Hamiltonian and process plants.  The forward pass is plant_rollout_kernel's, statement for statement, with every
+// state kept in the workspace a.xs [B][N + 1][n]; the backward pass reads x_t back and recomputes U and dU_k (m4q_grad.h).
+template <int PLANT>
+constexpr int grad_lds_elems() {
+  constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;
+  constexpr int need = grad_scratch_elems<NX, NU, D>();
+  return need > SCRATCH_ELEMS ? need : SCRATCH_ELEMS;          // (the forward step works in the same block)
+}
+// (d = 3: compiled for two waves per SIMD the 9 x 9 block matrix of expm_cols<9> spills 101 VGPRs, 392 B of scratch per lane)
+template <int PLANT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NX == 9 ? 1 : WAVES, 8))) void plant_rollout_grad_kernel(GradArgs ga) {
+  static_assert(PLANT == PLANT_HAMILTONIAN || PLANT == PLANT_PROCESS, "the generator plant has no gradient kernel");
+  constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;
+  constexpr int NC = PLANT == PLANT_PROCESS ? D * D : 1;
+  const RollArgs& a = ga.roll;
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const LaneGeo L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* scratch = lds + g * grad_lds_elems<PLANT>();
+  const int nquads = quads_of(a.B);
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const QuadRow r(quad, g, a.B);
+    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
+    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const bool st0 = r.valid && jj == 0;
+    const RollOut out(a, r.b, j, r.valid && L.lane_ok, st0);
+    RollCtl ctl(a, r.b);
+    double dtn = gld(a.dts, 0);
+    cplx x = gld(a.x0, r.b * NX + j);
+    out.put(0, x);
+    for (int t = 0; t < a.N; ++t) {
+      double u[NU];
+      ctl.take(t, u);
+      const double dt = dtn;
+      dtn = gld(a.dts, t + 1 < a.N ? t + 1 : t);
+      M4Q_PLANT_STEP(PLANT, x, x, u, op0, ops, dt, scratch, j, jj);
+      out.put(t + 1, x);
+    }
+    wave_sync();                                   // the states of this member are in the workspace
+    const M4Q_GLOBAL cplx* xw = a.xs + r.b * (a.N + 1) * NX;
+    cplx lam = figure_grad<NX>(csub(x, out.f), a.W, j);
+    for (int t = a.N - 1; t >= 0; --t) {
+      double v[NU], ge[NU];
+      grad_controls(ctl, t, v);
+      const cplx xt = gld(xw, (long)t * NX + j);
+      lam = plant_grad_step<NX, NU, D, NC>(xt, lam, v, op0, ops, gld(a.dts, t), scratch, j, jj, ge);
+      if (a.q_mode == 2) lam = cadd(lam, figure_grad<NX>(csub(xt, out.f), a.W, j));
+      grad_park(ga, r.b, t, ge, st0);
+    }
+    grad_finish(ga, ctl, r.b, st0);
   }
 }
 
@@ -1825,10 +1977,62 @@ static int launch_noise(const NoiseArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(noise_sample_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, s, a);
   return -(int)hipGetLastError();
 }
+
+// the two passes of the ordered reduction behind a gradient kernel, on its stream: members in chunks of GRAD_CHUNK into
+// a.partial [chunks][N m + 1], then the chunk partials, as one chunk and without weights, into a.grad_mean and a.q_mean
+static int launch_grad_reduce(const GradArgs& a, hipStream_t s) {
+  if (!a.reduce) return 0;
+  const RollArgs& r = a.roll;
+  const int nm = r.N * NU;
+  const int nchunks = (r.B + GRAD_CHUNK - 1) / GRAD_CHUNK;
+  GradReduceArgs p{};
+  p.count = r.B; p.chunk = GRAD_CHUNK; p.nm = nm; p.q_cols = r.q_mode == 2 ? r.N + 1 : 1;
+  p.vals = a.grad; p.row_stride = nm; p.q = r.q; p.w = a.weights;
+  p.out = a.partial; p.out_stride = nm + 1; p.out_last = a.partial + nm; p.last_stride = nm + 1;
+  GradReduceArgs f{};
+  f.count = nchunks; f.chunk = nchunks; f.nm = nm; f.q_cols = 0;
+  f.vals = a.partial; f.row_stride = nm + 1;
+  f.out = a.grad_mean; f.out_last = a.q_mean;
+  const long threads = (long)nchunks * (nm + 1);
+  const long blocks = (threads + 255) / 256;
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, p);
+  if (hipError_t e = hipGetLastError()) return -(int)e;
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((nm + 1 + 255) / 256)), dim3(256), 0, s, f);
+  return -(int)hipGetLastError();
+}
+// a gradient kernel over quads of members (launch_aux's launch), then the reduction when the call asks for one
+template <class K>
+static int launch_grad(K kern, const GradArgs& a, size_t lds, hipStream_t s) {
+  int rc = prep_lds(kern, lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid_for(a.roll.B)), dim3(64), lds, s, a);
+  if (hipError_t e = hipGetLastError()) return -(int)e;
+  return launch_grad_reduce(a, s);
+}
+static int launch_plant_grad(const GradArgs& a, hipStream_t s) {
+  if constexpr (!SQUARE) {
+    return UNBUILT;
+  } else {
+    if (a.roll.kind == PLANT_HAMILTONIAN)
+      return launch_grad(plant_rollout_grad_kernel<PLANT_HAMILTONIAN>, a, sizeof(cplx) * (size_t)(ROWS * grad_lds_elems<PLANT_HAMILTONIAN>()), s);
+    if constexpr (QUARTIC) {
+      if (a.roll.kind == PLANT_PROCESS)
+        return launch_grad(plant_rollout_grad_kernel<PLANT_PROCESS>, a, sizeof(cplx) * (size_t)(ROWS * grad_lds_elems<PLANT_PROCESS>()), s);
+    }
+    return UNBUILT;
+  }
+}
+#ifndef M4Q_NO_AUX
+static int launch_model_grad(const GradArgs& a, hipStream_t s) { return launch_grad(model_rollout_grad_kernel, a, MODEL_LDS, s); }
+#else
+static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
+#endif
 #else
 static int launch_plant(const PlantArgs&, hipStream_t) { return UNBUILT; }
 static int launch_noise(const NoiseArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant_rollout(const RollArgs&, hipStream_t) { return UNBUILT; }
+static int launch_plant_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
+static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 #endif
 
 #if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
@@ -1861,7 +2065,7 @@ static const ShapeOps* shape_ops() {
 #endif
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
-                               ONLINE_LDS, launch_online};
+                               ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad};
   return &ops;
 }
 

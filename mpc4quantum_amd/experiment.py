@@ -79,6 +79,18 @@ def _simulate_batch(exp, x0s, ts, us, op0, u_scale, W, target, keep, figure):
                                keep=keep, figure=figure)
 
 
+def _gradient_batch(exp, x0s, ts, us, W, target, op0, u_scale, figure, weights, reduce, scale_grad):
+    """gradient_batch of the two unitary device plants: simulate_batch's arguments into plant_rollout_grad_batch."""
+    from .grad import plant_rollout_grad_batch
+    x0s = np.asarray(x0s, dtype=np.complex128)
+    if x0s.ndim == 1:
+        x0s = x0s[None]
+    own0, ops = exp.operators()
+    u = held_controls(us, ts, len(exp.H1_list), x0s.shape[0])
+    return plant_rollout_grad_batch(x0s, u, own0 if op0 is None else op0, ops, ts, W, target, exp.plant_kind, u_scale=u_scale,
+                                    figure=figure, weights=weights, reduce=reduce, scale_grad=scale_grad)
+
+
 class QExperiment(Experiment):
     """Closed-system plant: H0 and H1_list are d x d Hermitian (ndarray or qutip.Qobj)."""
 
@@ -168,6 +180,15 @@ class QExperiment(Experiment):
         axis first) and / or "q".  Noise-free, and no expectation values: e_ops, set_sigma and set_noise act on simulate() and mpc()."""
         return _simulate_batch(self, x0s, ts, us, op0, u_scale, W, target, keep, figure)
 
+    def gradient_batch(self, x0s, ts, us, W, target, op0=None, u_scale=None, figure="last", weights=None, reduce=False,
+                       scale_grad=False):
+        """The figure of simulate_batch's rollout and its gradient with respect to the held controls, for an ensemble in one launch
+        (plant_rollout_grad_batch): x0s, ts, us, op0, u_scale as simulate_batch; figure "last" (J = q_N) or "sum" (J = sum_t q_t).
+        Returns its dict: "q", "grad" [B, N, m] with N = len(ts) - 1 (ensemble axis first, then time, then control), "grad_scale",
+        "q_mean".  With collapse operators the plant is a generator plant, which the library refuses: take the gradient of the
+        discretised model (model_rollout_grad_batch)."""
+        return _gradient_batch(self, x0s, ts, us, W, target, op0, u_scale, figure, weights, reduce, scale_grad)
+
 
 class LExperiment(QExperiment):
     """Open-system plant: x' = (L0 + sum_k u_k L_k) x with n x n generators on vec_r(rho)."""
@@ -176,6 +197,11 @@ class LExperiment(QExperiment):
 
     def operators(self):
         return self.H0, np.stack(self.H1_list)
+
+    def gradient_batch(self, *args, **kwargs):
+        """Refused: the generator plant has no gradient kernel."""
+        raise ValueError("LExperiment.gradient_batch: the generator plant has no control gradient on the device - discretise the "
+                         "generators (discretize_homogeneous) and take the gradient of the model with model_rollout_grad_batch")
 
     def f(self, t, x, u):
         L = self.H0 + sum(h * uk for h, uk in zip(self.H1_list, np.reshape(u, -1)))
@@ -292,6 +318,12 @@ class QSynthesis(Experiment):
         u_scale [B, m]: the members' drive-amplitude factors.  Returns the dict of plant_rollout_batch: "xs" [B, len(ts), n] (ensemble
         axis first) and / or "q".  Noise-free, and no expectation values: e_ops, set_sigma and set_noise act on simulate() and mpc()."""
         return _simulate_batch(self, x0s, ts, us, op0, u_scale, W, target, keep, figure)
+
+    def gradient_batch(self, x0s, ts, us, W, target, op0=None, u_scale=None, figure="last", weights=None, reduce=False,
+                       scale_grad=False):
+        """The figure of simulate_batch's rollout and its gradient with respect to the held controls, for an ensemble in one launch
+        (plant_rollout_grad_batch on the process plant): arguments and the returned dict as QExperiment.gradient_batch."""
+        return _gradient_batch(self, x0s, ts, us, W, target, op0, u_scale, figure, weights, reduce, scale_grad)
 
 
 def split_blocks(bmatrix, nrows, ncols):

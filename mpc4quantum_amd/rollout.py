@@ -106,6 +106,26 @@ def _result(xs, q):
     return out
 
 
+def _plant_operators(op0, ops, kind, B, n, m):
+    """Checks and lays out the plant operators of B members: returns (op0, ops, per)."""
+    k = _plant_dim(kind, n)
+    op0 = np.ascontiguousarray(op0, dtype=np.complex128)
+    ops = np.ascontiguousarray(ops, dtype=np.complex128)
+    if op0.ndim not in (2, 3) or op0.shape[-2:] != (k, k) or (op0.ndim == 3 and op0.shape[0] not in (1, B)):
+        raise ValueError("op0 must be [k, k] or [B|1, k, k] with k = %d, B = %d, got %s" % (k, B, op0.shape))
+    if ops.ndim not in (3, 4) or ops.shape[-3:] != (m, k, k) or (ops.ndim == 4 and ops.shape[0] not in (1, B)):
+        raise ValueError("ops must be [m, k, k] or [B|1, m, k, k] with m = %d, k = %d, B = %d, got %s" % (m, k, B, ops.shape))
+    per0 = op0.ndim == 3 and op0.shape[0] == B and B > 1
+    perk = ops.ndim == 4 and ops.shape[0] == B and B > 1
+    per = 1 if (per0 or perk) else 0
+    if per:          # the kernel reads both operator sets with the member's stride: repeat the shared one
+        if not per0:
+            op0 = np.ascontiguousarray(np.broadcast_to(op0.reshape(-1, k, k)[:1], (B, k, k)))
+        if not perk:
+            ops = np.ascontiguousarray(np.broadcast_to(ops.reshape(-1, m, k, k)[:1], (B, m, k, k)))
+    return op0, ops, per
+
+
 def plant_rollout_batch(x0, us, op0, ops, dt_or_ts, kind=_lib.PLANT_HAMILTONIAN, u_scale=None, W=None, target=None, keep="all",
                         figure="none"):
     """N held-control plant steps of B members in one launch.
@@ -118,22 +138,8 @@ def plant_rollout_batch(x0, us, op0, ops, dt_or_ts, kind=_lib.PLANT_HAMILTONIAN,
     x0, us, u_per, u_scale, W, target, t_per, xs_mode, q_mode = _common(x0, us, u_scale, W, target, keep, figure)
     B, n = x0.shape
     N, m = us.shape[-2:]
-    k = _plant_dim(kind, n)
-    op0 = np.ascontiguousarray(op0, dtype=np.complex128)
-    ops = np.ascontiguousarray(ops, dtype=np.complex128)
-    if op0.ndim not in (2, 3) or op0.shape[-2:] != (k, k) or (op0.ndim == 3 and op0.shape[0] not in (1, B)):
-        raise ValueError("op0 must be [k, k] or [B|1, k, k] with k = %d, B = %d, got %s" % (k, B, op0.shape))
-    if ops.ndim not in (3, 4) or ops.shape[-3:] != (m, k, k) or (ops.ndim == 4 and ops.shape[0] not in (1, B)):
-        raise ValueError("ops must be [m, k, k] or [B|1, m, k, k] with m = %d, k = %d, B = %d, got %s" % (m, k, B, ops.shape))
+    op0, ops, per = _plant_operators(op0, ops, kind, B, n, m)
     dts = dts_of(dt_or_ts, N)
-    per0 = op0.ndim == 3 and op0.shape[0] == B and B > 1
-    perk = ops.ndim == 4 and ops.shape[0] == B and B > 1
-    per = 1 if (per0 or perk) else 0
-    if per:          # the kernel reads both operator sets with the member's stride: repeat the shared one
-        if not per0:
-            op0 = np.ascontiguousarray(np.broadcast_to(op0.reshape(-1, k, k)[:1], (B, k, k)))
-        if not perk:
-            ops = np.ascontiguousarray(np.broadcast_to(ops.reshape(-1, m, k, k)[:1], (B, m, k, k)))
     xs, q = _outputs(B, N, n, xs_mode, q_mode)
     L = _lib.lib()
     _lib.check(L.m4q_plant_rollout_batch(B, n, m, int(kind), N, _ptr(dts), _ptr(x0), _ptr(us), u_per, _ptr(u_scale), _ptr(op0),
