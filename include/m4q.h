@@ -379,6 +379,33 @@ M4Q_API int m4q_session_set_noise(m4q_session* s, int32_t mode, const double* si
  * needs n = d d. */
 M4Q_API int m4q_noise_sample_batch(int32_t B, int32_t n, int32_t mode, const double* sigma, int32_t sigma_per_instance, uint64_t seed,
                                    uint64_t member_base, int32_t state_index, double* out);
+/* Observed plants: the loop closes on x = observe(z) of a plant state z that the model does not describe (the reference's
+ * QCoupledExperiment and QExperiment32; mpc4quantum_amd/observe.py is the normative definition).  z has n_p = d_p^2 entries and
+ * evolves by M4Q_PLANT_HAMILTONIAN's arithmetic on d_p x d_p operators; x has n = dim_x entries.
+ *   M4Q_OBSERVE_PARTIAL_TRACE  n_p = 16, n = 8: z = vec_r of a two-qubit state, x = [vec_r(tr_B rho), vec_r(tr_A rho)]
+ *   M4Q_OBSERVE_QUBIT_BLOCK    n_p = 9,  n = 4: z = vec_r of a three-level state, x = vec_r(Bk / s), Bk its leading 2 x 2 block and
+ *                              s = sqrt(|Bk|_F^2 + 2 |det Bk|) its trace norm (s = 0 gives NaN: the member ends with exit code 3)
+ * An observed plant is a setting of an M4Q_PLANT_NONE session, not a plant_kind: m4q_session_create, m4q_plant_step_batch, the
+ * rollouts and their gradients take the plant kinds above and nothing else; exit conditions and noise stay refused on such a session. */
+#define M4Q_OBSERVE_PARTIAL_TRACE 1
+#define M4Q_OBSERVE_QUBIT_BLOCK 2
+/* x = observe(z) alone, by the kernel the loop calls: z [B][n_p] c, x [B][n] c (host).  M4Q_E_BADARG: B < 1, another kind, a
+ * null pointer. */
+M4Q_API int m4q_observe_batch(int32_t B, int32_t observe, const double* z, double* x);
+/* op0 [B|1][d_p][d_p] c, ops [B|1][m][d_p][d_p] c (plant_per_instance), z0 [B][n_p] c: host buffers, copied.  Allocates the plant
+ * states zs [B][n_steps + 1][n_p] (zero), writes zs[:, 0] = z0 and xs[:, 0] = observe(z0); the caller uploads the same observe(z0)
+ * (m4q_observe_batch) as M4Q_F_X0.  M4Q_E_BADARG, before any device work: a session whose plant_kind is not M4Q_PLANT_NONE,
+ * measure_freq > 1, a dim_x that is not the kind's n, a null pointer, a call after the session's first run. */
+M4Q_API int m4q_session_set_observed_plant(m4q_session* s, int32_t observe, const double* op0, const double* ops,
+                                           int32_t plant_per_instance, const double* z0);
+/* for k in [step_begin, step_end): the launch of m4q_session_run(k, k + 1), then one kernel that - for every member that launch
+ * completed step k for (exit code 0, steps_done = k + 1) - takes the plant step zs[k] -> zs[k + 1] under us[k] and stores
+ * xs[k + 1] = observe(zs[k + 1]); every other member is left untouched.  All on the session's stream: no synchronisation, no copy.
+ * Ranges are refused as m4q_session_run refuses them. */
+M4Q_API int m4q_session_run_observed(m4q_session* s, int32_t step_begin, int32_t step_end);
+/* download / upload (restore) zs [B][n_steps + 1][n_p] c; both synchronise and check the watchdog, as m4q_session_download does */
+M4Q_API int m4q_session_plant_states(m4q_session* s, void* host, size_t bytes);
+M4Q_API int m4q_session_put_plant_states(m4q_session* s, const void* host, size_t bytes);
 /* kernel time of the launches since the last call, from HIP events on the session stream */
 M4Q_API int m4q_session_kernel_ms(m4q_session* s, double* total_ms, int32_t* launches);
 /* arithmetic path the uploaded problem will run on: 0 complex, 1 real (Hermitian operator basis, d*d coordinates),

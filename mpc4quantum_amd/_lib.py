@@ -23,6 +23,7 @@ OPT_NO_SG = 16
 PLANT_NONE, PLANT_HAMILTONIAN, PLANT_GENERATOR, PLANT_PROCESS = 0, 1, 2, 3
 EXIT_PREV, EXIT_NEXT, EXIT_BELOW, EXIT_ABOVE = 1, 2, 4, 8
 NOISE_IID, NOISE_HERMITIAN = 1, 2
+OBSERVE_PARTIAL_TRACE, OBSERVE_QUBIT_BLOCK = 1, 2
 ONLINE_HERMITIAN = 1
 E_UNSUPPORTED, E_BADARG, E_NODEVICE, E_TIMEOUT, E_COMM = -1001, -1002, -1003, -1004, -1005
 UNIQUE_ID_BYTES = 128
@@ -92,6 +93,11 @@ PROTOTYPES = {
     "m4q_session_set_codes": (C.c_int, [_vp, _ip]),
     "m4q_session_set_exit": (C.c_int, [_vp, _i32, _dp, _dp, _i32, _dp, _i32]),
     "m4q_session_set_noise": (C.c_int, [_vp, _i32, _dp, _i32, C.c_uint64, C.c_uint64]),
+    "m4q_observe_batch": (C.c_int, [_i32, _i32, _dp, _dp]),
+    "m4q_session_set_observed_plant": (C.c_int, [_vp, _i32, _dp, _dp, _i32, _dp]),
+    "m4q_session_run_observed": (C.c_int, [_vp, _i32, _i32]),
+    "m4q_session_plant_states": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "m4q_session_put_plant_states": (C.c_int, [_vp, _vp, C.c_size_t]),
     "m4q_noise_sample_batch": (C.c_int, [_i32, _i32, _i32, _dp, _i32, C.c_uint64, C.c_uint64, _i32, _dp]),
     "m4q_session_kernel_ms": (C.c_int, [_vp, C.POINTER(C.c_double), _ip]),
     "m4q_session_info": (C.c_int, [_vp, C.POINTER(C.c_int64), _ip, _ip]),

@@ -199,6 +199,34 @@ struct NoiseArgs {
   M4Q_P(cplx) out;
 };
 
+// Observed plants (m4q_observe.h; observe.py is the definition): the plant state z has n_p = d_p^2 entries and evolves by the
+// Hamiltonian plant's arithmetic, the loop sees x = observe(z) of n = dim_x entries.  (mirrored in include/m4q.h: M4Q_OBSERVE_*)
+enum : int { OBSERVE_PARTIAL_TRACE = 1, OBSERVE_QUBIT_BLOCK = 2 };
+constexpr int observe_np(int kind) { return kind == OBSERVE_PARTIAL_TRACE ? 16 : kind == OBSERVE_QUBIT_BLOCK ? 9 : 0; }
+constexpr int observe_dp(int kind) { return kind == OBSERVE_PARTIAL_TRACE ? 4 : kind == OBSERVE_QUBIT_BLOCK ? 3 : 0; }
+constexpr int observe_n(int kind) { return kind == OBSERVE_PARTIAL_TRACE ? 8 : kind == OBSERVE_QUBIT_BLOCK ? 4 : 0; }
+
+// x = observe(z) for B members (m4q_observe_batch; xs[:, 0] of a session): member b reads z + b z_stride, writes x + b x_stride
+struct ObserveArgs {
+  int B, kind;
+  M4Q_P(const cplx) z; long z_stride;              // n_p entries each
+  M4Q_P(cplx) x; long x_stride;                    // n entries each
+};
+
+// One MPC step of an observed plant, between two closed-loop launches of a PLANT_NONE session (m4q_session_run_observed): for
+// every member with codes[b] == 0 and steps_done[b] == step + 1 - the launch just before completed that step - one plant step
+// from zs[b][step] under us[b][step] into zs[b][step + 1], and its observation into xs[b][step + 1].  Other members: untouched.
+struct ObsPlantArgs {
+  int B, kind, step, n_steps;
+  double dt;
+  M4Q_P(const int) codes; M4Q_P(const int) steps_done;
+  M4Q_P(const double) us;                          // [B][n_steps][m]
+  M4Q_P(const cplx) op0; long op0_stride;          // [B|1][d_p][d_p], as PlantArgs
+  M4Q_P(const cplx) ops; long ops_stride;          // [B|1][m][d_p][d_p]
+  M4Q_P(cplx) zs;                                  // [B][n_steps + 1][n_p]
+  M4Q_P(cplx) xs;                                  // [B][n_steps + 1][n]
+};
+
 // one entry per compiled (dim_x, dim_u, order)
 struct ShapeOps {
   int nx, nu, order, np, d;
@@ -222,6 +250,9 @@ struct ShapeOps {
   int (*launch_online)(const OnlineArgs&, int hermitian, hipStream_t);
   int (*launch_plant_grad)(const GradArgs&, hipStream_t);          // (square shapes, plant-only ones included; no generator plant)
   int (*launch_model_grad)(const GradArgs&, hipStream_t);          // (every shape with a model)
+  int observe_kind;                                                // the observation whose loop state has this dim_x (0: none)
+  int (*launch_observe)(const ObserveArgs&, hipStream_t);          // (shapes with an observe_kind; depends on dim_x alone)
+  int (*launch_observed_plant)(const ObsPlantArgs&, hipStream_t);  // (... and on dim_u: the plant has the shape's controls)
 };
 
 }  // namespace m4q

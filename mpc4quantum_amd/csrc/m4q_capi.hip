@@ -294,6 +294,12 @@ struct m4q_session {
   DevBuf noise_sigma;
   uint64_t noise_seed = 0, noise_member_base = 0;
   bool ran = false;             // m4q_session_run has been called: the noise mode is fixed from here on
+  // observed plant (m4q_session_set_observed_plant; PLANT_NONE sessions): M4Q_OBSERVE_* (0: none), the plant's operators
+  // [B|1][d_p][d_p] and [B|1][m][d_p][d_p], its states zs [B][n_steps + 1][n_p], the shape whose object holds the kernels
+  int observe = 0;
+  bool obs_per = false;
+  DevBuf obs_op0, obs_ops, zs;
+  const m4q::ShapeOps* obs_shape = nullptr;
   std::vector<double> hQ, hQf, hR;
 
   // R weighs the controls, which are real on every path: its one real copy ([COORDS_HERM]) serves both real coordinate systems
@@ -726,6 +732,118 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   s->launched = true;
   s->ran = true;
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// observed plants (m4q_observe.h)
+// ------------------------------------------------------------------------------------------
+static int check_observe_kind(const char* who, int32_t observe) {
+  if (observe != M4Q_OBSERVE_PARTIAL_TRACE && observe != M4Q_OBSERVE_QUBIT_BLOCK)
+    return fail(M4Q_E_BADARG, "%s: observe %d is not M4Q_OBSERVE_PARTIAL_TRACE or M4Q_OBSERVE_QUBIT_BLOCK", who, observe);
+  return 0;
+}
+
+int m4q_observe_batch(int32_t B, int32_t observe, const double* z, double* x) {
+  if (B < 1 || !z || !x) return fail(M4Q_E_BADARG, "m4q_observe_batch: bad argument (B >= 1, z, x)");
+  if (int rc = check_observe_kind("m4q_observe_batch", observe)) return rc;
+  const int n = m4q::observe_n(observe), np = m4q::observe_np(observe);
+  const m4q::ShapeOps* sh = nullptr;
+  for (int nu = 1; nu <= 3 && !sh; ++nu) sh = find_shape_any_order(n, nu);
+  if (!sh || sh->observe_kind != observe) return fail(M4Q_E_UNSUPPORTED, "m4q_observe_batch: no compiled kernel with dim_x=%d", n);
+  if (int rc = need_device()) return rc;
+  Stage st;
+  m4q::ObserveArgs a{};
+  a.B = B; a.kind = observe;
+  a.z = st.in<cplx>(z, (size_t)B * np); a.z_stride = np;
+  a.x = st.out<cplx>(x, (size_t)B * n); a.x_stride = n;
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_observe(a, nullptr), "observe kernel");
+}
+
+int m4q_session_set_observed_plant(m4q_session* s, int32_t observe, const double* op0, const double* ops, int32_t plant_per_instance,
+                                   const double* z0) {
+  if (!s || !op0 || !ops || !z0) return fail(M4Q_E_BADARG, "m4q_session_set_observed_plant: bad argument (session, op0, ops, z0)");
+  if (int rc = check_observe_kind("m4q_session_set_observed_plant", observe)) return rc;
+  const m4q_problem& p = s->prob;
+  if (p.plant_kind != M4Q_PLANT_NONE)
+    return fail(M4Q_E_BADARG, "m4q_session_set_observed_plant: the session has a device plant (plant_kind %d); an observed plant is a "
+                "setting of an M4Q_PLANT_NONE session", p.plant_kind);
+  if (p.measure_freq > 1)
+    return fail(M4Q_E_BADARG, "m4q_session_set_observed_plant: measure_freq = %d; an observed plant is measured at every step",
+                p.measure_freq);
+  if (p.dim_x != m4q::observe_n(observe))
+    return fail(M4Q_E_BADARG, "m4q_session_set_observed_plant: observe %d gives loop states of %d entries, the session has dim_x = %d",
+                observe, m4q::observe_n(observe), p.dim_x);
+  if (s->ran)
+    return fail(M4Q_E_BADARG, "m4q_session_set_observed_plant: the session has already run; the plant is set before the first run");
+  const size_t B = s->B, m = p.dim_u, ns = p.n_steps, n = p.dim_x, C = 16;
+  const size_t np = m4q::observe_np(observe), dp = m4q::observe_dp(observe);
+  if (plant_per_instance && (double)B * m * dp * dp * 16.0 >= 4294967296.0)     // (32-bit byte offsets from one base: m4q_session_create)
+    return fail(M4Q_E_BADARG, "per-instance plant operators must stay below 4 GiB in total");
+  const m4q::ShapeOps* sh = find_shape_any_order(p.dim_x, p.dim_u);
+  if (!sh || sh->observe_kind != observe)
+    return fail(M4Q_E_UNSUPPORTED, "m4q_session_set_observed_plant: no observed-plant kernel for dim_x=%d dim_u=%d", p.dim_x, p.dim_u);
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  s->observe = 0;
+  const Extent e0(B, plant_per_instance, dp * dp), ek(B, plant_per_instance, m * dp * dp);
+  int rc;
+  if ((rc = s->obs_op0.alloc(e0.count * C)) || (rc = s->obs_ops.alloc(ek.count * C)) || (rc = s->zs.alloc(B * (ns + 1) * np * C))) return rc;
+  HIP_TRY(hipMemcpy(s->obs_op0.p, op0, e0.count * C, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->obs_ops.p, ops, ek.count * C, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(s->zs.p, 0, s->zs.bytes));
+  HIP_TRY(hipMemcpy2D(s->zs.p, (ns + 1) * np * C, z0, np * C, np * C, B, hipMemcpyHostToDevice));
+  // xs[:, 0] = observe(z0), by the kernel the loop calls
+  m4q::ObserveArgs a{};
+  a.B = s->B; a.kind = observe;
+  a.z = (const cplx*)s->zs.p; a.z_stride = (long)((ns + 1) * np);
+  a.x = (cplx*)s->f[M4Q_F_XS].p; a.x_stride = (long)((ns + 1) * n);
+  rc = sh->launch_observe(a, s->stream);
+  if (rc) return fail(rc, "observe kernel launch failed: %s", hipGetErrorString((hipError_t)(-rc)));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  s->obs_per = plant_per_instance != 0;
+  s->obs_shape = sh;
+  s->observe = observe;
+  return 0;
+}
+
+int m4q_session_run_observed(m4q_session* s, int32_t step_begin, int32_t step_end) {
+  if (!s || step_begin < 0 || step_end > s->prob.n_steps || step_begin >= step_end)
+    return fail(M4Q_E_BADARG, "m4q_session_run_observed: bad step range [%d, %d)", step_begin, step_end);
+  if (!s->observe) return fail(M4Q_E_BADARG, "m4q_session_run_observed: no observed plant is set (m4q_session_set_observed_plant)");
+  const m4q_problem& p = s->prob;
+  const size_t m = p.dim_u, dp = m4q::observe_dp(s->observe);
+  m4q::ObsPlantArgs a{};
+  a.B = s->B; a.kind = s->observe; a.n_steps = p.n_steps; a.dt = p.dt;
+  a.codes = (const int*)s->f[M4Q_F_CODES].p; a.steps_done = (const int*)s->f[M4Q_F_STEPS_DONE].p;
+  a.us = (const double*)s->f[M4Q_F_US].p;
+  a.op0 = (const cplx*)s->obs_op0.p; a.op0_stride = Extent(s->B, s->obs_per, dp * dp).stride;
+  a.ops = (const cplx*)s->obs_ops.p; a.ops_stride = Extent(s->B, s->obs_per, m * dp * dp).stride;
+  a.zs = (cplx*)s->zs.p; a.xs = (cplx*)s->f[M4Q_F_XS].p;
+  for (int k = step_begin; k < step_end; ++k) {
+    if (int rc = m4q_session_run(s, k, k + 1)) return rc;
+    a.step = k;
+    const int rc = s->obs_shape->launch_observed_plant(a, s->stream);
+    if (rc) return fail(rc, "observed-plant kernel launch failed: %s", hipGetErrorString((hipError_t)(-rc)));
+  }
+  return 0;
+}
+
+static int plant_states_copy(m4q_session* s, const char* who, void* host, size_t bytes, bool down) {
+  if (!s || !host) return fail(M4Q_E_BADARG, "%s: bad argument", who);
+  if (!s->observe) return fail(M4Q_E_BADARG, "%s: no observed plant is set (m4q_session_set_observed_plant)", who);
+  if (bytes != s->zs.bytes) return fail(M4Q_E_BADARG, "%s: the plant states hold %zu bytes, got %zu", who, s->zs.bytes, bytes);
+  if (down) HIP_TRY(hipMemcpyAsync(host, s->zs.p, bytes, hipMemcpyDeviceToHost, s->stream));
+  else HIP_TRY(hipMemcpyAsync(s->zs.p, host, bytes, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return check_watchdog(s);
+}
+
+int m4q_session_plant_states(m4q_session* s, void* host, size_t bytes) {
+  return plant_states_copy(s, "m4q_session_plant_states", host, bytes, true);
+}
+
+int m4q_session_put_plant_states(m4q_session* s, const void* host, size_t bytes) {
+  return plant_states_copy(s, "m4q_session_put_plant_states", const_cast<void*>(host), bytes, false);
 }
 
 int m4q_session_set_exit(m4q_session* s, int32_t mode, const double* W, const double* target, int32_t target_per_instance,

@@ -10,6 +10,7 @@
 #include "m4q_online.h"
 #include "m4q_grad.h"
 #include "m4q_noise.h"
+#include "m4q_observe.h"
 #include "m4q_tile3.h"
 
 #ifndef M4Q_NX
@@ -1552,6 +1553,60 @@ __global__ __launch_bounds__(64) M4Q_OCC void qp_kernel(QpArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Observed plants (m4q_observe.h): the kernels live in the objects whose dim_x is the OBSERVED dimension - the qubit block in
+// the dim_x = 4 objects (plant on n_p = 9), the partial traces in the dim_x = 8 object (plant on n_p = 16) - with the shape's
+// controls.  Rows, quads and strides as the other auxiliary kernels; the lanes are laid out on n_p.
+// ---------------------------------------------------------------------------------------------
+constexpr int OBS_KIND = NX == 4 ? OBSERVE_QUBIT_BLOCK : NX == 8 ? OBSERVE_PARTIAL_TRACE : 0;
+
+template <int OBS>
+__global__ __launch_bounds__(64) void observe_kernel(ObserveArgs a) {
+  constexpr int NPL = ObserveDims<OBS>::NP, NO = ObserveDims<OBS>::N;
+  static_assert(NO == NX, "the observed state is the loop state of this shape");
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const PlantLaneGeo<NPL> L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* blk = lds + g * NPL;
+  const int nquads = quads_of(a.B);
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const QuadRow r(quad, g, a.B);
+    const cplx z = gld(a.z, r.b * a.z_stride + j);
+    const cplx x = observe_row<OBS>(z, blk, jj);
+    if (r.valid && jj < NO) gst(a.x, r.b * a.x_stride + jj, x);
+  }
+}
+
+// the plant step is plant_kernel's device function, unchanged, on the plant's own dimensions: the arithmetic of
+// m4q_plant_step_batch at (n_p, m)
+template <int OBS>
+__global__ __launch_bounds__(64) void observed_plant_kernel(ObsPlantArgs a) {
+  constexpr int NPL = ObserveDims<OBS>::NP, DP = ObserveDims<OBS>::DP, NO = ObserveDims<OBS>::N;
+  static_assert(NO == NX, "the observed state is the loop state of this shape");
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const PlantLaneGeo<NPL> L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* scratch = lds + g * observe_row_elems<OBS>();
+  const int nquads = quads_of(a.B);
+  const long sZ = (long)(a.n_steps + 1) * NPL, sX = (long)(a.n_steps + 1) * NO, sU = (long)a.n_steps * NU;
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const QuadRow r(quad, g, a.B);
+    // the launch before this one completed step a.step for this member (mpc_kernel: codes, steps_done); a member that ended
+    // earlier, or at this step, keeps what it has
+    const bool live = r.valid && gld(a.codes, r.b) == 0 && gld(a.steps_done, r.b) == a.step + 1;
+    const cplx z = gld(a.zs, r.b * sZ + (long)a.step * NPL + j);
+    double u[NU];
+#pragma unroll
+    for (int k = 0; k < NU; ++k) u[k] = gld(a.us, r.b * sU + (long)a.step * NU + k);
+    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
+    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const cplx zn = plant_hamiltonian<NPL, NU, DP>(z, u, op0, ops, a.dt, scratch, j, jj);
+    const cplx x = observe_row<OBS>(zn, scratch, jj);
+    if (live && jj < NPL) gst(a.zs, r.b * sZ + (long)(a.step + 1) * NPL + j, zn);
+    if (live && jj < NO) gst(a.xs, r.b * sX + (long)(a.step + 1) * NO + jj, x);
+  }
+}
+
 #endif  // M4Q_NO_AUX
 
 #ifndef M4Q_VARIANT_GEN
@@ -1939,7 +1994,29 @@ struct OnlineLaunch<true, N_> {
 constexpr bool ONLINE_FITS = OnlineLayout<NX, NU, ORDER>::FITS;
 constexpr int ONLINE_LDS = ONLINE_FITS ? (int)OnlineLayout<NX, NU, ORDER>::BYTES : 0;
 static int launch_online(const OnlineArgs& a, int hermitian, hipStream_t s) { return OnlineLaunch<ONLINE_FITS>::run(a, hermitian, s); }
+// (a partial specialisation, so that the kernels are instantiated only in the objects they belong to)
+template <int OBS>
+struct ObserveLaunch {
+  static int lift(const ObserveArgs& a, hipStream_t s) {
+    if (a.kind != OBS) return UNBUILT;
+    return launch_aux(observe_kernel<OBS>, a, sizeof(cplx) * (size_t)(ROWS * ObserveDims<OBS>::NP), s);
+  }
+  static int step(const ObsPlantArgs& a, hipStream_t s) {
+    if (a.kind != OBS) return UNBUILT;
+    return launch_aux(observed_plant_kernel<OBS>, a, sizeof(cplx) * (size_t)(ROWS * observe_row_elems<OBS>()), s);
+  }
+};
+template <>
+struct ObserveLaunch<0> {
+  static int lift(const ObserveArgs&, hipStream_t) { return UNBUILT; }
+  static int step(const ObsPlantArgs&, hipStream_t) { return UNBUILT; }
+};
+static int launch_observe(const ObserveArgs& a, hipStream_t s) { return ObserveLaunch<OBS_KIND>::lift(a, s); }
+static int launch_observed_plant(const ObsPlantArgs& a, hipStream_t s) { return ObserveLaunch<OBS_KIND>::step(a, s); }
 #else
+constexpr int OBS_KIND = 0;
+static int launch_observe(const ObserveArgs&, hipStream_t) { return UNBUILT; }
+static int launch_observed_plant(const ObsPlantArgs&, hipStream_t) { return UNBUILT; }
 constexpr int FIT_LDS = 0;
 static int launch_fit(const FitArgs&, hipStream_t) { return UNBUILT; }
 constexpr int ONLINE_LDS = 0;
@@ -2065,7 +2142,7 @@ static const ShapeOps* shape_ops() {
 #endif
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
-                               ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad};
+                               ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant};
   return &ops;
 }
 

@@ -435,6 +435,8 @@ def mpc_batch_sharded(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0
     from .mpc import check_batch_exit, open_session
     from .noise import check_batch_noise
     # (before the transport exists: a rank that raises here has joined nothing)
+    if kw.get("observe") is not None:
+        raise ValueError("mpc_batch_sharded: observed plants (observe=) are not sharded; run mpc_batch on each rank's own members")
     if models is not None and kw.get("generators") is not None:
         raise ValueError("pass models or generators (and scales), not both")
     if kw.get("scales") is not None and (np.ndim(kw["scales"]) != 2 or np.shape(kw["scales"])[0] != np.shape(x0)[0]):

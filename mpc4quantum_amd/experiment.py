@@ -345,6 +345,8 @@ def isqrt(n):
 class QExperiment32(QExperiment):
     """Three-level plant seen through its qubit block (experiment.py:215-235): the model lives on the 2x2 block."""
 
+    observe_kind = _lib.OBSERVE_QUBIT_BLOCK      # what lift is on the device (observe.py): mpc() keeps this class's loop there
+
     @staticmethod
     def lift(rho33_vec):
         block = np.reshape(np.asarray(rho33_vec, dtype=np.complex128), (3, 3))[:2, :2]
@@ -359,6 +361,8 @@ class QExperiment32(QExperiment):
 class QCoupledExperiment(QExperiment):
     """Two identical subsystems: the model sees the two reduced states [vec(rho_A), vec(rho_B)] (partial traces),
     the plant the joint state (experiment.py:238-306)."""
+
+    observe_kind = _lib.OBSERVE_PARTIAL_TRACE    # what lift is on the device (observe.py): mpc() keeps this class's loop there
 
     @staticmethod
     def lift(rhoAB_vec):

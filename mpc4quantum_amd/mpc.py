@@ -10,10 +10,11 @@ import numpy as np
 
 from . import _lib
 from .exit_condition import QuadraticExit, require_device_exit
-from .experiment import Experiment, QExperiment, QSynthesis
+from .experiment import Experiment, QCoupledExperiment, QExperiment, QExperiment32, QSynthesis
 from .library import krtimes
 from .linearize import WrapModel
 from .noise import check_batch_noise, require_noise
+from .observe import check_observed_plant, observe_batch, observe_dims
 from .session import EnsembleSession
 
 
@@ -151,6 +152,19 @@ def _runs_fused(experiment, exit_condition, streaming):
             and (exit_condition is None or isinstance(exit_condition, QuadraticExit)))
 
 
+def _runs_observed(experiment, exit_condition, streaming, measure_freq=1):
+    """mpc() keeps the closed loop of an observed plant (observe.py) on the device - one MPC launch and one plant-and-observe launch
+    per step, no host round trip - when the experiment's class is exactly QCoupledExperiment or QExperiment32 (a subclass may bring
+    its own lift) on the dimensions the kernels are built for, without collapse operators, e_ops, sigma or device noise, with no exit
+    condition, no streaming updates and measure_freq 1.  Anything else keeps the host path."""
+    if type(experiment) not in (QCoupledExperiment, QExperiment32):
+        return False
+    d = observe_dims(type(experiment).observe_kind)[2]
+    return (np.shape(experiment.H0) == (d, d) and not experiment._c_ops() and experiment._me_args.get("e_ops") is None
+            and not experiment._sigma and experiment.device_noise is None and exit_condition is None and not streaming
+            and int(measure_freq) == 1)
+
+
 def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sat=None, du=None, max_iter=100,
         exit_condition=None, streaming=False, warm_start=True, progress_bar=True, verbose=False, exact_qp=False,
         qp_flags=None):
@@ -165,14 +179,22 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
     with a native plant or QSynthesis (and no streaming) keeps the loop fused: the kernel evaluates it after every step.
     Measurement noise: experiment.set_noise(MeasurementNoise(...)) keeps the loop fused - the kernel draws the noise of member
     `member_base` - and a loop that runs step by step for another reason adds the same draws here, after simulate: the same run
-    either way.  set_sigma alone is the reference's np.random noise on the host path, as before; both on one experiment raise."""
+    either way.  set_sigma alone is the reference's np.random noise on the host path, as before; both on one experiment raise.
+    A QCoupledExperiment or QExperiment32 with default settings (_runs_observed) keeps its loop on the device as an observed plant:
+    the same states and controls as the host path returns, to the rounding of the lift and of the loop's conditioning."""
     noise = require_noise(getattr(experiment, "device_noise", None), "mpc (experiment.device_noise)")
     if noise is not None and getattr(experiment, "_sigma", 0):
         raise ValueError("the experiment has both device noise (set_noise) and a non-zero sigma (set_sigma): choose one")
     mf = int(clock.measure_freq)
     x0 = np.asarray(x0, dtype=np.complex128).reshape(-1)
     lift, proj = _loop_maps(experiment)
-    lift_x0 = np.asarray(lift(x0), dtype=np.complex128).reshape(-1)
+    observed = _runs_observed(experiment, exit_condition, streaming, mf)
+    if observed and x0.shape[0] != observe_dims(experiment.observe_kind)[0]:
+        raise ValueError("mpc: x0 has %d entries, the plant state of a %s has %d"
+                         % (x0.shape[0], type(experiment).__name__, observe_dims(experiment.observe_kind)[0]))
+    # (observed plant: the state the first QP sees is the device's own observation of x0, the one it stores as xs[:, 0])
+    lift_x0 = observe_batch(experiment.observe_kind, x0[None])[0] if observed \
+        else np.asarray(lift(x0), dtype=np.complex128).reshape(-1)
     A_x, A_u = model.get_discrete()
     wrapped = WrapModel(A_x, A_u, dim_u, order)          # validates the library size like mpc.py:156
     n = wrapped.dim_x
@@ -209,6 +231,19 @@ def mpc(x0, dim_u, order, X_targ, U_targ, clock, experiment, model, Q, R, Qf, sa
                 solver_warning()                                                               # mpc.py:193-196
             clock.set_endsim(done)
             return _trim(res["xs"][0].T, res["us"][0].T, code, done), model, code
+        if observed:
+            sess.set_observed_plant(experiment.observe_kind, experiment.H0, np.stack(experiment.H1_list), x0[None])
+            sess.run_observed(0, ns)
+            sess.sync()
+            res = sess.results()
+            zs = sess.plant_states()
+            code, done = int(res["exit_codes"][0]), int(res["steps_done"][0])
+            if code == 3:
+                isinf_warning()
+            if code == 2:
+                solver_warning()
+            clock.set_endsim(done)
+            return _trim(zs[0].T, res["us"][0].T, code, done), model, code      # (the plant states, as the host path returns them)
         # host plant: one launch per MPC step, the plant (and lift/proj) evaluated by the caller's object
         xs = [x0]
         us = []
@@ -290,15 +325,32 @@ def check_batch_exit(cond, B, n, plant_kind, where):
 def open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_ops, Q, R, Qf, sat, du=None,
                  max_iter=100, warm_start=True, qp_flags=None, plant_kind=_lib.PLANT_HAMILTONIAN, device=-1,
                  force_complex=False, exact_qp=False, traceless=True, tile=None, generators=None, scales=None,
-                 shared_generators=None, exit_condition=None, noise=None):
+                 shared_generators=None, exit_condition=None, noise=None, observe=None):
     """An EnsembleSession loaded with mpc_batch's arguments (everything resident in HBM, nothing run yet).
     models = None with generators [1+m, n, n] (or [B, 1+m, n, n]) and optional scales [B, 1+m]: the members' models are built on the
     device (discretize_homogeneous of the scaled generators, vectorize.py:8-49), and a set of SHARED generators at order 1 lets the
     closed loop run on them directly where that kernel exists (d = 4; EnsembleSession(shared_generators=...)).
     exit_condition: None or a QuadraticExit the kernel evaluates for every member (EnsembleSession.set_exit_condition).
-    noise: None or a MeasurementNoise the kernel adds to every measured state (EnsembleSession.set_noise)."""
+    noise: None or a MeasurementNoise the kernel adds to every measured state (EnsembleSession.set_noise).
+    observe: None, or an observation kind (observe.py: OBSERVE_PARTIAL_TRACE, OBSERVE_QUBIT_BLOCK) for an observed plant: x0 is then
+    the plant states [B, n_p], plant_op0 / plant_ops the plant's d_p x d_p operators (shared or per member), plant_kind stays at its
+    default, the X0 field is observe_batch(observe, x0) and the loop runs with run_observed (EnsembleSession.set_observed_plant)."""
     x0 = np.ascontiguousarray(x0, dtype=np.complex128)
+    if x0.ndim != 2:
+        raise ValueError("open_session: x0 must have shape (B, n), got %s" % (x0.shape,))
     Bn, n = x0.shape
+    z0 = None
+    if observe is not None:
+        # every shape is checked here, before the library is touched
+        n = observe_dims(observe)[1]
+        if plant_kind != _lib.PLANT_HAMILTONIAN:
+            raise ValueError("open_session: with observe= the plant is the observed (Hamiltonian) plant: leave plant_kind at its default")
+        if getattr(clock, "measure_freq", 1) != 1:
+            raise ValueError("open_session: an observed plant is measured at every step (measure_freq=%d)" % clock.measure_freq)
+        if exit_condition is not None or noise is not None:
+            raise ValueError("open_session: exit conditions and measurement noise are not evaluated on the device for observed plants")
+        plant_op0, plant_ops, _, z0 = check_observed_plant(observe, Bn, n, dim_u, plant_op0, plant_ops, x0, "open_session")
+        plant_kind = _lib.PLANT_NONE
     check_batch_exit(exit_condition, Bn, n, plant_kind, "open_session")
     check_batch_noise(noise, Bn, n, plant_kind, "open_session")
     if models is None:
@@ -316,7 +368,7 @@ def open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, pla
         op0 = op0[None]
     if ops.ndim == 3:
         ops = ops[None]
-    per_plant = op0.shape[0] > 1 or ops.shape[0] > 1
+    per_plant = z0 is None and (op0.shape[0] > 1 or ops.shape[0] > 1)        # (an observed plant's operators are not session fields)
     if per_plant:
         op0 = np.broadcast_to(op0, (Bn,) + op0.shape[1:])
         ops = np.broadcast_to(ops, (Bn,) + ops.shape[1:])
@@ -330,7 +382,9 @@ def open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, pla
     try:
         if models is None:
             sess.build_models(clock.dt, generators, scales)
-        sess.load_problem(models, x0, X_targ, U_targ, Q, R, Qf, op0, ops)
+        sess.load_problem(models, x0 if z0 is None else observe_batch(observe, z0), X_targ, U_targ, Q, R, Qf, op0, ops)
+        if z0 is not None:
+            sess.set_observed_plant(observe, plant_op0, plant_ops, z0)
         if exit_condition is not None:
             sess.set_exit_condition(exit_condition)
         if noise is not None:
@@ -344,7 +398,7 @@ def open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, pla
 def mpc_batch(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_ops, Q, R, Qf, sat, du=None,
               max_iter=100, warm_start=True, qp_flags=None, plant_kind=_lib.PLANT_HAMILTONIAN, device=-1,
               force_complex=False, exact_qp=False, traceless=True, tile=None, generators=None, scales=None, shared_generators=None,
-              exit_condition=None, noise=None):
+              exit_condition=None, noise=None, observe=None):
     """B independent closed loops in one launch.
     x0 [B, n]; models [B|1, n, n(1+P)] (or None with generators / scales: built on the device, see open_session);
     X_targ (n, cols) / U_targ (m, cols) shared (or [B, ...] each);
@@ -354,13 +408,21 @@ def mpc_batch(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_
     exit_condition: None or a QuadraticExit, evaluated on the device; a member it stops has exit code 1 and steps_done = the step
     after which it fired (that step's entries are dropped, as mpc() drops them).
     noise: None or a MeasurementNoise: measurement noise drawn on the device for every member and measured step (kind "iid" runs
-    the complex path); member b of this call is member noise.member_base + b of the generator."""
+    the complex path); member b of this call is member noise.member_base + b of the generator.
+    observe: None or an observation kind for an observed plant (open_session): x0 holds the plant states [B, n_p]; the loop stays
+    on the device, two launches per step; the dict gains "zs" [B, n_p, n_steps+1], the plant states, and "xs" holds the observed
+    states the QPs saw."""
     sess = open_session(x0, models, dim_u, order, X_targ, U_targ, clock, plant_op0, plant_ops, Q, R, Qf, sat, du, max_iter,
                         warm_start, qp_flags, plant_kind, device, force_complex, exact_qp, traceless, tile, generators, scales,
-                        shared_generators, exit_condition, noise)
+                        shared_generators, exit_condition, noise, observe)
     try:
-        sess.run(0, clock.n_steps)
+        if observe is not None:
+            sess.run_observed(0, clock.n_steps)
+        else:
+            sess.run(0, clock.n_steps)
         res = sess.results()
+        if observe is not None:
+            res["zs"] = np.swapaxes(sess.plant_states(), 1, 2)
         res["path"] = sess.path()
         res["path_detail"] = sess.path_detail()
         res["kernel_ms"] = sess.kernel_ms()[0]

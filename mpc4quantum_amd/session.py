@@ -7,6 +7,7 @@ import numpy as np
 from . import _lib
 from .exit_condition import require_device_exit
 from .noise import check_batch_noise
+from .observe import check_observed_plant, observe_dims
 
 _DTYPES = {
     _lib.F_MODELS: np.complex128, _lib.F_X0: np.complex128, _lib.F_X_TARG: np.complex128, _lib.F_U_TARG: np.float64,
@@ -62,6 +63,7 @@ class EnsembleSession:
         self._L = _lib.lib()
         _lib.check(self._L.m4q_session_create(C.byref(p), self.B, int(device), C.byref(self._h)))
         self._keep = {}
+        self.observe = 0              # the observation kind once set_observed_plant has been called
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -148,6 +150,51 @@ class EnsembleSession:
     def run(self, step_begin=0, step_end=None):
         _lib.check(self._L.m4q_session_run(self._h, int(step_begin), int(self.problem.n_steps if step_end is None else step_end)))
 
+    def set_observed_plant(self, kind, op0, ops, z0):
+        """Give a PLANT_NONE session an observed plant (observe.py; m4q_session_set_observed_plant): plant states z0 [B, n_p] that
+        evolve by the Hamiltonian plant's arithmetic under op0 [B|1, d_p, d_p] and ops [B|1, m, d_p, d_p], and the loop state
+        x = observe(z).  Writes zs[:, 0] = z0 and xs[:, 0] = observe(z0); the X0 field is the caller's (observe_batch(kind, z0):
+        load_problem).  Before the first run, measure_freq 1.  Every shape is checked here, before the library is touched."""
+        p = self.problem
+        if p.plant_kind != _lib.PLANT_NONE:
+            raise ValueError("EnsembleSession.set_observed_plant: the session has a device plant (plant_kind=%d); an observed plant "
+                             "is a setting of a PLANT_NONE session" % p.plant_kind)
+        if p.measure_freq > 1:
+            raise ValueError("EnsembleSession.set_observed_plant: measure_freq=%d; an observed plant is measured at every step"
+                             % p.measure_freq)
+        op0, ops, per, z0 = check_observed_plant(kind, self.B, p.dim_x, p.dim_u, op0, ops, z0, "EnsembleSession.set_observed_plant")
+        _lib.check(self._L.m4q_session_set_observed_plant(self._h, int(kind), op0.ctypes.data_as(_lib._dp), ops.ctypes.data_as(_lib._dp),
+                                                          per, z0.ctypes.data_as(_lib._dp)))
+        self.observe = int(kind)
+
+    def _need_observed(self, where):
+        if not self.observe:
+            raise ValueError("EnsembleSession.%s: no observed plant is set (set_observed_plant)" % where)
+
+    def run_observed(self, step_begin=0, step_end=None):
+        """run() for a session with an observed plant (m4q_session_run_observed): for every step of the range one MPC launch, then
+        the kernel that advances the plant and writes the observed state into xs[:, step + 1], all on the session's stream with no
+        host round trip in between."""
+        self._need_observed("run_observed")
+        _lib.check(self._L.m4q_session_run_observed(self._h, int(step_begin),
+                                                    int(self.problem.n_steps if step_end is None else step_end)))
+
+    def plant_states(self):
+        """zs [B, n_steps + 1, n_p]: the plant states of a session with an observed plant (columns beyond steps_done are zero)."""
+        self._need_observed("plant_states")
+        out = np.empty((self.B, self.problem.n_steps + 1, observe_dims(self.observe)[0]), dtype=np.complex128)
+        _lib.check(self._L.m4q_session_plant_states(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def put_plant_states(self, zs):
+        """Inverse of plant_states() (restore)."""
+        self._need_observed("put_plant_states")
+        shape = (self.B, self.problem.n_steps + 1, observe_dims(self.observe)[0])
+        a = np.ascontiguousarray(zs, dtype=np.complex128)
+        if a.shape != shape:
+            raise ValueError("EnsembleSession.put_plant_states: zs must have shape %s, got %s" % (shape, a.shape))
+        _lib.check(self._L.m4q_session_put_plant_states(self._h, a.ctypes.data_as(C.c_void_p), a.nbytes))
+
     def sync(self):
         _lib.check(self._L.m4q_session_sync(self._h))
 
@@ -208,17 +255,24 @@ class EnsembleSession:
             self.upload(_lib.F_OPS, ops)
 
     def state(self):
-        """Everything a run needs to resume at MPC step k (checkpoint): states, controls, SQP guesses, codes."""
+        """Everything a run needs to resume at MPC step k (checkpoint): states, controls, SQP guesses, codes - and the plant states
+        "zs" of a session with an observed plant (only then)."""
         p = self.problem
         B, n, m, ns, T = self.B, p.dim_x, p.dim_u, p.n_steps, p.horizon
-        return {
+        st = {
             "xs": self.download(_lib.F_XS, (B, ns + 1, n)), "us": self.download(_lib.F_US, (B, ns, m)),
             "x_guess": self.download(_lib.F_X_GUESS, (B, T + 1, n)), "u_guess": self.download(_lib.F_U_GUESS, (B, T, m)),
             "exit_codes": self.download(_lib.F_CODES, (B,)), "steps_done": self.download(_lib.F_STEPS_DONE, (B,)),
         }
+        if self.observe:
+            st["zs"] = self.plant_states()
+        return st
 
     def restore(self, state):
-        """Inverse of state(): afterwards run(k, ...) continues a run interrupted before step k."""
+        """Inverse of state(): afterwards run(k, ...) continues a run interrupted before step k.  A session with an observed plant
+        (set_observed_plant first: the operators are a setting, not part of the state) takes the plant states "zs" too."""
+        if self.observe:
+            self.put_plant_states(state["zs"])
         self.upload(_lib.F_XS, state["xs"])
         self.upload(_lib.F_US, state["us"])
         self.upload(_lib.F_X_GUESS, state["x_guess"])
