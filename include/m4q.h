@@ -262,6 +262,32 @@ M4Q_API int m4q_dmdc_fit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t 
                        const double* u, int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R,
                        double* models, int32_t* ranks, double* svals, int32_t* status);
 
+/* The same fit, same arguments and results, from a QR of the data themselves and not from their Gram matrix: the error of A is
+ * O(eps kappa) where m4q_dmdc_fit_batch's is O(eps kappa^2), and ranks are decided down to rcond = 1e-12.  Prefer it when the data
+ * are ill-conditioned (noise-free trajectories, cut-offs at the low end of the training grid) or rcond < 1e-7 is wanted;
+ * m4q_dmdc_fit_batch is the cheaper one.  mpc4quantum_amd/fit.py (dmdc_fit_qr_reference) is the definition, in NumPy, in the
+ * kernel's order of operations.  Per member:
+ * - every snapshot (e outer, t inner) contributes the row (z^H | x_{t+1}^H), rotated into R [nz][nz] (upper triangular, from 0) and
+ *   T [nz][n] (from 0) by Givens rotations j = 0 .. nz-1: with a = R[j][j], b = row[j] (skipped when b = 0),
+ *   h = sqrt(|a|^2 + |b|^2), c = a / h, s = b / h: R[j][j:] <- conj(c) R[j][j:] + conj(s) row[j:], row[j:] <- c row[j:] - s R[j][j:],
+ *   the same on T[j] and the right-hand side.  Then Z^H = Q R and T = Q^H Y^H.
+ * - one-sided (Hestenes) Jacobi on the columns of M = R, V = I accumulated, pairs cyclic by rows: with a_pp = m_p^H m_p,
+ *   a_qq = m_q^H m_q, g = m_p^H m_q the rotation and the skip rule (|g| <= eps sqrt(a_pp a_qq)) of m4q_dmdc_fit_batch; the iteration
+ *   stops after a sweep without rotations, 30 sweeps at the most.
+ * - lam_k = m_k^H m_k; svals = sqrt(lam) descending (no second pass over the data); for each rconds[r] the k with
+ *   lam_k > rconds[r]^2 max(lam) give A_r = sum_k (T^H m_k / lam_k) v_k^H.
+ * rconds each in [M4Q_FIT_QR_RCOND_MIN, 1) = [1e-12, 1): the singular values come out to a few eps s_0, so a cut-off a factor 1.2
+ * from every singular value is decidable down to about 1e3 eps; numpy's default 1e-15 lies inside the rounding of the data
+ * themselves and stays a host call (DiscrepDMDc.from_data).
+ * status [B]: 0 ok, 1 the Jacobi iteration hit its cap (the models are written from the last iterate), 3 non-finite data (R or T
+ * holds a non-finite entry: zero models and singular values, rank 0).
+ * M4Q_E_BADARG and M4Q_E_UNSUPPORTED: the argument classes of m4q_dmdc_fit_batch, with this entry point's rcond range (R, V and T
+ * take the room of G, V and C, so the same shapes fit).  Arguments are checked before the device is asked for. */
+#define M4Q_FIT_QR_RCOND_MIN 1e-12
+M4Q_API int m4q_dmdc_fit_qr_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs,
+                          const double* u, int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R,
+                          double* models, int32_t* ranks, double* svals, int32_t* status);
+
 /* Recursive DMDc updates for an ensemble in ONE launch: OnlineDMDc.fit_iteration (model.py:216-313, recursive least squares with a
  * forgetting factor) fed with every snapshot of B members - what mpc(..., streaming=True) does to its model, for an ensemble.
  * mpc4quantum_amd/online.py (online_dmdc_reference) is the definition, in NumPy, in the kernel's order of operations.

@@ -5,7 +5,7 @@ linearize, model, mpc, vectorize), backed by hand-written HIP kernels in libm4q_
 from .exit_condition import QuadraticExit  # noqa: F401
 from .experiment import (Experiment, LExperiment, QCoupledExperiment, QExperiment, QExperiment32, QSynthesis,  # noqa: F401
                          isqrt, plant_step_batch, process_dim, split_blocks)
-from .fit import dmdc_fit_batch, dmdc_fit_reference, train_models_batch  # noqa: F401
+from .fit import dmdc_fit_batch, dmdc_fit_qr_reference, dmdc_fit_reference, train_models_batch  # noqa: F401
 from .grad import (model_rollout_grad_batch, model_rollout_grad_reference, ordered_weighted_sum,  # noqa: F401
                    plant_rollout_grad_batch, plant_rollout_grad_reference)
 from .library import (create_library, create_library_from_list, create_power_list, diff_library, krtimes,  # noqa: F401

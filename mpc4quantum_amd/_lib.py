@@ -75,6 +75,7 @@ PROTOTYPES = {
     "m4q_model_rollout_grad_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _i32, _dp,
                                                _i32, _dp, _dp, _dp, _dp]),
     "m4q_dmdc_fit_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _ip]),
+    "m4q_dmdc_fit_qr_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _ip]),
     "m4q_online_dmdc_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _i32, _dp, _i32, C.c_double,
                                         _dp, _i32, _i32, _i32, _dp, _dp, _dp, _dp, _ip]),
     "m4q_mpc_batch": (C.c_int, [C.POINTER(Problem), _i32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip,

@@ -253,6 +253,7 @@ struct ShapeOps {
   int observe_kind;                                                // the observation whose loop state has this dim_x (0: none)
   int (*launch_observe)(const ObserveArgs&, hipStream_t);          // (shapes with an observe_kind; depends on dim_x alone)
   int (*launch_observed_plant)(const ObsPlantArgs&, hipStream_t);  // (... and on dim_u: the plant has the shape's controls)
+  int (*launch_fit_qr)(const FitArgs&, hipStream_t);               // dmdc_fit_qr_kernel: the shapes and the LDS of launch_fit
 };
 
 }  // namespace m4q

@@ -1342,21 +1342,25 @@ int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
   return st.finish(sh->launch_model_grad(a, nullptr), "model rollout gradient");
 }
 
-int m4q_dmdc_fit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs, const double* u,
-                       int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R, double* models, int32_t* ranks,
-                       double* svals, int32_t* status) {
+// the two routes of the DMDc fit share their arguments, their checks and their staging: qr names m4q_dmdc_fit_qr_batch
+static int dmdc_fit(const char* who, bool qr, int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs,
+                    const double* u, int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R, double* models,
+                    int32_t* ranks, double* svals, int32_t* status) {
   const m4q::ShapeOps* sh = find_shape(dim_x, dim_u, order);
   if (!sh) return fail(M4Q_E_UNSUPPORTED, "no model kernel for dim_x=%d dim_u=%d order=%d", dim_x, dim_u, order);
   if (sh->fit_lds_bytes == 0)
-    return fail(M4Q_E_UNSUPPORTED, "m4q_dmdc_fit_batch: the Gram data of dim_x=%d dim_u=%d order=%d (nz = %d) do not fit one workgroup's "
-                "LDS; fit such models on the host (DiscrepDMDc.from_data)", dim_x, dim_u, order, dim_x * (1 + sh->np));
-  if (B < 1 || E < 1 || N < 1) return fail(M4Q_E_BADARG, "m4q_dmdc_fit_batch: B, E and N must be at least 1 (got %d, %d, %d)", B, E, N);
-  if (R < 1 || R > M4Q_FIT_MAX_RCONDS) return fail(M4Q_E_BADARG, "m4q_dmdc_fit_batch: R must be 1..%d, got %d", M4Q_FIT_MAX_RCONDS, R);
-  if (!xs || !u || !rconds || !models || !status) return fail(M4Q_E_BADARG, "m4q_dmdc_fit_batch: xs, u, rconds, models and status are required");
+    return fail(M4Q_E_UNSUPPORTED, "%s: the %s data of dim_x=%d dim_u=%d order=%d (nz = %d) do not fit one workgroup's "
+                "LDS; fit such models on the host (DiscrepDMDc.from_data)", who, qr ? "factored" : "Gram", dim_x, dim_u, order,
+                dim_x * (1 + sh->np));
+  if (B < 1 || E < 1 || N < 1) return fail(M4Q_E_BADARG, "%s: B, E and N must be at least 1 (got %d, %d, %d)", who, B, E, N);
+  if (R < 1 || R > M4Q_FIT_MAX_RCONDS) return fail(M4Q_E_BADARG, "%s: R must be 1..%d, got %d", who, M4Q_FIT_MAX_RCONDS, R);
+  if (!xs || !u || !rconds || !models || !status) return fail(M4Q_E_BADARG, "%s: xs, u, rconds, models and status are required", who);
+  const double rcond_min = qr ? M4Q_FIT_QR_RCOND_MIN : M4Q_FIT_RCOND_MIN;
   for (int r = 0; r < R; ++r)
-    if (!(rconds[r] >= M4Q_FIT_RCOND_MIN && rconds[r] < 1.0))
-      return fail(M4Q_E_BADARG, "m4q_dmdc_fit_batch: rconds[%d] = %g is outside [%g, 1): below that the cut-off lies in the Gram matrix's "
-                  "rounding floor (fit on the host with DiscrepDMDc.from_data)", r, rconds[r], M4Q_FIT_RCOND_MIN);
+    if (!(rconds[r] >= rcond_min && rconds[r] < 1.0))
+      return fail(M4Q_E_BADARG, "%s: rconds[%d] = %g is outside [%g, 1): below that the cut-off lies in the %s "
+                  "(fit on the host with DiscrepDMDc.from_data)", who, r, rconds[r], rcond_min,
+                  qr ? "rounding of the data themselves" : "Gram matrix's rounding floor");
   if (int rc = need_device()) return rc;
   const size_t n = dim_x, m = dim_u, nz = n * (1 + (size_t)sh->np);
   const Extent eu(B, u_per_instance, (size_t)E * N * m);
@@ -1372,7 +1376,21 @@ int m4q_dmdc_fit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, i
   if (svals) a.svals = st.out<double>(svals, (size_t)B * nz);
   a.status = st.out<int>(status, B);
   if (st.error()) return st.error();
-  return st.finish(sh->launch_fit(a, nullptr), "DMDc fit");
+  return qr ? st.finish(sh->launch_fit_qr(a, nullptr), "DMDc fit (QR)") : st.finish(sh->launch_fit(a, nullptr), "DMDc fit");
+}
+
+int m4q_dmdc_fit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs, const double* u,
+                       int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R, double* models, int32_t* ranks,
+                       double* svals, int32_t* status) {
+  return dmdc_fit("m4q_dmdc_fit_batch", false, B, dim_x, dim_u, order, E, N, xs, u, u_per_instance, u_scale, rconds, R, models, ranks, svals,
+                  status);
+}
+
+int m4q_dmdc_fit_qr_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs, const double* u,
+                          int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R, double* models, int32_t* ranks,
+                          double* svals, int32_t* status) {
+  return dmdc_fit("m4q_dmdc_fit_qr_batch", true, B, dim_x, dim_u, order, E, N, xs, u, u_per_instance, u_scale, rconds, R, models, ranks,
+                  svals, status);
 }
 
 int m4q_online_dmdc_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs, const double* u,

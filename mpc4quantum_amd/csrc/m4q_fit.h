@@ -230,6 +230,43 @@ __device__ __forceinline__ void fit_svals(const FitArgs& a, long b, cplx* lds, i
   wave_sync();
 }
 
+// The truncated products of phase 3, shared with the QR route (m4q_fit_qr.h): C holds W[:, k] / lam_k, LAM the spectrum and lmax
+// its maximum; per rcond A = sum_{lam_k > rcond^2 lmax} C[:, k] V[:, k]^H, lane l on column l of A.  ok = false: zero models and ranks.
+template <int NX, int NU, int ORDER>
+__device__ __forceinline__ void fit_truncate(const FitArgs& a, long b, cplx* lds, int lane, bool ok, double lmax) {
+  using L = FitLayout<NX, NU, ORDER>;
+  constexpr int NZ = L::NZ, PITCH = L::PITCH;
+  const cplx* V = lds + L::V;
+  const cplx* C = lds + L::C;
+  const double* LAM = reinterpret_cast<const double*>(lds + L::LAM);
+  const bool act = lane < NZ;
+  const int l = act ? lane : NZ - 1;
+  cplx acc[NX];
+  for (int r = 0; r < a.R; ++r) {
+    const double rc = gld(a.rconds, r);
+    const double thr = (rc * rc) * lmax;
+    int rank = 0;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) acc[i] = czero();
+    if (uniform(ok)) {
+#pragma unroll 1
+      for (int k = 0; k < NZ; ++k) {
+        if (!uniform(LAM[k] > thr)) continue;
+        ++rank;
+        const cplx v = cconj(V[l * PITCH + k]);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) cmac(acc[i], C[i * PITCH + k], v);
+      }
+    }
+    const long m0 = ((long)r * a.B + b) * NX * NZ;
+    if (act) {
+#pragma unroll
+      for (int i = 0; i < NX; ++i) gst(a.models, m0 + i * NZ + l, acc[i]);
+    }
+    if (lane == 0 && a.ranks) gst(a.ranks, (long)r * a.B + b, rank);
+  }
+}
+
 // Phase 3: eigenvalues, then per rcond the truncated product
 // A = sum_{lam_k > rcond^2 max(lam)} (W[:, k] / lam_k) V[:, k]^H with W = C V; lane l holds column l of A and stores it along the nz
 // axis (coalesced).  ok = false: zero models and ranks.
@@ -268,29 +305,7 @@ __device__ __forceinline__ void fit_models(const FitArgs& a, long b, cplx* lds, 
     }
     wave_sync();
   }
-  for (int r = 0; r < a.R; ++r) {
-    const double rc = gld(a.rconds, r);
-    const double thr = (rc * rc) * lmax;
-    int rank = 0;
-#pragma unroll
-    for (int i = 0; i < NX; ++i) acc[i] = czero();
-    if (uniform(ok)) {
-#pragma unroll 1
-      for (int k = 0; k < NZ; ++k) {
-        if (!uniform(LAM[k] > thr)) continue;
-        ++rank;
-        const cplx v = cconj(V[l * PITCH + k]);
-#pragma unroll
-        for (int i = 0; i < NX; ++i) cmac(acc[i], C[i * PITCH + k], v);
-      }
-    }
-    const long m0 = ((long)r * a.B + b) * NX * NZ;
-    if (act) {
-#pragma unroll
-      for (int i = 0; i < NX; ++i) gst(a.models, m0 + i * NZ + l, acc[i]);
-    }
-    if (lane == 0 && a.ranks) gst(a.ranks, (long)r * a.B + b, rank);
-  }
+  fit_truncate<NX, NU, ORDER>(a, b, lds, lane, ok, lmax);
 }
 
 }  // namespace m4q

@@ -7,6 +7,7 @@
 #include "m4q_args.h"
 #include "m4q_mpc.h"
 #include "m4q_fit.h"
+#include "m4q_fit_qr.h"
 #include "m4q_online.h"
 #include "m4q_grad.h"
 #include "m4q_noise.h"
@@ -1456,6 +1457,25 @@ __global__ __launch_bounds__(64) void dmdc_fit_kernel(FitArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// DMDc identification of B members from a QR of their data (m4q_dmdc_fit_qr_batch; fit.py: dmdc_fit_qr_reference is the
+// definition): the frame and the LDS layout of dmdc_fit_kernel, R, V and T in the places of G, V and C (m4q_fit_qr.h).
+// ---------------------------------------------------------------------------------------------
+template <int NX_, int NU_, int ORDER_>
+__global__ __launch_bounds__(64) void dmdc_fit_qr_kernel(FitArgs a) {
+  using L = FitLayout<NX_, NU_, ORDER_>;
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const int lane = threadIdx.x;
+  for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
+    wave_sync();                                   // the previous member's reads are done
+    const bool finite = fit_qr_factor<NX_, NU_, ORDER_>(a, b, lds, lane);
+    bool converged = true;
+    if (uniform(finite)) converged = fit_qr_jacobi<L::NZ, L::PITCH>(lds + L::G, lds + L::V, lane);
+    fit_qr_models<NX_, NU_, ORDER_>(a, b, lds, lane, finite);
+    if (lane == 0) gst(a.status, b, !finite ? 3 : converged ? 0 : 1);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Recursive DMDc updates of B members (m4q_online_dmdc_batch; online.py: online_dmdc_reference is the definition): the frame of
 // dmdc_fit_kernel, the model A and the inverse Gram matrix P in dynamic LDS from the first snapshot to the last (OnlineLayout,
 // m4q_online.h).  HERM_: the conjugated form.
@@ -1961,6 +1981,7 @@ static int launch_model_rollout(const RollArgs& a, hipStream_t s) { return launc
 template <bool FITS, int N_ = NX>
 struct FitLaunch {
   static int run(const FitArgs&, hipStream_t) { return UNBUILT; }
+  static int run_qr(const FitArgs&, hipStream_t) { return UNBUILT; }
 };
 template <int N_>
 struct FitLaunch<true, N_> {
@@ -1971,10 +1992,18 @@ struct FitLaunch<true, N_> {
     hipLaunchKernelGGL((dmdc_fit_kernel<N_, NU, ORDER>), dim3(a.B < 4096 ? a.B : 4096), dim3(64), lds, s, a);
     return -(int)hipGetLastError();
   }
+  static int run_qr(const FitArgs& a, hipStream_t s) {
+    constexpr size_t lds = FitLayout<N_, NU, ORDER>::BYTES;
+    int rc = prep_lds(dmdc_fit_qr_kernel<N_, NU, ORDER>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((dmdc_fit_qr_kernel<N_, NU, ORDER>), dim3(a.B < 4096 ? a.B : 4096), dim3(64), lds, s, a);
+    return -(int)hipGetLastError();
+  }
 };
 constexpr bool FIT_FITS = FitLayout<NX, NU, ORDER>::FITS;
 constexpr int FIT_LDS = FIT_FITS ? (int)FitLayout<NX, NU, ORDER>::BYTES : 0;
 static int launch_fit(const FitArgs& a, hipStream_t s) { return FitLaunch<FIT_FITS>::run(a, s); }
+static int launch_fit_qr(const FitArgs& a, hipStream_t s) { return FitLaunch<FIT_FITS>::run_qr(a, s); }
 template <bool FITS, int N_ = NX>
 struct OnlineLaunch {
   static int run(const OnlineArgs&, int, hipStream_t) { return UNBUILT; }
@@ -2019,6 +2048,7 @@ static int launch_observe(const ObserveArgs&, hipStream_t) { return UNBUILT; }
 static int launch_observed_plant(const ObsPlantArgs&, hipStream_t) { return UNBUILT; }
 constexpr int FIT_LDS = 0;
 static int launch_fit(const FitArgs&, hipStream_t) { return UNBUILT; }
+static int launch_fit_qr(const FitArgs&, hipStream_t) { return UNBUILT; }
 constexpr int ONLINE_LDS = 0;
 static int launch_online(const OnlineArgs&, int, hipStream_t) { return UNBUILT; }
 static int launch_linearize(const LinArgs&, hipStream_t) { return UNBUILT; }
@@ -2142,7 +2172,7 @@ static const ShapeOps* shape_ops() {
 #endif
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
-                               ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant};
+                               ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr};
   return &ops;
 }
 

@@ -24,6 +24,23 @@ The decomposition is done once, every rcond costs one truncated product.  rcond 
 the cut-off rcond^2 sits in the Gram matrix's own rounding floor (~ nz eps relative to max(lam)) and the rank is no longer
 decidable from G.  The host `DiscrepDMDc.from_data` (an SVD of Z itself) remains the path for rcond = 1e-15.
 
+The QR route (method="qr", m4q_dmdc_fit_qr_batch; dmdc_fit_qr_reference is its definition, csrc/m4q_fit_qr.h reproduces it) takes
+the same fit from the data themselves, so that its error is O(eps kappa) and not O(eps kappa^2):
+  QR          R = 0 [nz, nz], T = 0 [nz, n]; every snapshot, in the same order, contributes the row (z^H | x_{t+1}^H), rotated in by
+              Givens rotations j = 0 .. nz - 1: a = R[j, j], b = row[j] (skipped when b == 0), h = sqrt(|a|^2 + |b|^2), c = a / h,
+              s = b / h, R[j, j:] <- conj(c) R[j, j:] + conj(s) row[j:], row[j:] <- c row[j:] - s R[j, j:] (the old R[j, j:]), the same
+              on T[j] and the right-hand side.  Then Z^H = Q R, T = Q^H Y^H, and R has Z's singular values.  (Rows z^T | y^T and a
+              conjugate on the final product would be the same numbers, bit for bit.)
+  spectrum    one-sided (Hestenes) Jacobi on the columns of M = R, V = I accumulated, pairs cyclic by rows: a_pp = m_p^H m_p,
+              a_qq = m_q^H m_q, g = m_p^H m_q (each a lane_sum over the nz axis); skipped when |g|^2 <= eps^2 a_pp a_qq, otherwise
+              jacobi_hermitian's rotation on columns p, q of M and V; the same stopping rule and cap.
+  models      lam_k = m_k^H m_k; per rcond keep lam_k > rcond^2 max(lam); A = sum over the kept k, ascending, of
+              (W[:, k] / lam_k) V[:, k]^H with W = T^H M.  svals = sqrt(lam) descending: no second pass, this route has no floor.
+rcond must lie in [RCOND_MIN_QR, 1) = [1e-12, 1): the singular values come out to a few eps s_0, so a cut-off a factor 1.2 from every
+singular value is decidable down to about 1e3 eps; numpy's default 1e-15 lies inside the rounding of the data themselves and stays
+a host call.  status 3: R or T has a non-finite entry.  Data that are exactly rank-deficient (fewer snapshots than nz) can reach the
+cap: null columns are rotated until they underflow; the models at the cap are good.
+
 status per member: 0 ok; 1 the Jacobi iteration hit its cap (the models are written from the last iterate); 3 non-finite data
 (G or C has a non-finite entry, which any non-finite sample produces): the models are zero and the rank is 0."""
 import numpy as np
@@ -33,6 +50,8 @@ from .library import create_power_list, size_of_library
 from .rollout import model_rollout_batch
 
 RCOND_MIN = 1e-7
+RCOND_MIN_QR = 1e-12
+METHODS = ("gram", "qr")
 MAX_RCONDS = 16
 MAX_SWEEPS = 30
 _EPS = float(np.finfo(np.float64).eps)
@@ -132,15 +151,10 @@ def singular_values(V, Z):
     return np.sqrt(np.sort(acc)[::-1])
 
 
-def truncated_models(lam, V, C, rconds):
-    """A [R, n, nz] and rank [R] from the spectrum: the sums run over the kept eigenpairs in ascending index."""
-    W = np.zeros(C.shape, dtype=np.complex128)
-    for j in range(V.shape[0]):
-        W += np.outer(C[:, j], V[j, :])
-    with np.errstate(divide="ignore", invalid="ignore"):
-        Wl = W * (1.0 / lam)[None, :]
+def truncated_products(lam, Wl, V, rconds):
+    """A [R, n, nz] and rank [R] from the spectrum and Wl = W / lam: the sums run over the kept k in ascending index."""
     lmax = lam.max()
-    A = np.zeros((len(rconds),) + C.shape, dtype=np.complex128)
+    A = np.zeros((len(rconds),) + Wl.shape, dtype=np.complex128)
     rank = np.zeros(len(rconds), dtype=np.int32)
     for r, rc in enumerate(rconds):
         keep = lam > (rc * rc) * lmax
@@ -150,8 +164,114 @@ def truncated_models(lam, V, C, rconds):
     return A, rank
 
 
-def _check(xs, us, order, rcond, u_scale):
-    """Shapes and values of a fit call; returns (xs [B, E, N + 1, n], us [B|1, E, N, m], u_per, u_scale, rconds, scalar_rcond)."""
+def truncated_models(lam, V, C, rconds):
+    """A [R, n, nz] and rank [R] from the spectrum: the sums run over the kept eigenpairs in ascending index."""
+    W = np.zeros(C.shape, dtype=np.complex128)
+    for j in range(V.shape[0]):
+        W += np.outer(C[:, j], V[j, :])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        Wl = W * (1.0 / lam)[None, :]
+    return truncated_products(lam, Wl, V, rconds)
+
+
+# ---------------------------------------------------------------- the QR route (m4q_dmdc_fit_qr_batch, csrc/m4q_fit_qr.h)
+def givens_qr(Z, Y):
+    """Row-wise Givens QR of the stacked data, one snapshot at a time in their order: the snapshot contributes the row
+    (z^H | y^H) (the conjugated columns of Z [nz, S] and Y [n, S]), rotated into R [nz, nz] (upper triangular, real diagonal)
+    and T [nz, n] by nz dependent rotations.  Afterwards Z^H = Q R and T = Q^H Y^H, and R has Z's singular values."""
+    nz, S = Z.shape
+    R = np.zeros((nz, nz), dtype=np.complex128)
+    T = np.zeros((nz, Y.shape[0]), dtype=np.complex128)
+    for s in range(S):
+        row = Z[:, s].conj()
+        rhs = Y[:, s].conj()
+        for j in range(nz):
+            b = row[j]
+            if b == 0:
+                continue
+            a = R[j, j]
+            h = np.sqrt((a.real * a.real + a.imag * a.imag) + (b.real * b.real + b.imag * b.imag))
+            c = complex(a.real / h, a.imag / h)
+            sn = complex(b.real / h, b.imag / h)
+            cc, sc = c.conjugate(), sn.conjugate()
+            rj, tj = R[j, j:].copy(), T[j].copy()
+            R[j, j:] = cc * rj + sc * row[j:]
+            row[j:] = c * row[j:] - sn * rj
+            T[j] = cc * tj + sc * rhs
+            rhs = c * rhs - sn * tj
+    return R, T
+
+
+def lane_sum(v):
+    """The sum over the nz axis (last, at most 64 long) in the wavefront's order: lane l holds entry l; the 16 lanes of each DPP
+    row are added in ascending order, then the four row sums in ascending order."""
+    pad = np.zeros(v.shape[:-1] + (64,))
+    pad[..., :v.shape[-1]] = v
+    rows = np.cumsum(pad.reshape(v.shape[:-1] + (4, 16)), axis=-1)[..., -1]
+    return ((rows[..., 0] + rows[..., 1]) + rows[..., 2]) + rows[..., 3]
+
+
+def column_products(mp, mq):
+    """(m_p^H m_p, m_q^H m_q, Re m_p^H m_q, Im m_p^H m_q) of two columns, each summed by lane_sum."""
+    return lane_sum(np.stack([mp.real * mp.real + mp.imag * mp.imag, mq.real * mq.real + mq.imag * mq.imag,
+                              mp.real * mq.real + mp.imag * mq.imag, mp.real * mq.imag - mp.imag * mq.real]))
+
+
+def jacobi_one_sided(R):
+    """One-sided (Hestenes) Jacobi on the columns of M = R, cyclic by rows, with jacobi_hermitian's rotation and skip rule applied
+    to the implicit Gram matrix M^H M.  Returns (M [nz, nz], V [nz, nz], sweeps, converged): R V = M, the columns of M
+    orthogonal; `sweeps` counts every sweep made, the last, all-skipped one included."""
+    M = np.array(R, dtype=np.complex128)
+    nz = M.shape[0]
+    V = np.eye(nz, dtype=np.complex128)
+    for sweep in range(1, MAX_SWEEPS + 1):
+        rotated = False
+        for p in range(nz - 1):
+            for q in range(p + 1, nz):
+                mp, mq = M[:, p].copy(), M[:, q].copy()
+                app, aqq, gre, gim = column_products(mp, mq)
+                m2 = gre * gre + gim * gim
+                if m2 <= _EPS * _EPS * (app * aqq):
+                    continue
+                rotated = True
+                absg = np.sqrt(m2)
+                w = complex(gre / absg, gim / absg)
+                tau = (aqq - app) / (2.0 * absg)
+                t = (1.0 if tau >= 0.0 else -1.0) / (abs(tau) + np.sqrt(1.0 + tau * tau))
+                c = 1.0 / np.sqrt(1.0 + t * t)
+                sw = complex(t * c * w.real, t * c * w.imag)
+                M[:, p] = c * mp - sw.conjugate() * mq
+                M[:, q] = sw * mp + c * mq
+                vp, vq = V[:, p].copy(), V[:, q].copy()
+                V[:, p] = c * vp - sw.conjugate() * vq
+                V[:, q] = sw * vp + c * vq
+        if not rotated:
+            return M, V, sweep, True
+    return M, V, MAX_SWEEPS, False
+
+
+def qr_models(M, V, T, rconds):
+    """(A [R, n, nz], rank [R], lam [nz]) from the orthogonalised factor: lam_k = m_k^H m_k (lane_sum), W = T^H M summed over the
+    rows in ascending index, A = sum over the kept k, ascending, of (W[:, k] / lam_k) V[:, k]^H."""
+    lam = lane_sum((M.real * M.real + M.imag * M.imag).T)
+    W = np.zeros((T.shape[1], M.shape[0]), dtype=np.complex128)
+    for j in range(M.shape[0]):
+        W += np.outer(T[j].conj(), M[j, :])
+    with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+        Wl = W * (1.0 / lam)[None, :]
+    A, rank = truncated_products(lam, Wl, V, rconds)
+    return A, rank, lam
+
+
+def _method(method):
+    if method not in METHODS:
+        raise ValueError("method must be one of %s, got %r" % (METHODS, method))
+    return method
+
+
+def _check(xs, us, order, rcond, u_scale, method="gram"):
+    """Shapes and values of a fit call; returns (xs [B, E, N + 1, n], us [B|1, E, N, m], u_per, u_scale, rconds, scalar_rcond).
+    The rcond range is the method's: [RCOND_MIN, 1) for "gram", [RCOND_MIN_QR, 1) for "qr"."""
     order = int(order)
     if order < 1:
         raise ValueError("order must be at least 1, got %d" % order)
@@ -181,7 +301,12 @@ def _check(xs, us, order, rcond, u_scale):
     rconds = np.ascontiguousarray(rc.reshape(-1) if rc.ndim <= 1 else rc)
     if rconds.ndim != 1 or not 1 <= rconds.shape[0] <= MAX_RCONDS:
         raise ValueError("rcond must be a scalar or a 1-D array of 1 to %d values, got shape %s" % (MAX_RCONDS, rc.shape))
-    if not np.all((rconds >= RCOND_MIN) & (rconds < 1.0)):
+    if method == "qr":
+        if not np.all((rconds >= RCOND_MIN_QR) & (rconds < 1.0)):
+            raise ValueError("rcond must lie in [%g, 1) with method=\"qr\": below that (numpy's default 1e-15 included) the cut-off "
+                             "is inside the rounding of the data themselves (use the host DiscrepDMDc.from_data), got %s"
+                             % (RCOND_MIN_QR, rconds))
+    elif not np.all((rconds >= RCOND_MIN) & (rconds < 1.0)):
         raise ValueError("rcond must lie in [%g, 1): below that the cut-off is in the Gram matrix's rounding floor (use the host "
                          "DiscrepDMDc.from_data), got %s" % (RCOND_MIN, rconds))
     return xs, us, u_per, u_scale, rconds, scalar, order
@@ -221,15 +346,48 @@ def dmdc_fit_reference(xs, us, order, rcond, u_scale=None):
     return out
 
 
-def dmdc_fit_batch(xs, us, order, rcond, u_scale=None):
+def dmdc_fit_qr_reference(xs, us, order, rcond, u_scale=None):
+    """The QR route's definition in NumPy, member by member (the module docstring's last part).  Arguments and result as
+    dmdc_fit_batch(method="qr"), plus "sweeps" [B]."""
+    xs, us, u_per, u_scale, rconds, scalar, order = _check(xs, us, order, rcond, u_scale, "qr")
+    B, E, N1, n = xs.shape
+    nz = n * size_of_library(order, us.shape[3])
+    R = rconds.shape[0]
+    models = np.zeros((R, B, n, nz), dtype=np.complex128)
+    rank = np.zeros((R, B), dtype=np.int32)
+    svals = np.zeros((B, nz))
+    status = np.zeros(B, dtype=np.int32)
+    sweeps = np.zeros(B, dtype=np.int32)
+    for b in range(B):
+        u = us[b if u_per else 0]
+        if u_scale is not None:
+            u = u_scale[b] * u
+        with np.errstate(all="ignore"):
+            Z, Y = stack_snapshots(xs[b], u, order)
+            Rf, T = givens_qr(Z, Y)
+        if not (np.all(np.isfinite(Rf)) and np.all(np.isfinite(T))):
+            status[b] = 3
+            continue
+        M, V, sweeps[b], converged = jacobi_one_sided(Rf)
+        status[b] = 0 if converged else 1
+        models[:, b], rank[:, b], lam = qr_models(M, V, T, rconds)
+        svals[b] = np.sqrt(np.sort(lam)[::-1])
+    out = _result(models, rank, svals, status, scalar)
+    out["sweeps"] = sweeps
+    return out
+
+
+def dmdc_fit_batch(xs, us, order, rcond, u_scale=None, method="gram"):
     """Fit B DMDc models on the device in one launch.
 
     xs [B, N + 1, n] or [B, E, N + 1, n] complex: E experiments of N steps per member; us [N, m] / [E, N, m] (shared by the
     ensemble), [B, N, m] (E = 1) or [B, E, N, m]; u_scale [B, m]: member b saw u_scale[b] * us; rcond a scalar or up to 16 values
     in [1e-7, 1).  Returns a dict: "models" [R, B, n, n (1 + P)] ([B, n, n (1 + P)] for a scalar rcond) in the layout every other
     entry point takes, "rank" [R, B] ([B]), "svals" [B, nz] (the singular values of the stacked data, descending) and "status" [B]
-    (0 ok, 1 the eigen-iteration hit its cap, 3 non-finite data: zero models, rank 0)."""
-    xs, us, u_per, u_scale, rconds, scalar, order = _check(xs, us, order, rcond, u_scale)
+    (0 ok, 1 the eigen-iteration hit its cap, 3 non-finite data: zero models, rank 0).
+    method "gram" (m4q_dmdc_fit_batch): from the Gram matrix of the data, error O(eps kappa^2), rcond in [1e-7, 1);
+    method "qr" (m4q_dmdc_fit_qr_batch): from a QR of the data themselves, error O(eps kappa), rcond in [1e-12, 1)."""
+    xs, us, u_per, u_scale, rconds, scalar, order = _check(xs, us, order, rcond, u_scale, _method(method))
     B, E, N1, n = xs.shape
     m = us.shape[3]
     nz = n * size_of_library(order, m)
@@ -240,10 +398,10 @@ def dmdc_fit_batch(xs, us, order, rcond, u_scale=None):
     status = np.empty(B, dtype=np.int32)
     dp, ip = _lib._dp, _lib._ip
     L = _lib.lib()
-    _lib.check(L.m4q_dmdc_fit_batch(B, n, m, order, E, N1 - 1, xs.ctypes.data_as(dp), us.ctypes.data_as(dp), u_per,
-                                    None if u_scale is None else u_scale.ctypes.data_as(dp), rconds.ctypes.data_as(dp), R,
-                                    models.ctypes.data_as(dp), rank.ctypes.data_as(ip), svals.ctypes.data_as(dp),
-                                    status.ctypes.data_as(ip)))
+    entry = L.m4q_dmdc_fit_qr_batch if method == "qr" else L.m4q_dmdc_fit_batch
+    _lib.check(entry(B, n, m, order, E, N1 - 1, xs.ctypes.data_as(dp), us.ctypes.data_as(dp), u_per,
+                     None if u_scale is None else u_scale.ctypes.data_as(dp), rconds.ctypes.data_as(dp), R,
+                     models.ctypes.data_as(dp), rank.ctypes.data_as(ip), svals.ctypes.data_as(dp), status.ctypes.data_as(ip)))
     return _result(models, rank, svals, status, scalar)
 
 
@@ -263,13 +421,13 @@ def prediction_losses(xs, models, us, order, u_scale=None):
     return losses
 
 
-def train_models_batch(xs, us, order, rconds=np.logspace(-6, -1, 10), u_scale=None):
+def train_models_batch(xs, us, order, rconds=np.logspace(-6, -1, 10), u_scale=None, method="gram"):
     """The reference's hyper-parameter search (its tests/util_training.train_model) for an ensemble: one fit call covers all
     rconds, every candidate is rolled along the training controls, and each member keeps the model that loses least (the first
     of equals, as the reference's `loss < smallest_loss`).  Returns a dict: "models" [B, n, nz], "rcond" [B], "index" [B] (into
-    rconds), "losses" [R, B], "status" [B]."""
-    xs4, us4, _, u_scale, rconds, _, order = _check(xs, us, order, np.atleast_1d(rconds), u_scale)
-    fit = dmdc_fit_batch(xs4, us4, order, rconds, u_scale)
+    rconds), "losses" [R, B], "status" [B].  method: dmdc_fit_batch's."""
+    xs4, us4, _, u_scale, rconds, _, order = _check(xs, us, order, np.atleast_1d(rconds), u_scale, _method(method))
+    fit = dmdc_fit_batch(xs4, us4, order, rconds, u_scale, method)
     losses = prediction_losses(xs4, fit["models"], us4, order, u_scale)
     finite = np.where(np.isfinite(losses), losses, np.inf)
     index = np.argmin(finite, axis=0)

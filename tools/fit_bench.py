@@ -1,18 +1,20 @@
 #!/usr/bin/env python3
 """The batched DMDc fit on the device against the host loop it replaces.
 
-    python tools/fit_bench.py [--members 65536] [--host-members 1024] [--repeats 3] [--once]
+    python tools/fit_bench.py [--method gram|qr] [--members 65536] [--host-members 1024] [--repeats 3] [--once]
 
 Config 3's plant (the three-level transmon under two drives), `members` of them with per-member detuning (op0 scaled) and drive
 calibration (u_scale), E = 3 training experiments of N = 40 held-control steps from random full-rank states, one smooth pulse set
 shared by the ensemble; the trajectories come from plant_rollout_batch (one launch per experiment).  Fitted for the ten rconds of
-the reference's training grid np.logspace(-6, -1, 10) in ONE m4q_dmdc_fit_batch call.
+the reference's training grid np.logspace(-6, -1, 10) in ONE m4q_dmdc_fit_batch call, or - with --method qr - in one
+m4q_dmdc_fit_qr_batch call on the same inputs (the time to hold it against is --method gram's; accuracy is the point of the QR
+route, so no threshold is set there either).
 Printed: the wall time of that call (host buffers in and out, as the one-shot entry points copy them: 2.5 GB of models come back
 at 65,536 members) per repeat, the host loop `DiscrepDMDc.from_data` over the same rconds timed on the first `host-members`
 members and scaled to the ensemble, and the largest difference between the two on those members at the cut-offs where their ranks
 agree.  No threshold is set: nothing upstream fits an ensemble.
 --once runs the device fit exactly once and times nothing: the run to put under `rocprofv3 --kernel-trace --stats`, a run of its
-own, whose kernel statistics give dmdc_fit_kernel's time without the copies."""
+own, whose kernel statistics give dmdc_fit_kernel's (dmdc_fit_qr_kernel's) time without the copies."""
 import argparse
 import os
 import sys
@@ -58,6 +60,7 @@ def host_fit(xs, us, u_scale):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--method", choices=fit.METHODS, default="gram")
     ap.add_argument("--members", type=int, default=65536)
     ap.add_argument("--host-members", type=int, default=1024)
     ap.add_argument("--repeats", type=int, default=3)
@@ -65,16 +68,16 @@ def main():
     a = ap.parse_args()
     B, Bh = a.members, min(a.host_members, a.members)
     xs, us, u_scale = training_data(B)
-    out = m4q.dmdc_fit_batch(xs, us, 1, RCONDS, u_scale=u_scale)             # warm-up (and, with --once, the only run)
-    print("fit_bench B=%d n=9 m=2 E=%d N=%d R=%d: status counts %s, ranks per rcond (member 0) %s" %
-          (B, E, N, len(RCONDS), np.bincount(out["status"], minlength=4).tolist(), out["rank"][:, 0].tolist()), flush=True)
+    out = m4q.dmdc_fit_batch(xs, us, 1, RCONDS, u_scale=u_scale, method=a.method)   # warm-up (and, with --once, the only run)
+    print("fit_bench method=%s B=%d n=9 m=2 E=%d N=%d R=%d: status counts %s, ranks per rcond (member 0) %s" %
+          (a.method, B, E, N, len(RCONDS), np.bincount(out["status"], minlength=4).tolist(), out["rank"][:, 0].tolist()), flush=True)
     print("fit_bench PCIe bytes: %.4g MB in, %.4g MB out" %
           ((xs.nbytes + us.nbytes + u_scale.nbytes) / 1e6, (out["models"].nbytes + out["rank"].nbytes + out["svals"].nbytes) / 1e6), flush=True)
     if a.once:
         return
     for r in range(a.repeats):
         t0 = time.perf_counter()
-        m4q.dmdc_fit_batch(xs, us, 1, RCONDS, u_scale=u_scale)
+        m4q.dmdc_fit_batch(xs, us, 1, RCONDS, u_scale=u_scale, method=a.method)
         dt = time.perf_counter() - t0
         print("fit_bench repeat %d device call wall %9.2f ms  %.3e fits/s (%d members x %d rconds)" %
               (r, 1e3 * dt, B * len(RCONDS) / dt, B, len(RCONDS)), flush=True)
