@@ -817,9 +817,12 @@ __device__ __forceinline__ void riccati_backward(const Prov& prov, int T, const 
 #pragma unroll
     for (int i = 0; i < NX; ++i) Qcol[i] = Q0[i * NX + j];
   }
-  auto step = [&](int t, const Ops& cur, Ops& nxt, const S (&Pc)[NX], const S pv, S (&Pn)[NX], S& pv_out) __attribute__((always_inline)) {
+  // LAST (a std::bool_constant): the index is t = 0 - nothing to fetch ahead, and the sweep ends with its gain stores: the
+  // cost-to-go of index 0 is read by nothing (P and p are locals of this function, which returns no value)
+  auto step = [&](auto last, int t, const Ops& cur, Ops& nxt, const S (&Pc)[NX], const S pv, S (&Pn)[NX], S& pv_out) __attribute__((always_inline)) {
+    constexpr bool LAST = decltype(last)::value;
     M4Q_NO_HOIST();
-    nxt = load(t > 0 ? t - 1 : 0);
+    if constexpr (!LAST) nxt = load(t > 0 ? t - 1 : 0);
     const typename Prov::Lin& lin = cur.lin;
     const S xb = cur.xb;
     const double (&ub)[NU] = cur.ub;
@@ -961,6 +964,7 @@ __device__ __forceinline__ void riccati_backward(const Prov& prov, int T, const 
       stn<NU>(gains, gt + j * NU, Kst);
       stn<NU>(gains, gt + NX * NU, kst);   // (replicated over the row: every lane may write the same bytes)
     }
+    if constexpr (LAST) return;
 
     // closed loop: Sx = A_t + B Kx (column j, in place): Ac[i] += lane_i(B[i][k]) Kx[k];  s = c + B k
 #pragma unroll
@@ -998,6 +1002,10 @@ __device__ __forceinline__ void riccati_backward(const Prov& prov, int T, const 
     pv_out = pn;
     xb_next = xb;
   };
+  // PEEL: index 0 out of the loop, ending at its gains.  Not in the pinned sweep (peeled, the exact kernel measured slower - see
+  // TileBackwardB::backward, m4q_tile3.h) and not at n >= 15: the d = 4 kernels live on their register budget, and config 4 on
+  // shared generators measured 61.7 -> 64.9 ms with the second copy of the step (profiles/r06_ab_experiments.txt ## 4)
+  constexpr bool PEEL = !PINNED && NX < 15;
   S Pd[NX];
   S pd = zero_of<S>();
   Ops opsA = load(T - 1), opsB;
@@ -1006,20 +1014,29 @@ __device__ __forceinline__ void riccati_backward(const Prov& prov, int T, const 
   // of the neighbouring commits pass a static audit and the GPU suite; the form is gone from the source).
   if constexpr (sizeof(S) == sizeof(double)) {
     int t = T - 1;
-    for (; t >= 1; t -= 2) {
-      step(t, opsA, opsB, Pc, pv, Pd, pd);
-      step(t - 1, opsB, opsA, Pd, pd, Pc, pv);
+    for (; t >= (PEEL ? 2 : 1); t -= 2) {
+      step(std::false_type{}, t, opsA, opsB, Pc, pv, Pd, pd);
+      step(std::false_type{}, t - 1, opsB, opsA, Pd, pd, Pc, pv);
     }
-    if (t == 0) step(0, opsA, opsB, Pc, pv, Pd, pd);
+    // index 0, peeled (after index 1 where T is even; T >= 1: every entry point refuses a shorter horizon)
+    if constexpr (!PEEL) {
+      if (t == 0) step(std::false_type{}, 0, opsA, opsB, Pc, pv, Pd, pd);
+    } else if (t == 1) {
+      step(std::false_type{}, 1, opsA, opsB, Pc, pv, Pd, pd);
+      step(std::true_type{}, 0, opsB, opsA, Pd, pd, Pc, pv);
+    } else {
+      step(std::true_type{}, 0, opsA, opsB, Pc, pv, Pd, pd);
+    }
   } else {
     // complex path: one index per trip and plain copies (twice the registers per matrix: the two-index form does not pay)
-    for (int t = T - 1; t >= 0; --t) {
-      step(t, opsA, opsB, Pc, pv, Pd, pd);
+    for (int t = T - 1; t >= (PEEL ? 1 : 0); --t) {
+      step(std::false_type{}, t, opsA, opsB, Pc, pv, Pd, pd);
 #pragma unroll
       for (int i = 0; i < NX; ++i) Pc[i] = Pd[i];
       pv = pd;
       opsA = opsB;
     }
+    if constexpr (PEEL) step(std::true_type{}, 0, opsA, opsB, Pc, pv, Pd, pd);        // index 0, peeled
   }
 }
 

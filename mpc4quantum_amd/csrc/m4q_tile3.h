@@ -29,6 +29,13 @@ __device__ __forceinline__ double quad_bcast(double x) {
   return __hiloint2double(hi, lo);
 }
 
+// the value of lane addr / 4 (two ds_bpermute_b32)
+__device__ __forceinline__ double lane_gather(double x, int addr) {
+  const int lo = __builtin_amdgcn_ds_bpermute(addr, __double2loint(x));
+  const int hi = __builtin_amdgcn_ds_bpermute(addr, __double2hiint(x));
+  return __hiloint2double(hi, lo);
+}
+
 // a wave-uniform double into scalar registers
 __device__ __forceinline__ double to_sgpr(double x) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
@@ -112,6 +119,11 @@ struct TileBackwardB {
       mdl = (const double*)ml;
       Q = (const double*)ql;
     }
+    // The clipped sweep ends at the gains of index 0 (PEEL: the block that holds t = 0 is peeled out of the block loop, LAST below)
+    // and reads the gain's second layout across lanes (KPERM, at Kr below).  The pinned sweep keeps the plain loop and the MFMA form:
+    // with both, bit-identical as well, the exact mode measured 2 % SLOWER in three alternations (config 3: 182.7 184.5 181.7 ->
+    // 187.1 186.4 186.4 ms; the exact kernel grows from 14.4 k to 17.1 k instructions: profiles/r06_ab_experiments.txt)
+    constexpr bool PEEL = !PINNED, KPERM = !PINNED;
     constexpr bool QLDS = NS % 4 == 0;           // Q's tiles re-read from LDS at every index (no masking at n = 4k)
     double M[1 + NP][NT][NT], NpT[NP][NT][NT], P[NT][NT], pv[NT], xb[NT], tt[1 + NP][NT], Qt[QLDS ? 1 : NT][QLDS ? 1 : NT];
     const double* Qlane = Q + L.r * NS + L.q;
@@ -155,10 +167,14 @@ struct TileBackwardB {
 #pragma unroll
       for (int l = 0; l < NU; ++l) Rm[s][l] = to_sgpr(R[s * NU + l]);
     const double satu = to_sgpr(sat);
+    const int kr_src = 4 * (((int)threadIdx.x & ~3) | ((int)threadIdx.x >> 4));     // byte address of lane (r, member, q' = r)
 
-    // one horizon index; ug / ub: its controls and control targets, b: rowrep(N_s x_g), all replicated over the member's lanes
-    auto step = [&](int t, const double (&ug)[NU], const double (&ub)[NU], const double (&b)[NU][NT],
+    // one horizon index; ug / ub: its controls and control targets, b: rowrep(N_s x_g), all replicated over the member's lanes.
+    // LAST (a std::bool_constant): the index is t = 0 - the sweep ends with its gain stores: the cost-to-go of index 0 (S, P S, w,
+    // R K, Kr, the new P and p: 28 of the index's 44 MFMAs in the MFMA form) is read by nothing, backward() returns no value
+    auto step = [&](auto last, int t, const double (&ug)[NU], const double (&ub)[NU], const double (&b)[NU][NT],
                     const double (&stv)[NU], const double (&cin)[NT]) __attribute__((always_inline)) {
+      constexpr bool LAST = decltype(last)::value;
       double At[NT][NT], c[NT], W[NT], Y[NT], H[NT];
 #pragma unroll
       for (int I = 0; I < NT; ++I)
@@ -287,7 +303,11 @@ struct TileBackwardB {
         for (int J = 0; J < NT; ++J) {
           Ks[s][J] = mm(cst[s], H[J], 0.0);                                     // the stored row: [4J + q] in every r
           Kc[s][J] = PINNED ? (fix[s] ? 0.0 : Ks[s][J]) : Ks[s][J];             // K_s[4J + q] in every r (a pinned control: 0)
-          Kr[s][J] = mm(H[J], cf[s], 0.0);                                      // K_s[4J + r] in every q
+          // K_s[4J + r] in every q.  KPERM: what lane q' = r of the own quad holds of Kc - the same sums over k of the same products
+          // as mm(H[J], cf[s], 0), which it replaces (4 of the index's 44 MFMAs); issued here, first read by the p / P update at the
+          // end of the index
+          if constexpr (!KPERM) Kr[s][J] = mm(H[J], cf[s], 0.0);
+          else if constexpr (!LAST) Kr[s][J] = lane_gather(Kc[s][J], kr_src);
         }
       if (store_ok) {
         // gains [t][col][s]: the m entries of a column are one tuple; Kc is replicated over r, kk over the member's 16 lanes: every
@@ -302,6 +322,7 @@ struct TileBackwardB {
         }
         stn<NU>(gains, gt + NS * NU, kst);
       }
+      if constexpr (LAST) return;
       double S[NT][NT], sv[NT], PS[NT][NT], w[NT];
 #pragma unroll
       for (int I = 0; I < NT; ++I) {
@@ -367,8 +388,10 @@ struct TileBackwardB {
         }
       }
     };
-    // the four indices of a block: index tb - j takes column j of the block's tiles
-    auto block = [&](int tb, int cnt, const Blk& cur) __attribute__((always_inline)) {
+    // the four indices of a block: index tb - j takes column j of the block's tiles.  FIN (a std::bool_constant): the block that
+    // ends the sweep - its last live index, j == cnt - 1, is t = 0
+    auto block = [&](auto fin, int tb, int cnt, const Blk& cur) __attribute__((always_inline)) {
+      constexpr bool FIN = decltype(fin)::value;
       double BT[NU][NT];
 #pragma unroll
       for (int s = 0; s < NU; ++s)
@@ -406,7 +429,10 @@ struct TileBackwardB {
           }
 #pragma unroll
           for (int K = 0; K < NT; ++K) cin[K] = quad_bcast<j>(CT[K]);
-          step(tb - j, ug, ub, b, stv, cin);
+          if constexpr (!FIN) step(std::false_type{}, tb - j, ug, ub, b, stv, cin);
+          else if constexpr (j == 3) step(std::true_type{}, tb - j, ug, ub, b, stv, cin);          // (j < cnt: cnt == 4)
+          else if (j == cnt - 1) step(std::true_type{}, tb - j, ug, ub, b, stv, cin);               // (wave-uniform)
+          else step(std::false_type{}, tb - j, ug, ub, b, stv, cin);
         }
       });
     };
@@ -417,13 +443,19 @@ struct TileBackwardB {
     // (one block ahead, the next set copied into place: two sets swapping roles over two blocks per trip measured 32.35 against
     //  32.25 ms - more spills -, two blocks ahead 32.93: profiles/r04_ab_experiments.txt)
     Blk cur = load_blk(tb);
-    while (tb >= 0) {
+    while (PEEL ? tb >= cnt : tb >= 0) {
       M4Q_NO_HOIST();
       const Blk nxt = load_blk(tb - cnt);
-      block(tb, cnt, cur);
+      block(std::false_type{}, tb, cnt, cur);
       tb -= cnt;
       cnt = 4;
       cur = nxt;
+    }
+    // the block that holds t = 0 (tb == cnt - 1: a full one after the loop, the only one at T <= 4; T >= 1), peeled: nothing to
+    // fetch ahead, and its last index stops at its gains
+    if constexpr (PEEL) {
+      M4Q_NO_HOIST();
+      block(std::true_type{}, tb, cnt, cur);
     }
   }
 };
