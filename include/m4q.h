@@ -235,6 +235,46 @@ M4Q_API int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u
                                  int32_t q_mode, const double* weights, int32_t reduce, double* q, double* grad, double* grad_scale,
                                  double* q_mean);
 
+/* A stored feedback law run on B members over N steps in ONE launch: the tier between the open-loop rollouts above and the closed
+ * loop that re-solves a QP at every step - time-varying gains around a nominal trajectory with saturation, a slew band and
+ * measurement noise.  mpc4quantum_amd/feedback.py (FeedbackLaw, plant_feedback_reference, model_feedback_reference) is the
+ * definition, in NumPy and SciPy.
+ * The law: gains [B|1][N][n+1][m] c, the layout m4q_quad_program_batch returns (gains[t][col][k], col = n the affine column),
+ * x_ref [B|1][N][n] c, u_ref [B|1][N][m] r - all three per member or all three shared (law_per_instance).  Step t of member b in
+ * state x_t:
+ *   s_k = sum_j Re(K_t[j][k] (x_t - x_ref[t])_j) + Re(K_t[n][k]) + u_ref[t][k];   lo = -sat, hi = sat (sat > 0, INFINITY: no box);
+ *   du_band != 0: lo = fmax(lo, p_k - du), hi = fmin(hi, p_k + du) with p = u_prev[b] ([B|1][m] r) at t = 0, then u_{t-1};
+ *   u_t[k] = fmin(fmax(s_k, lo), hi) (lo > hi: hi wins);   x_{t+1} = step(x_t, u_scale[b] u_t);
+ *   noise_mode != 0: x_{t+1} += the draw of (seed, member_base + b, t + 1, component) scaled by sigma [B|1] r, as
+ *   m4q_noise_sample_batch returns it - the noisy state is stored, read by the next control and stepped from; x0 is never measured.
+ * x0, u_scale, W, target, xs_mode, xs, q_mode, q as the rollouts (column 0 of xs = x0 as given).  Further outputs:
+ * us [B][N][m] r or NULL: the commanded u_t, before u_scale; clipped [B] i32 or NULL: the number of (t, k) with s_k <= lo or
+ * s_k >= hi; status [B] i32, required: 0, or 3 when a state or a control of the member was not finite.
+ * M4Q_E_BADARG: B or N < 1, a missing x0, gains, x_ref, u_ref or status, sat <= 0 or NaN, du_band with du <= 0 or not finite or
+ * without u_prev, a mode outside 0-2, xs_mode and q_mode 0 with neither us nor clipped, a mode without its array, q_mode != 0
+ * without W or target, a noise mode outside 0-2 or without sigma (or a sigma that is negative or not finite), M4Q_NOISE_HERMITIAN
+ * on M4Q_PLANT_PROCESS or with n not a square, (plant) missing dts, op0 or ops, a plant_kind that is no device plant,
+ * M4Q_PLANT_PROCESS with n not a fourth power.  M4Q_E_UNSUPPORTED: the cases of the rollouts.  Arguments are checked before the
+ * device is asked for.
+ *
+ * m4q_plant_feedback_batch: the step of m4q_plant_rollout_batch (dts, op0, ops, plant_kind as there; all three device plants). */
+M4Q_API int m4q_plant_feedback_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                             const double* x0, const double* gains, const double* x_ref, const double* u_ref,
+                             int32_t law_per_instance, double sat, int32_t du_band, double du, const double* u_prev,
+                             int32_t u_prev_per_instance, const double* u_scale, const double* op0, const double* ops,
+                             int32_t plant_per_instance, int32_t noise_mode, const double* sigma, int32_t sigma_per_instance,
+                             uint64_t seed, uint64_t member_base, const double* W, const double* target,
+                             int32_t target_per_instance, int32_t xs_mode, double* xs, int32_t q_mode, double* q, double* us,
+                             int32_t* clipped, int32_t* status);
+/* m4q_model_feedback_batch: the step of m4q_model_rollout_batch; models [B|1][n][n(1+P)] c. */
+M4Q_API int m4q_model_feedback_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0,
+                             const double* gains, const double* x_ref, const double* u_ref, int32_t law_per_instance, double sat,
+                             int32_t du_band, double du, const double* u_prev, int32_t u_prev_per_instance, const double* u_scale,
+                             const double* models, int32_t model_per_instance, int32_t noise_mode, const double* sigma,
+                             int32_t sigma_per_instance, uint64_t seed, uint64_t member_base, const double* W, const double* target,
+                             int32_t target_per_instance, int32_t xs_mode, double* xs, int32_t q_mode, double* q, double* us,
+                             int32_t* clipped, int32_t* status);
+
 /* DMDc identification for an ensemble in ONE launch: DiscrepDMDc.from_data(X2, X1, krtimes(lift(U1), X1), rcond) = X2 pinv(Z, rcond)
  * (model.py: DiscrepDMDc.from_data, the fit of the reference's training workflow) for B members and R cut-offs, the models in the layout every other
  * entry point takes.  mpc4quantum_amd/fit.py (dmdc_fit_reference) is the definition, in NumPy, in the kernel's order of operations.

@@ -5,6 +5,8 @@ linearize, model, mpc, vectorize), backed by hand-written HIP kernels in libm4q_
 from .exit_condition import QuadraticExit  # noqa: F401
 from .experiment import (Experiment, LExperiment, QCoupledExperiment, QExperiment, QExperiment32, QSynthesis,  # noqa: F401
                          isqrt, plant_step_batch, process_dim, split_blocks)
+from .feedback import (FeedbackLaw, model_feedback_batch, model_feedback_reference, plant_feedback_batch,  # noqa: F401
+                       plant_feedback_reference)
 from .fit import dmdc_fit_batch, dmdc_fit_qr_reference, dmdc_fit_reference, train_models_batch  # noqa: F401
 from .grad import (model_rollout_grad_batch, model_rollout_grad_reference, ordered_weighted_sum,  # noqa: F401
                    plant_rollout_grad_batch, plant_rollout_grad_reference)

@@ -74,6 +74,12 @@ PROTOTYPES = {
                                                _i32, _dp, _i32, _dp, _dp, _dp, _dp]),
     "m4q_model_rollout_grad_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _i32, _dp,
                                                _i32, _dp, _dp, _dp, _dp]),
+    "m4q_plant_feedback_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _dp, _dp, _dp, _i32, C.c_double, _i32, C.c_double, _dp,
+                                           _i32, _dp, _dp, _dp, _i32, _i32, _dp, _i32, C.c_uint64, C.c_uint64, _dp, _dp, _i32, _i32, _dp,
+                                           _i32, _dp, _dp, _ip, _ip]),
+    "m4q_model_feedback_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _dp, _dp, _i32, C.c_double, _i32, C.c_double, _dp, _i32,
+                                           _dp, _dp, _i32, _i32, _dp, _i32, C.c_uint64, C.c_uint64, _dp, _dp, _i32, _i32, _dp, _i32, _dp,
+                                           _dp, _ip, _ip]),
     "m4q_dmdc_fit_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _ip]),
     "m4q_dmdc_fit_qr_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _ip]),
     "m4q_online_dmdc_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _i32, _dp, _i32, C.c_double,

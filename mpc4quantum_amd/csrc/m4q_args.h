@@ -156,6 +156,25 @@ struct GradReduceArgs {
   M4Q_P(double) out_last; long last_stride;        // element nm of chunk c -> out_last[c last_stride]
 };
 
+// A stored feedback law closing the loop of a rollout (m4q_plant_feedback_batch, m4q_model_feedback_batch; m4q_feedback.h,
+// feedback.py is the definition).  `roll` is the rollout without its control sequence (roll.u is u_ref, roll.u_stride its
+// stride): at step t the member commands u_t = clip(Re(K_t [x_t - x_ref[t] ; 1]) + u_ref[t]) and sees u_scale[b][k] u_t[k].
+// The law is per member or shared as a whole: law_per 1 or 0 multiplies the strides N (n + 1) m, N n and N m.
+// du_band: the band p +- du around the control applied before (u_prev [B|1][m] at t = 0; u_prev_stride m or 0) joins the box.
+// noise_mode etc.: as MpcArgs', the draw of (seed, member_base + b, t + 1, component) is added to x_{t+1}.
+struct FeedbackArgs {
+  RollArgs roll;
+  M4Q_P(const cplx) gains; M4Q_P(const cplx) x_ref; M4Q_P(const double) u_ref; int law_per;
+  double sat, du; int du_band;
+  M4Q_P(const double) u_prev; long u_prev_stride;
+  int noise_mode;
+  unsigned long long seed, member_base;
+  M4Q_P(const double) sigma; long sigma_stride;    // [B|1]
+  M4Q_P(double) us;                                // [B][N][m] or null
+  M4Q_P(int) clipped;                              // [B] or null
+  M4Q_P(int) status;                               // [B]: 0 ok, 3 a state or control was not finite
+};
+
 // m4q_dmdc_fit_batch: the truncated least-squares DMDc fit of B members from E experiments of N steps each (m4q_fit.h; fit.py is
 // the definition).  The member sees u_scale[b][k] u[e][t][k], as in the rollouts.  rconds live in device memory: the kernel indexes
 // them at run time.
@@ -254,6 +273,8 @@ struct ShapeOps {
   int (*launch_observe)(const ObserveArgs&, hipStream_t);          // (shapes with an observe_kind; depends on dim_x alone)
   int (*launch_observed_plant)(const ObsPlantArgs&, hipStream_t);  // (... and on dim_u: the plant has the shape's controls)
   int (*launch_fit_qr)(const FitArgs&, hipStream_t);               // dmdc_fit_qr_kernel: the shapes and the LDS of launch_fit
+  int (*launch_plant_feedback)(const FeedbackArgs&, hipStream_t);  // (the shapes of launch_plant_rollout)
+  int (*launch_model_feedback)(const FeedbackArgs&, hipStream_t);  // (the shapes of launch_model_rollout)
 };
 
 }  // namespace m4q

@@ -1255,6 +1255,119 @@ int m4q_model_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t ord
 }
 
 namespace {
+// the arguments the two feedback runs share, checked before a device is asked for
+int check_feedback_args(const char* who, int32_t B, int32_t dim_x, int32_t N, const double* x0, const double* gains, const double* x_ref,
+                        const double* u_ref, double sat, int32_t du_band, double du, const double* u_prev, int32_t noise_mode,
+                        const double* sigma, size_t sigma_count, bool hermitian_ok, const double* W, const double* target, int32_t xs_mode,
+                        double* xs, int32_t q_mode, double* q, double* us, int32_t* clipped, int32_t* status) {
+  if (B < 1 || N < 1) return fail(M4Q_E_BADARG, "%s: B and N must be at least 1 (got %d, %d)", who, B, N);
+  if (!x0 || !gains || !x_ref || !u_ref || !status) return fail(M4Q_E_BADARG, "%s: x0, gains, x_ref, u_ref and status are required", who);
+  if (!(sat > 0.0)) return fail(M4Q_E_BADARG, "%s: sat = %g is not positive (INFINITY: no box)", who, sat);
+  if (du_band && !(du > 0.0 && std::isfinite(du))) return fail(M4Q_E_BADARG, "%s: du = %g is not positive and finite", who, du);
+  if (du_band && !u_prev) return fail(M4Q_E_BADARG, "%s: the band needs u_prev, the control applied before step 0", who);
+  if (xs_mode < 0 || xs_mode > 2 || q_mode < 0 || q_mode > 2)
+    return fail(M4Q_E_BADARG, "%s: xs_mode and q_mode are 0 (none), 1 (last) or 2 (all), got %d and %d", who, xs_mode, q_mode);
+  if (xs_mode == 0 && q_mode == 0 && !us && !clipped)
+    return fail(M4Q_E_BADARG, "%s: nothing to return (xs_mode and q_mode are 0, us and clipped NULL)", who);
+  if (xs_mode != 0 && !xs) return fail(M4Q_E_BADARG, "%s: xs_mode %d without xs", who, xs_mode);
+  if (q_mode != 0 && (!q || !W || !target)) return fail(M4Q_E_BADARG, "%s: q_mode %d needs W, target and q", who, q_mode);
+  if (int rc = check_noise_args(who, noise_mode, sigma, sigma_count)) return rc;
+  if (noise_mode == M4Q_NOISE_HERMITIAN && !hermitian_ok)
+    return fail(M4Q_E_BADARG, "%s: M4Q_NOISE_HERMITIAN needs a density-matrix state, n = d d and no process plant (dim_x = %d: use "
+                "M4Q_NOISE_IID)", who, dim_x);
+  return 0;
+}
+
+// stages what the two feedback runs share: the rollout with u_ref in its controls' place, the law, the noise, the further outputs
+m4q::FeedbackArgs stage_feedback(Stage& st, int32_t B, size_t n, size_t m, int32_t N, const double* x0, const double* gains,
+                                 const double* x_ref, const double* u_ref, int32_t law_per_instance, double sat, int32_t du_band, double du,
+                                 const double* u_prev, int32_t u_prev_per_instance, const double* u_scale, int32_t noise_mode,
+                                 const double* sigma, int32_t sigma_per_instance, uint64_t seed, uint64_t member_base, const double* W,
+                                 const double* target, int32_t target_per_instance, int32_t xs_mode, double* xs, int32_t q_mode, double* q,
+                                 double* us, int32_t* clipped, int32_t* status) {
+  m4q::FeedbackArgs f{};
+  f.roll = stage_roll(st, B, n, m, N, x0, u_ref, law_per_instance, u_scale, W, target, target_per_instance, xs_mode, xs, q_mode, q);
+  const Extent eg(B, law_per_instance, (size_t)N * (n + 1) * m), ex(B, law_per_instance, (size_t)N * n);
+  f.u_ref = f.roll.u;
+  f.gains = st.in<cplx>(gains, eg.count);
+  f.x_ref = st.in<cplx>(x_ref, ex.count);
+  f.law_per = law_per_instance ? 1 : 0;
+  f.sat = sat; f.du_band = du_band ? 1 : 0; f.du = du_band ? du : 0.0;
+  if (du_band) {
+    const Extent ep(B, u_prev_per_instance, m);
+    f.u_prev = st.in<double>(u_prev, ep.count); f.u_prev_stride = ep.stride;
+  }
+  f.noise_mode = noise_mode; f.seed = seed; f.member_base = member_base;
+  if (noise_mode != 0) {
+    const Extent sg(B, sigma_per_instance, 1);
+    f.sigma = st.in<double>(sigma, sg.count); f.sigma_stride = sg.stride;
+  }
+  if (us) f.us = st.out<double>(us, (size_t)B * N * m);
+  if (clipped) f.clipped = st.out<int>(clipped, (size_t)B);
+  f.status = st.out<int>(status, (size_t)B);
+  return f;
+}
+}  // namespace
+
+int m4q_plant_feedback_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts, const double* x0,
+                             const double* gains, const double* x_ref, const double* u_ref, int32_t law_per_instance, double sat,
+                             int32_t du_band, double du, const double* u_prev, int32_t u_prev_per_instance, const double* u_scale,
+                             const double* op0, const double* ops, int32_t plant_per_instance, int32_t noise_mode, const double* sigma,
+                             int32_t sigma_per_instance, uint64_t seed, uint64_t member_base, const double* W, const double* target,
+                             int32_t target_per_instance, int32_t xs_mode, double* xs, int32_t q_mode, double* q, double* us,
+                             int32_t* clipped, int32_t* status) {
+  const char* who = "m4q_plant_feedback_batch";
+  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d", dim_x, dim_u);
+  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  const size_t sigma_count = B < 1 ? 0 : Extent(B, sigma_per_instance, 1).count;
+  if (int rc = check_feedback_args(who, B, dim_x, N, x0, gains, x_ref, u_ref, sat, du_band, du, u_prev, noise_mode, sigma, sigma_count,
+                                   plant_kind != M4Q_PLANT_PROCESS, W, target, xs_mode, xs, q_mode, q, us, clipped, status))
+    return rc;
+  if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, op0 and ops are required", who);
+  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_feedback_batch: plant_kind %d is not a device plant")) return rc;
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x);
+  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  Stage st;
+  m4q::FeedbackArgs a = stage_feedback(st, B, n, m, N, x0, gains, x_ref, u_ref, law_per_instance, sat, du_band, du, u_prev,
+                                       u_prev_per_instance, u_scale, noise_mode, sigma, sigma_per_instance, seed, member_base, W, target,
+                                       target_per_instance, xs_mode, xs, q_mode, q, us, clipped, status);
+  a.roll.kind = plant_kind;
+  a.roll.dts = st.in<double>(dts, N);
+  a.roll.op0 = st.in<cplx>(op0, e0.count); a.roll.op0_stride = e0.stride;
+  a.roll.ops = st.in<cplx>(ops, ek.count); a.roll.ops_stride = ek.stride;
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_plant_feedback(a, nullptr), "plant feedback");
+}
+
+int m4q_model_feedback_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* gains,
+                             const double* x_ref, const double* u_ref, int32_t law_per_instance, double sat, int32_t du_band, double du,
+                             const double* u_prev, int32_t u_prev_per_instance, const double* u_scale, const double* models,
+                             int32_t model_per_instance, int32_t noise_mode, const double* sigma, int32_t sigma_per_instance, uint64_t seed,
+                             uint64_t member_base, const double* W, const double* target, int32_t target_per_instance, int32_t xs_mode,
+                             double* xs, int32_t q_mode, double* q, double* us, int32_t* clipped, int32_t* status) {
+  const char* who = "m4q_model_feedback_batch";
+  const m4q::ShapeOps* sh = find_shape(dim_x, dim_u, order);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no model kernel for dim_x=%d dim_u=%d order=%d", dim_x, dim_u, order);
+  const size_t sigma_count = B < 1 ? 0 : Extent(B, sigma_per_instance, 1).count;
+  if (int rc = check_feedback_args(who, B, dim_x, N, x0, gains, x_ref, u_ref, sat, du_band, du, u_prev, noise_mode, sigma, sigma_count,
+                                   dim_d(dim_x) != 0, W, target, xs_mode, xs, q_mode, q, us, clipped, status))
+    return rc;
+  if (!models) return fail(M4Q_E_BADARG, "%s: models are required", who);
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, P = sh->np;
+  const Extent mdl(B, model_per_instance, n * n * (1 + P));
+  Stage st;
+  m4q::FeedbackArgs a = stage_feedback(st, B, n, m, N, x0, gains, x_ref, u_ref, law_per_instance, sat, du_band, du, u_prev,
+                                       u_prev_per_instance, u_scale, noise_mode, sigma, sigma_per_instance, seed, member_base, W, target,
+                                       target_per_instance, xs_mode, xs, q_mode, q, us, clipped, status);
+  a.roll.models = st.in<cplx>(models, mdl.count); a.roll.model_stride = mdl.stride;
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_model_feedback(a, nullptr), "model feedback");
+}
+
+namespace {
 // the arguments the two rollout gradients share, checked before a device is asked for
 int check_grad_args(const char* who, int32_t B, int32_t N, const double* x0, const double* u, int32_t u_per_instance, const double* W,
                     const double* target, int32_t q_mode, const double* weights, int32_t reduce, double* q, double* grad, double* q_mean) {

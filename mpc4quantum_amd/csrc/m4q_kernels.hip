@@ -6,6 +6,7 @@
 #define M4Q_KERNEL_TU 1
 #include "m4q_args.h"
 #include "m4q_mpc.h"
+#include "m4q_feedback.h"
 #include "m4q_fit.h"
 #include "m4q_fit_qr.h"
 #include "m4q_online.h"
@@ -1262,6 +1263,48 @@ struct RollCtl {
   }
 };
 
+// Feedback runs (FeedbackArgs; m4q_feedback.h): what a member leaves besides its trajectory - the commanded controls of every
+// step, and at its end the count of active bounds and the status (3: a state or a control was not finite).  A lane watches its own
+// entry of the state; the controls are the same in every lane of the row.
+struct FeedbackOut {
+  M4Q_GLOBAL double* us; M4Q_GLOBAL int* clipped; M4Q_GLOBAL int* status;
+  long b;
+  int N;
+  bool st0;
+  bool bad;
+  __device__ __forceinline__ FeedbackOut(const FeedbackArgs& a, long b_, bool st0_)
+      : us(a.us), clipped(a.clipped), status(a.status), b(b_), N(a.roll.N), st0(st0_), bad(false) {}
+  __device__ __forceinline__ void state(cplx x) { bad = bad || !finite_d(x.re) || !finite_d(x.im); }
+  __device__ __forceinline__ void controls(int t, const double (&u)[NU]) const {
+    if (us != nullptr && st0) {
+#pragma unroll
+      for (int k = 0; k < NU; ++k) gst(us, (b * N + t) * NU + k, u[k]);
+    }
+  }
+  __device__ __forceinline__ void finish(const FeedbackRow<NX, NU>& law) const {
+    const bool lost = rowsum<NX>(bad ? 1.0 : 0.0) != 0.0 || law.bad;
+    if (st0) {
+      gst(status, b, lost ? 3 : 0);
+      if (clipped != nullptr) gst(clipped, b, law.clipped);
+    }
+  }
+};
+// ... and the measurement noise of column t + 1, added to the state the step left (m4q_noise.h; as mpc_kernel's step-done phase:
+// out of line, behind one scalar branch on the mode; lanes that shadow column NX - 1 draw that column's noise)
+struct FeedbackNoise {
+  int mode;
+  unsigned long long seed, member;
+  double sg;
+  __device__ __forceinline__ FeedbackNoise(const FeedbackArgs& a, long b)
+      : mode(a.noise_mode), seed(a.seed), member(a.member_base + (unsigned long long)b), sg(0.0) {
+    if (mode != 0) sg = gld(a.sigma, b * a.sigma_stride);
+  }
+  __device__ __forceinline__ cplx add(int t, cplx x, int j) const {
+    if (mode != 0) x = cadd(x, noise_sample(mode, seed, member, (unsigned)(t + 1), j, SQUARE ? DD : 0, sg));
+    return x;
+  }
+};
+
 // Rollout gradients (GradArgs; m4q_grad.h): the controls of step t as the member saw them in the forward pass - the same product
 template <class A>
 __device__ __forceinline__ void grad_controls(const RollCtl& ctl, int t, A& v) {
@@ -1376,6 +1419,50 @@ __global__ __launch_bounds__(64) M4Q_OCC void model_rollout_kernel(RollArgs a) {
       x = pred;
       out.put(t + 1, x);
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// model_rollout_kernel with a stored law closing the loop (m4q_model_feedback_batch; feedback.py: model_feedback_reference is the
+// definition): the controls of step t come from the state in registers (FeedbackRow), the step is that kernel's.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) M4Q_OCC void model_feedback_kernel(FeedbackArgs fa) {
+  const RollArgs& a = fa.roll;
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const LaneGeo L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* mdl = lds + g * MODEL_ELEMS;
+  const int nquads = quads_of(a.B);
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const QuadRow r(quad, g, a.B);
+    wave_sync();
+    stage_model<NX>(mdl, a.models + r.b * a.model_stride, jj);
+    wave_sync();
+    FusedProv<cplx, NX, NU, ORDER> prov;
+    prov.mdl = mdl;
+    prov.Xg = prov.Ug = gview(a.x0, 0, 0);         // (rows() reads neither)
+    prov.j = j;
+    const bool st0 = r.valid && jj == 0;
+    const RollOut out(a, r.b, j, r.valid && L.lane_ok, st0);
+    FeedbackRow<NX, NU> law(fa, r.b, j);
+    FeedbackOut fo(fa, r.b, st0);
+    const FeedbackNoise noise(fa, r.b);
+    cplx x = gld(a.x0, r.b * NX + j);
+    fo.state(x);
+    out.put(0, x);
+    for (int t = 0; t < a.N; ++t) {
+      FusedProv<cplx, NX, NU, ORDER>::Lin lin;
+      double u[NU];
+      law.take(t, x, u, lin.u);
+      fo.controls(t, u);
+      lin.xg = x;
+      cplx pred, Bdummy[NU], ddummy;
+      prov.rows(lin, x, pred, Bdummy, ddummy);      // A x + N (polyu (x) x) = A_t(u) x
+      x = noise.add(t, pred, j);
+      fo.state(x);
+      out.put(t + 1, x);
+    }
+    fo.finish(law);
   }
 }
 
@@ -1690,6 +1777,47 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_rollout_kernel(RollArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// plant_rollout_kernel with a stored law closing the loop (m4q_plant_feedback_batch; feedback.py: plant_feedback_reference is the
+// definition): the controls of step t come from the state in registers (FeedbackRow), the step is that kernel's, over dts[t].
+template <int PLANT>
+__global__ __launch_bounds__(64) M4Q_OCC void plant_feedback_kernel(FeedbackArgs fa) {
+  const RollArgs& a = fa.roll;
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const LaneGeo L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* scratch = lds + g * SCRATCH_ELEMS;
+  const int nquads = quads_of(a.B);
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const QuadRow r(quad, g, a.B);
+    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
+    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const bool st0 = r.valid && jj == 0;
+    const RollOut out(a, r.b, j, r.valid && L.lane_ok, st0);
+    FeedbackRow<NX, NU> law(fa, r.b, j);
+    FeedbackOut fo(fa, r.b, st0);
+    const FeedbackNoise noise(fa, r.b);
+    double dtn = gld(a.dts, 0);
+    cplx x = gld(a.x0, r.b * NX + j);
+    fo.state(x);
+    out.put(0, x);
+    for (int t = 0; t < a.N; ++t) {
+      double u[NU], v[NU];
+      law.take(t, x, u, v);
+      fo.controls(t, u);
+      const double dt = dtn;
+      dtn = gld(a.dts, t + 1 < a.N ? t + 1 : t);
+      GView o0 = op0, ok = ops;                      // (the generator's operators are read again at every step: plant_rollout_kernel)
+      if constexpr (PLANT == PLANT_GENERATOR) asm volatile("" : "+v"(o0.off), "+v"(ok.off));
+      M4Q_PLANT_STEP(PLANT, x, x, v, o0, ok, dt, scratch, j, jj);
+      x = noise.add(t, x, j);
+      fo.state(x);
+      out.put(t + 1, x);
+    }
+    fo.finish(law);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Control gradient of an open-loop plant rollout (m4q_plant_rollout_grad_batch; grad.py: plant_rollout_grad_reference is the
 // definition), Hamiltonian and process plants.  The forward pass is plant_rollout_kernel's, statement for statement, with every
 // state kept in the workspace a.xs [B][N + 1][n]; the backward pass reads x_t back and recomputes U and dU_k (m4q_grad.h).
@@ -1971,12 +2099,21 @@ static int launch_aux(K kern, const A& a, size_t lds, hipStream_t s) {
   return -(int)hipGetLastError();
 }
 [[maybe_unused]] constexpr int UNBUILT = -(int)hipErrorInvalidValue;      // what the launcher of a kernel this object does not hold returns
+// ... a feedback kernel, whose ensemble size is its rollout's
+template <class K>
+[[maybe_unused]] static int launch_feedback(K kern, const FeedbackArgs& a, size_t lds, hipStream_t s) {
+  int rc = prep_lds(kern, lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid_for(a.roll.B)), dim3(64), lds, s, a);
+  return -(int)hipGetLastError();
+}
 
 #ifndef M4Q_NO_AUX
 constexpr size_t MODEL_LDS = sizeof(cplx) * (size_t)(ROWS * MODEL_ELEMS);
 static int launch_linearize(const LinArgs& a, hipStream_t s) { return launch_aux(linearize_kernel, a, MODEL_LDS, s); }
 static int launch_qp(const QpArgs& a, hipStream_t s) { return launch_aux(qp_kernel, a, 0, s); }
 static int launch_model_rollout(const RollArgs& a, hipStream_t s) { return launch_aux(model_rollout_kernel, a, MODEL_LDS, s); }
+static int launch_model_feedback(const FeedbackArgs& a, hipStream_t s) { return launch_feedback(model_feedback_kernel, a, MODEL_LDS, s); }
 // (a partial specialisation, so that the kernel is instantiated only for the shapes whose layout fits)
 template <bool FITS, int N_ = NX>
 struct FitLaunch {
@@ -2054,6 +2191,7 @@ static int launch_online(const OnlineArgs&, int, hipStream_t) { return UNBUILT; 
 static int launch_linearize(const LinArgs&, hipStream_t) { return UNBUILT; }
 static int launch_qp(const QpArgs&, hipStream_t) { return UNBUILT; }
 static int launch_model_rollout(const RollArgs&, hipStream_t) { return UNBUILT; }
+static int launch_model_feedback(const FeedbackArgs&, hipStream_t) { return UNBUILT; }
 #endif
 
 #ifndef M4Q_VARIANT_GEN
@@ -2077,6 +2215,19 @@ static int launch_plant(const PlantArgs& a, hipStream_t s) {
 }
 static int launch_plant_rollout(const RollArgs& a, hipStream_t s) {
   return launch_by_plant(a, s, [](auto plant) { return plant_rollout_kernel<decltype(plant)::value>; });
+}
+static int launch_plant_feedback(const FeedbackArgs& a, hipStream_t s) {
+  if constexpr (!SQUARE) {
+    return UNBUILT;
+  } else {
+    constexpr size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
+    if (a.roll.kind == PLANT_HAMILTONIAN) return launch_feedback(plant_feedback_kernel<PLANT_HAMILTONIAN>, a, lds, s);
+    if (a.roll.kind == PLANT_PROCESS) {
+      if constexpr (QUARTIC) return launch_feedback(plant_feedback_kernel<PLANT_PROCESS>, a, lds, s);
+      else return UNBUILT;
+    }
+    return launch_feedback(plant_feedback_kernel<PLANT_GENERATOR>, a, lds, s);
+  }
 }
 
 static int launch_noise(const NoiseArgs& a, hipStream_t s) {
@@ -2138,6 +2289,7 @@ static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant(const PlantArgs&, hipStream_t) { return UNBUILT; }
 static int launch_noise(const NoiseArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant_rollout(const RollArgs&, hipStream_t) { return UNBUILT; }
+static int launch_plant_feedback(const FeedbackArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 #endif
@@ -2172,7 +2324,8 @@ static const ShapeOps* shape_ops() {
 #endif
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
-                               ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr};
+                               ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr,
+                               launch_plant_feedback, launch_model_feedback};
   return &ops;
 }
 

@@ -10,6 +10,7 @@ from abc import ABC, abstractmethod
 import numpy as np
 
 from . import _lib
+from .feedback import plant_feedback_batch
 from .noise import require_noise
 from .rollout import held_controls, plant_rollout_batch
 
@@ -77,6 +78,16 @@ def _simulate_batch(exp, x0s, ts, us, op0, u_scale, W, target, keep, figure):
     u = held_controls(us, ts, len(exp.H1_list), x0s.shape[0])
     return plant_rollout_batch(x0s, u, own0 if op0 is None else op0, ops, ts, exp.plant_kind, u_scale=u_scale, W=W, target=target,
                                keep=keep, figure=figure)
+
+
+def _feedback_batch(exp, x0s, ts, law, op0, u_scale, noise, W, target, keep, figure, controls):
+    """feedback_batch of the three device plants: simulate_batch's arguments, a FeedbackLaw in the controls' place."""
+    x0s = np.asarray(x0s, dtype=np.complex128)
+    if x0s.ndim == 1:
+        x0s = x0s[None]
+    own0, ops = exp.operators()
+    return plant_feedback_batch(x0s, law, own0 if op0 is None else op0, ops, ts, exp.plant_kind, u_scale=u_scale, noise=noise, W=W,
+                                target=target, keep=keep, figure=figure, controls=controls)
 
 
 def _gradient_batch(exp, x0s, ts, us, W, target, op0, u_scale, figure, weights, reduce, scale_grad):
@@ -179,6 +190,14 @@ class QExperiment(Experiment):
         u_scale [B, m]: the members' drive-amplitude factors.  Returns the dict of plant_rollout_batch: "xs" [B, len(ts), n] (ensemble
         axis first) and / or "q".  Noise-free, and no expectation values: e_ops, set_sigma and set_noise act on simulate() and mpc()."""
         return _simulate_batch(self, x0s, ts, us, op0, u_scale, W, target, keep, figure)
+
+    def feedback_batch(self, x0s, ts, law, op0=None, u_scale=None, noise=None, W=None, target=None, keep="all", figure="none",
+                       controls=True):
+        """simulate_batch with a stored FeedbackLaw closing the loop (plant_feedback_batch): at every point of ts but the last the
+        law reads each member's state and its control is held to the next point.  x0s, ts, op0, u_scale, W, target, keep, figure as
+        simulate_batch; noise: a MeasurementNoise added to every stored state but x0s, or None (set_noise and set_sigma act on mpc()
+        and simulate()).  Returns plant_feedback_batch's dict: "xs", "q", "us" [B, len(ts) - 1, m], "clipped", "status"."""
+        return _feedback_batch(self, x0s, ts, law, op0, u_scale, noise, W, target, keep, figure, controls)
 
     def gradient_batch(self, x0s, ts, us, W, target, op0=None, u_scale=None, figure="last", weights=None, reduce=False,
                        scale_grad=False):
@@ -318,6 +337,14 @@ class QSynthesis(Experiment):
         u_scale [B, m]: the members' drive-amplitude factors.  Returns the dict of plant_rollout_batch: "xs" [B, len(ts), n] (ensemble
         axis first) and / or "q".  Noise-free, and no expectation values: e_ops, set_sigma and set_noise act on simulate() and mpc()."""
         return _simulate_batch(self, x0s, ts, us, op0, u_scale, W, target, keep, figure)
+
+    def feedback_batch(self, x0s, ts, law, op0=None, u_scale=None, noise=None, W=None, target=None, keep="all", figure="none",
+                       controls=True):
+        """simulate_batch with a stored FeedbackLaw closing the loop (plant_feedback_batch): at every point of ts but the last the
+        law reads each member's state and its control is held to the next point.  x0s, ts, op0, u_scale, W, target, keep, figure as
+        simulate_batch; noise: a MeasurementNoise added to every stored state but x0s, or None (set_noise and set_sigma act on mpc()
+        and simulate()).  Returns plant_feedback_batch's dict: "xs", "q", "us" [B, len(ts) - 1, m], "clipped", "status"."""
+        return _feedback_batch(self, x0s, ts, law, op0, u_scale, noise, W, target, keep, figure, controls)
 
     def gradient_batch(self, x0s, ts, us, W, target, op0=None, u_scale=None, figure="last", weights=None, reduce=False,
                        scale_grad=False):

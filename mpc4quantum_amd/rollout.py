@@ -49,12 +49,13 @@ def _plant_dim(kind, n):
     raise ValueError("kind must be PLANT_HAMILTONIAN, PLANT_GENERATOR or PLANT_PROCESS, got %r" % (kind,))
 
 
-def _common(x0, us, u_scale, W, target, keep, figure):
-    """Checks and lays out what the two rollouts share.  Returns (x0, us, u_per, u_scale, W, target, t_per, xs_mode, q_mode)."""
+def _common(x0, us, u_scale, W, target, keep, figure, need_output=True):
+    """Checks and lays out what the two rollouts share.  Returns (x0, us, u_per, u_scale, W, target, t_per, xs_mode, q_mode).
+    need_output: neither states nor figures is a refusal (the feedback runs, which return more, pass False)."""
     if keep not in _MODES or figure not in _MODES:
         raise ValueError('keep and figure must be "none", "last" or "all", got %r and %r' % (keep, figure))
     xs_mode, q_mode = _MODES[keep], _MODES[figure]
-    if xs_mode == 0 and q_mode == 0:
+    if need_output and xs_mode == 0 and q_mode == 0:
         raise ValueError('keep="none" with figure="none": nothing to return')
     x0 = np.ascontiguousarray(x0, dtype=np.complex128)
     if x0.ndim != 2 or x0.shape[0] < 1 or x0.shape[1] < 1:
