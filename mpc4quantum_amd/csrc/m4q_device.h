@@ -177,6 +177,20 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---- issue priority of the wavefront (s_setprio, 0..3): between the wavefronts of a SIMD the arbiter takes the higher level first and,
+// at equal levels, the older wavefront.  The instruction is scalar and ignores EXEC: call it in wave-uniform control flow only,
+// at a phase boundary of a persistent loop, never inside a horizon loop.  PrioMap: the level of every phase of mpc_kernel's main
+// loop after the draw, which always runs at 0 (a kernel whose map is all zeros issues no s_setprio at all).
+struct PrioMap {
+  int sweep, rollout, line_search, update, step_done, publish;
+  constexpr bool any() const { return (sweep | rollout | line_search | update | step_done | publish) != 0; }
+};
+template <bool ON, int P>
+__device__ __forceinline__ void issue_prio() {
+  static_assert(P >= 0 && P <= 3, "s_setprio takes a level 0..3");
+  if constexpr (ON) __builtin_amdgcn_s_setprio(P);
+}
+
 // ---- development builds (-DM4Q_DEV_PHASE_CLOCK): wavefront time per phase of the persistent loop, summed on the constant
 // 100 MHz clock; an empty object otherwise.  Slots: see m4q_session_qp_stats (M4Q_PHASE_TRACE=1 prints them).
 struct PhaseClock {

@@ -273,6 +273,19 @@ constexpr int NXC = (int)(sizeof(XCUTS) / sizeof(int));
 // the shared-generator and the tile kernels are compiled for two wavefronts per SIMD at every shape
 constexpr int WAVES_SG = 2;
 constexpr int WAVES_TILE = 2;
+// Issue priority by phase of the main loop (PrioMap, m4q_device.h), per instantiation and shape.  The two wavefronts of a SIMD run this
+// kernel unsynchronised; at equal priority the older one wins every issue conflict for the whole launch, whatever the two are doing:
+// a younger wavefront's rollout - a dependent chain of 4-cycle FMAs - then waits behind the older one's back-to-back 16-cycle MFMAs.
+// With the sweep at 0 and every later phase of the pass at 1 the short instruction goes first and the sweep, which has independent
+// MFMAs to spare, takes the remaining slots; no wavefront waits for another and no arithmetic changes.  Config 3 (the clipped tile
+// kernel at n = 8): -1.2 to -1.3 % in each of three alternations against a 0.05 % spread of the parent's runs; the short phases at 2 above
+// the rollout: the same; the sweep at 1 above everything else: +1.0 % (profiles/r07_ab_experiments.txt).  Kernels, shapes and
+// plants that have not been measured faster with levels keep all zeros: their code is then the same as without this table.
+template <class S, int PLANT, bool EXACT, bool TL, bool TILE, bool SG>
+constexpr PrioMap prio_map() {
+  if (TILE && !EXACT && NX == 9 && PLANT == PLANT_HAMILTONIAN) return PrioMap{0, 1, 1, 1, 1, 1};
+  return PrioMap{0, 0, 0, 0, 0, 0};
+}
 // Development builds (-DM4Q_DEV_PHASE_CLOCK): PhaseClock (m4q_device.h) sums the 100 MHz clock over the phases of the main loop; every
 // wavefront adds its sums to queue[8..23] (u64) on exit; M4Q_PHASE_TRACE=1 makes m4q_session_qp_stats print them.
 #if defined(M4Q_DEV_PHASE_CLOCK)
@@ -391,6 +404,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
   // results bit-identical): the complex path runs at 2.30 GHz instead of 2.04 (133.3 -> 117.6 ms, config 3), the real path at 2.29
   // instead of 2.18 (51.2 -> 50.4 ms; config 5's share 171.2 -> 166.3 ms).  profiles/r02_ab_experiments.txt, r02_clock_ramp.txt.
   constexpr bool MASK_IDLE = NS < 16 && !EXACT && !TILE;
+  // (the levels change at the phase boundaries of the main loop only, outside every lane-dependent branch: s_setprio ignores EXEC)
+  constexpr PrioMap PRIO = prio_map<S, PLANT, EXACT, TL, TILE, SG>();
+  constexpr bool PRIO_ON = PRIO.any();
+  static_assert(!EXACT || !PRIO_ON, "the exact solve's phases are those of box_qp_iterate: no levels there yet");
   GView Xg, Ug, Xo, Uo, gains, Xalt, Ualt, pin_stat;
   {
     KArgs* a = kargs();
@@ -619,6 +636,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
       __builtin_amdgcn_s_sleep(8);                 // only tail items whose head is still running: poll again
       continue;
     }
+    issue_prio<PRIO_ON && PRIO.sweep != 0, PRIO.sweep>();
     const bool running = active && step < row_end;
     if constexpr (SG) {
 #pragma unroll
@@ -695,6 +713,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
           M4Q_PHASE_MARK(1)
         }
         wave_sync();
+        issue_prio<PRIO_ON && PRIO.rollout != PRIO.sweep, PRIO.rollout>();
         // the rollout on DPP rows (on tiles it was built twice: round 3's per-index form took 2.3 times as long, round 4's time-batched
         // form - tools/tile_rollout_r04.h - the same SIMD time at d = 3 and 14 % more of the launch at d = 2)
         // (idle lanes sit it out as in the DPP kernels: MASK_IDLE itself is off for TILE because the tile sweep needs all 64 lanes)
@@ -721,6 +740,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
         M4Q_PHASE_MARK(3)
         if (!tc && (!MASK_IDLE || lane_ok)) riccati_backward<S, NS, NU>(prov, T, win, cost, flags, gains, j, st);
         wave_sync();
+        issue_prio<PRIO_ON && PRIO.rollout != PRIO.sweep, PRIO.rollout>();
         M4Q_PHASE_MARK(1)
         if constexpr (HAS_TC) {
           if (tc && (!MASK_IDLE || lane_ok))
@@ -839,6 +859,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
       }
     }
     wave_sync();
+    issue_prio<PRIO_ON && PRIO.line_search != PRIO.rollout, PRIO.line_search>();
     M4Q_PHASE_MARK(EXACT ? 15 : 2)
 #if defined(M4Q_DEV_PHASE_CLOCK)
     if (__any(running && !(kargs()->warm_start && step > 1))) pc.count(9);      // passes with a line search
@@ -878,6 +899,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
       if (use_ls) { alpha = al; fin = stepn < a->ls_tol; }   // mpc.py:224
     }
     wave_sync();
+    issue_prio<PRIO_ON && PRIO.update != PRIO.line_search, PRIO.update>();
     M4Q_PHASE_MARK(4)
     const bool upd = solved && !fail && use_ls;       // warm steps wrote the shifted guess in the rollout
     // X_guess += alpha (X_opt - X_guess) (mpc.py:228-229)
@@ -970,6 +992,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
       }
     }
     wave_sync();
+    issue_prio<PRIO_ON && PRIO.step_done != PRIO.update, PRIO.step_done>();
 
     M4Q_PHASE_MARK(8)
     // ---- rows that finished their MPC step: apply, propagate, shift ----
@@ -1106,6 +1129,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
       }
     }
 
+    issue_prio<PRIO_ON && PRIO.publish != PRIO.step_done, PRIO.publish>();
     M4Q_PHASE_MARK(5)
     // ---- rows that finished their item: publish the resumable state, free the slot ----
     const bool finished = active && step >= row_end;
@@ -1207,6 +1231,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
     }
     M4Q_PHASE_MARK(6)
     pc.count(7);
+    // back to level 0 (the level a wavefront starts at) before the pass ends, so that every way round the loop arrives there at 0:
+    // the watchdog exit, the draw (atomics and waits: memory latency, not issue), the final break and a wavefront that only polls
+    // - a poller must not outrank the head it waits for - all run between here and the first switch of the next pass
+    issue_prio<PRIO_ON, 0>();
   }
 }
 
