@@ -328,6 +328,33 @@ M4Q_API int m4q_dmdc_fit_qr_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32
                           const double* u, int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R,
                           double* models, int32_t* ranks, double* svals, int32_t* status);
 
+/* The two fits against a prior model: one DiscrepDMDc.fit_iteration (model.py:186-207) for B members in ONE launch,
+ *   A_r = A0 + (Y - A0 Z) pinv(Z, rconds[r]) on the discounted stacks = A0 (I - Pi_r) + Y Z_r^+,
+ * the fit where the data excited the plant, the prior A0 everywhere else.  m4q_dmdc_refit_batch takes m4q_dmdc_fit_batch's route,
+ * m4q_dmdc_refit_qr_batch m4q_dmdc_fit_qr_batch's; the first 16 arguments, the results and the rcond range are that entry point's.
+ * mpc4quantum_amd/fit.py (dmdc_fit_reference / dmdc_fit_qr_reference with A0, discount, counts) is the definition.
+ * A0 [B|1][n][nz] c: the prior model (A0_per_instance 0: one for the ensemble); discount [B|1] r, each in (0, 1]: snapshot s of the S
+ * a member takes has weight discount^(S-1-s); counts [B] or NULL: member b takes only t < counts[b] of every experiment
+ * (0 <= counts[b] <= N), as m4q_online_dmdc_batch does.  Per member:
+ * - Gram route: before a snapshot is accumulated G <- d2 G, C <- d2 C (and the sums behind svals likewise), d2 = discount * discount
+ *   formed once and each product rounded on its own; after the last one D[i][l] = C[i][l] - sum_k A0[i][k] G[k][l] (k ascending, the
+ *   terms subtracted one at a time) takes C's place.
+ * - QR route: R <- discount R, T <- discount T before a snapshot's rotations; after the last one
+ *   T[j][i] <- T[j][i] - sum_{k >= j} R[j][k] conj(A0[i][k]), k ascending.
+ * - spectrum, ranks, svals (those of the weighted stack) and truncated products as in the plain fit; A0 is added once to every entry
+ *   of every A_r.  With A0 = 0, discount = 1 and counts NULL (or N) the results are the plain fit's, number for number.
+ * status [B]: as the plain fit, and 3 also for a non-finite A0 (zero models).  counts[b] = 0: models = A0, rank 0, status 0.
+ * M4Q_E_BADARG: what the plain fit refuses, a missing A0 or discount, a discount outside (0, 1] (or NaN), a count outside [0, N].
+ * M4Q_E_UNSUPPORTED: exactly where the plain fit returns it.  Arguments are checked before the device is asked for. */
+M4Q_API int m4q_dmdc_refit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs,
+                         const double* u, int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R,
+                         double* models, int32_t* ranks, double* svals, int32_t* status, const double* A0,
+                         int32_t A0_per_instance, const double* discount, int32_t discount_per_instance, const int32_t* counts);
+M4Q_API int m4q_dmdc_refit_qr_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs,
+                         const double* u, int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R,
+                         double* models, int32_t* ranks, double* svals, int32_t* status, const double* A0,
+                         int32_t A0_per_instance, const double* discount, int32_t discount_per_instance, const int32_t* counts);
+
 /* Recursive DMDc updates for an ensemble in ONE launch: OnlineDMDc.fit_iteration (model.py:216-313, recursive least squares with a
  * forgetting factor) fed with every snapshot of B members - what mpc(..., streaming=True) does to its model, for an ensemble.
  * mpc4quantum_amd/online.py (online_dmdc_reference) is the definition, in NumPy, in the kernel's order of operations.

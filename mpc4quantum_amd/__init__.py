@@ -7,7 +7,7 @@ from .experiment import (Experiment, LExperiment, QCoupledExperiment, QExperimen
                          isqrt, plant_step_batch, process_dim, split_blocks)
 from .feedback import (FeedbackLaw, model_feedback_batch, model_feedback_reference, plant_feedback_batch,  # noqa: F401
                        plant_feedback_reference)
-from .fit import dmdc_fit_batch, dmdc_fit_qr_reference, dmdc_fit_reference, train_models_batch  # noqa: F401
+from .fit import dmdc_fit_batch, dmdc_fit_qr_reference, dmdc_fit_reference, refit_models_batch, train_models_batch  # noqa: F401
 from .grad import (model_rollout_grad_batch, model_rollout_grad_reference, ordered_weighted_sum,  # noqa: F401
                    plant_rollout_grad_batch, plant_rollout_grad_reference)
 from .library import (create_library, create_library_from_list, create_power_list, diff_library, krtimes,  # noqa: F401

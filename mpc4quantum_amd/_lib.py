@@ -82,6 +82,10 @@ PROTOTYPES = {
                                            _dp, _ip, _ip]),
     "m4q_dmdc_fit_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _ip]),
     "m4q_dmdc_fit_qr_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _ip]),
+    "m4q_dmdc_refit_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _ip,
+                                       _dp, _i32, _dp, _i32, _ip]),
+    "m4q_dmdc_refit_qr_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _ip,
+                                          _dp, _i32, _dp, _i32, _ip]),
     "m4q_online_dmdc_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _ip, _dp, _i32, _dp, _i32, C.c_double,
                                         _dp, _i32, _i32, _i32, _dp, _dp, _dp, _dp, _ip]),
     "m4q_mpc_batch": (C.c_int, [C.POINTER(Problem), _i32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip,

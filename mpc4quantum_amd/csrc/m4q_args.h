@@ -190,6 +190,15 @@ struct FitArgs {
   M4Q_P(int) status;                               // [B]: 0 ok, 1 the Jacobi iteration hit its cap, 3 non-finite data
 };
 
+// m4q_dmdc_refit_batch, m4q_dmdc_refit_qr_batch: the same fit against a prior model, A0 + the truncated fit of Y - A0 Z (fit.py's
+// last part).  Member b takes the first counts[b] steps of each experiment (N when counts is null), weighted discount^(age).
+struct RefitArgs {
+  FitArgs fit;
+  M4Q_P(const int) counts;                         // [B] or null
+  M4Q_P(const cplx) A0; long A0_stride;            // [B|1][n][nz]
+  M4Q_P(const double) discount; long discount_stride;     // [B|1]
+};
+
 // m4q_online_dmdc_batch: OnlineDMDc.fit_iteration for every snapshot of B members (m4q_online.h; online.py is the definition).
 // The snapshots are FitArgs'; member b takes the first counts[b] steps of each experiment (N when counts is null).
 struct OnlineArgs {
@@ -275,6 +284,8 @@ struct ShapeOps {
   int (*launch_fit_qr)(const FitArgs&, hipStream_t);               // dmdc_fit_qr_kernel: the shapes and the LDS of launch_fit
   int (*launch_plant_feedback)(const FeedbackArgs&, hipStream_t);  // (the shapes of launch_plant_rollout)
   int (*launch_model_feedback)(const FeedbackArgs&, hipStream_t);  // (the shapes of launch_model_rollout)
+  int (*launch_refit)(const RefitArgs&, hipStream_t);              // dmdc_refit_kernel, dmdc_refit_qr_kernel: the shapes and the
+  int (*launch_refit_qr)(const RefitArgs&, hipStream_t);           // LDS of launch_fit
 };
 
 }  // namespace m4q

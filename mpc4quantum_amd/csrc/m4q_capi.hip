@@ -1455,10 +1455,18 @@ int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
   return st.finish(sh->launch_model_grad(a, nullptr), "model rollout gradient");
 }
 
-// the two routes of the DMDc fit share their arguments, their checks and their staging: qr names m4q_dmdc_fit_qr_batch
+// what the fit against a prior model adds to the fit's arguments (m4q_dmdc_refit_batch, m4q_dmdc_refit_qr_batch)
+struct PriorIn {
+  const double* A0; int32_t A0_per_instance;
+  const double* discount; int32_t discount_per_instance;
+  const int32_t* counts;
+};
+
+// the two routes of the DMDc fit share their arguments, their checks and their staging: qr names the QR route's entry points;
+// prior: the fit against a prior model (the refit entry points), null for the plain fit
 static int dmdc_fit(const char* who, bool qr, int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs,
                     const double* u, int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R, double* models,
-                    int32_t* ranks, double* svals, int32_t* status) {
+                    int32_t* ranks, double* svals, int32_t* status, const PriorIn* prior = nullptr) {
   const m4q::ShapeOps* sh = find_shape(dim_x, dim_u, order);
   if (!sh) return fail(M4Q_E_UNSUPPORTED, "no model kernel for dim_x=%d dim_u=%d order=%d", dim_x, dim_u, order);
   if (sh->fit_lds_bytes == 0)
@@ -1474,11 +1482,22 @@ static int dmdc_fit(const char* who, bool qr, int32_t B, int32_t dim_x, int32_t 
       return fail(M4Q_E_BADARG, "%s: rconds[%d] = %g is outside [%g, 1): below that the cut-off lies in the %s "
                   "(fit on the host with DiscrepDMDc.from_data)", who, r, rconds[r], rcond_min,
                   qr ? "rounding of the data themselves" : "Gram matrix's rounding floor");
+  if (prior) {
+    if (!prior->A0 || !prior->discount) return fail(M4Q_E_BADARG, "%s: A0 and discount are required", who);
+    for (int b = 0; b < (prior->discount_per_instance ? B : 1); ++b)
+      if (!(prior->discount[b] > 0.0 && prior->discount[b] <= 1.0))
+        return fail(M4Q_E_BADARG, "%s: discount[%d] = %g is outside (0, 1]", who, b, prior->discount[b]);
+    if (prior->counts)
+      for (int b = 0; b < B; ++b)
+        if (prior->counts[b] < 0 || prior->counts[b] > N)
+          return fail(M4Q_E_BADARG, "%s: counts[%d] = %d is outside [0, N = %d]", who, b, prior->counts[b], N);
+  }
   if (int rc = need_device()) return rc;
   const size_t n = dim_x, m = dim_u, nz = n * (1 + (size_t)sh->np);
   const Extent eu(B, u_per_instance, (size_t)E * N * m);
   Stage st;
-  m4q::FitArgs a{};
+  m4q::RefitArgs ra{};
+  m4q::FitArgs& a = ra.fit;
   a.B = B; a.E = E; a.N = N; a.R = R;
   a.xs = st.in<cplx>(xs, (size_t)B * E * ((size_t)N + 1) * n);
   a.u = st.in<double>(u, eu.count); a.u_stride = eu.stride;
@@ -1488,7 +1507,16 @@ static int dmdc_fit(const char* who, bool qr, int32_t B, int32_t dim_x, int32_t 
   if (ranks) a.ranks = st.out<int>(ranks, (size_t)R * B);
   if (svals) a.svals = st.out<double>(svals, (size_t)B * nz);
   a.status = st.out<int>(status, B);
+  if (prior) {
+    const Extent ea(B, prior->A0_per_instance, n * nz), ed(B, prior->discount_per_instance, 1);
+    ra.A0 = st.in<cplx>(prior->A0, ea.count); ra.A0_stride = ea.stride;
+    ra.discount = st.in<double>(prior->discount, ed.count); ra.discount_stride = ed.stride;
+    if (prior->counts) ra.counts = st.in<int>(prior->counts, B);
+  }
   if (st.error()) return st.error();
+  if (prior)
+    return qr ? st.finish(sh->launch_refit_qr(ra, nullptr), "DMDc fit against a prior (QR)")
+              : st.finish(sh->launch_refit(ra, nullptr), "DMDc fit against a prior");
   return qr ? st.finish(sh->launch_fit_qr(a, nullptr), "DMDc fit (QR)") : st.finish(sh->launch_fit(a, nullptr), "DMDc fit");
 }
 
@@ -1504,6 +1532,24 @@ int m4q_dmdc_fit_qr_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order
                           double* svals, int32_t* status) {
   return dmdc_fit("m4q_dmdc_fit_qr_batch", true, B, dim_x, dim_u, order, E, N, xs, u, u_per_instance, u_scale, rconds, R, models, ranks,
                   svals, status);
+}
+
+int m4q_dmdc_refit_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs, const double* u,
+                         int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R, double* models, int32_t* ranks,
+                         double* svals, int32_t* status, const double* A0, int32_t A0_per_instance, const double* discount,
+                         int32_t discount_per_instance, const int32_t* counts) {
+  const PriorIn prior{A0, A0_per_instance, discount, discount_per_instance, counts};
+  return dmdc_fit("m4q_dmdc_refit_batch", false, B, dim_x, dim_u, order, E, N, xs, u, u_per_instance, u_scale, rconds, R, models, ranks,
+                  svals, status, &prior);
+}
+
+int m4q_dmdc_refit_qr_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs, const double* u,
+                            int32_t u_per_instance, const double* u_scale, const double* rconds, int32_t R, double* models, int32_t* ranks,
+                            double* svals, int32_t* status, const double* A0, int32_t A0_per_instance, const double* discount,
+                            int32_t discount_per_instance, const int32_t* counts) {
+  const PriorIn prior{A0, A0_per_instance, discount, discount_per_instance, counts};
+  return dmdc_fit("m4q_dmdc_refit_qr_batch", true, B, dim_x, dim_u, order, E, N, xs, u, u_per_instance, u_scale, rconds, R, models,
+                  ranks, svals, status, &prior);
 }
 
 int m4q_online_dmdc_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t E, int32_t N, const double* xs, const double* u,

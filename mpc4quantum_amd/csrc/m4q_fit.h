@@ -9,6 +9,10 @@
 // (lane stride 16 B) and those down a column (lane stride PITCH 16 B) spread over the banks.
 // All control flow is wave-uniform by construction (one member per wavefront); the rotation and truncation decisions are made
 // uniform for the compiler too (readfirstlane), so they are scalar branches.
+//
+// REFIT (dmdc_refit_kernel, dmdc_refit_qr_kernel; RefitArgs): the fit against a prior model A0, A0 + (Y - A0 Z) pinv(Z, rcond) on
+// the member's first `steps` snapshots of every experiment, weighted discount^(age) - fit.py's last part.  The flag adds to the
+// functions below what FitPrior describes and leaves their REFIT = false instances as they were.
 #pragma once
 #include "m4q_args.h"
 #include "m4q_mpc.h"
@@ -31,6 +35,33 @@ struct FitLayout {
 };
 
 __device__ __forceinline__ bool uniform(bool c) { return __builtin_amdgcn_readfirstlane((int)c) != 0; }
+
+// The member's part of a fit against a prior model: its A0 [n][nz], the steps it takes of every experiment, its discount.
+struct FitPrior {
+  const M4Q_GLOBAL cplx* A0;
+  int steps;
+  double discount;
+};
+
+// acc -= a * b
+__device__ __forceinline__ void cmsub(cplx& acc, cplx a, cplx b) {
+  acc.re = fma(-a.re, b.re, acc.re);
+  acc.re = fma(a.im, b.im, acc.re);
+  acc.im = fma(-a.re, b.im, acc.im);
+  acc.im = fma(-a.im, b.re, acc.im);
+}
+
+// Whether column l of the member's A0 is finite, for every lane: the prior's part of status 3.
+template <int NX, int NZ>
+__device__ __forceinline__ bool prior_finite(const FitPrior& pr, int l) {
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < NX; ++i) {
+    const cplx v = gld(pr.A0, i * NZ + l);
+    ok = ok && finite_d(v.re) && finite_d(v.im);
+  }
+  return !__any(!ok);
+}
 
 // (a', b') = (c a - conj(sw) b, sw a + c b): columns p, q of M J for the rotation J = [[c, sw], [-conj(sw), c]]
 __device__ __forceinline__ void rotate_pair(double c, cplx sw, cplx a, cplx b, cplx& an, cplx& bn) {
@@ -90,8 +121,11 @@ __device__ __forceinline__ void fit_stream(const Args& a, long b, cplx* lds, int
 // Phase 1: G = sum z z^H (upper triangle accumulated, then mirrored), C = sum x_{t+1} z^H over the member's snapshots.
 // The accumulators live in LDS: at nz = 64 they are 4096 + 1024 complex numbers, 160 doubles per lane, and the streaming phase is a
 // small part of the run beside the rotations.  Returns false if G or C holds a non-finite entry.
-template <int NX, int NU, int ORDER>
-__device__ __forceinline__ bool fit_accumulate(const FitArgs& a, long b, cplx* lds, int lane) {
+// REFIT: only t < steps of every experiment; G <- d2 G, C <- d2 C before a snapshot is accumulated, d2 = discount^2 and the product
+// rounded on its own; afterwards D = C - A0 G takes C's place, D[i][l] = C[i][l] - sum_k A0[i][k] G[k][l] with k ascending (lane l on
+// column l; every lane reads the same A0[i][k]: a broadcast).  Returns false for a non-finite A0, too.
+template <int NX, int NU, int ORDER, bool REFIT = false>
+__device__ __forceinline__ bool fit_accumulate(const FitArgs& a, long b, cplx* lds, int lane, const FitPrior& pr = FitPrior{}) {
   using L = FitLayout<NX, NU, ORDER>;
   constexpr int NZ = L::NZ, PITCH = L::PITCH;
   cplx* G = lds + L::G;
@@ -106,12 +140,20 @@ __device__ __forceinline__ bool fit_accumulate(const FitArgs& a, long b, cplx* l
 #pragma unroll
     for (int i = 0; i < NX; ++i) C[i * PITCH + l] = czero();
   }
+  [[maybe_unused]] const double d2 = pr.discount * pr.discount;
+  [[maybe_unused]] int t = 0;
   fit_stream<NX, NU, ORDER>(a, b, lds, lane, [&](cplx z) {
+    if constexpr (REFIT) {               // beyond the member's count the snapshot streams past
+      const bool taken = uniform(t < pr.steps);
+      if (++t == a.N) t = 0;
+      if (!taken) return;
+    }
     if (act) {
 #pragma unroll 1
       for (int i = 0; i < NZ; ++i) {
         if (i <= l) {
           cplx g = G[i * PITCH + l];
+          if constexpr (REFIT) g = cscale(g, d2);
           cmac_cj(g, z, Z[i]);           // += z_i conj(z_l)
           G[i * PITCH + l] = g;
         }
@@ -119,6 +161,7 @@ __device__ __forceinline__ bool fit_accumulate(const FitArgs& a, long b, cplx* l
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
         cplx c = C[i * PITCH + l];
+        if constexpr (REFIT) c = cscale(c, d2);
         cmac_cj(c, z, XN[i]);
         C[i * PITCH + l] = c;
       }
@@ -136,6 +179,26 @@ __device__ __forceinline__ bool fit_accumulate(const FitArgs& a, long b, cplx* l
     for (int i = 0; i < NX; ++i) ok = ok && finite_d(C[i * PITCH + l].re) && finite_d(C[i * PITCH + l].im);
   }
   wave_sync();
+  if constexpr (REFIT) {
+    const bool finite = !__any(!ok) && prior_finite<NX, NZ>(pr, l);
+    if (uniform(finite)) {
+      cplx d[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) d[i] = C[i * PITCH + l];
+#pragma unroll 1
+      for (int k = 0; k < NZ; ++k) {
+        const cplx g = G[k * PITCH + l];
+#pragma unroll
+        for (int i = 0; i < NX; ++i) cmsub(d[i], gld(pr.A0, i * NZ + k), g);
+      }
+      if (act) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) C[i * PITCH + l] = d[i];
+      }
+      wave_sync();
+    }
+    return finite;
+  }
   return !__any(!ok);
 }
 
@@ -198,8 +261,9 @@ __device__ __forceinline__ bool fit_jacobi(cplx* G, cplx* V, int lane) {
 // themselves in a second pass over them, lane l on column l of V; every term is non-negative, so a singular value that is zero
 // comes out at the rounding of the inner products (~eps s_0), not at sqrt of the rounding floor of G (~1e-8 s_0).  Stored in
 // descending order by rank-counting in LDS (Z's place).  ok = false: zeros.
-template <int NX, int NU, int ORDER>
-__device__ __forceinline__ void fit_svals(const FitArgs& a, long b, cplx* lds, int lane, bool ok) {
+// REFIT: the sums of the weighted stack, by G's recurrence: only t < steps, s2 <- d2 s2 (a product of its own) before a term is added.
+template <int NX, int NU, int ORDER, bool REFIT = false>
+__device__ __forceinline__ void fit_svals(const FitArgs& a, long b, cplx* lds, int lane, bool ok, const FitPrior& pr = FitPrior{}) {
   using L = FitLayout<NX, NU, ORDER>;
   constexpr int NZ = L::NZ, PITCH = L::PITCH;
   const cplx* V = lds + L::V;
@@ -212,7 +276,16 @@ __device__ __forceinline__ void fit_svals(const FitArgs& a, long b, cplx* lds, i
     return;
   }
   double s2 = 0.0;
+  [[maybe_unused]] const double d2 = pr.discount * pr.discount;
+  [[maybe_unused]] int t = 0;
   fit_stream<NX, NU, ORDER>(a, b, lds, lane, [&](cplx) {
+    if constexpr (REFIT) {
+      const bool taken = uniform(t < pr.steps);
+      if (++t == a.N) t = 0;
+      if (!taken) return;
+      s2 *= d2;
+      asm volatile("" : "+v"(s2));       // (rounded before the add: the empty asm keeps the two from contracting into an FMA)
+    }
     cplx d = czero();
 #pragma unroll 1
     for (int j = 0; j < NZ; ++j) cmac_cj(d, V[j * PITCH + l], Z[j]);      // += conj(V[j][l]) z_j
@@ -232,8 +305,10 @@ __device__ __forceinline__ void fit_svals(const FitArgs& a, long b, cplx* lds, i
 
 // The truncated products of phase 3, shared with the QR route (m4q_fit_qr.h): C holds W[:, k] / lam_k, LAM the spectrum and lmax
 // its maximum; per rcond A = sum_{lam_k > rcond^2 lmax} C[:, k] V[:, k]^H, lane l on column l of A.  ok = false: zero models and ranks.
-template <int NX, int NU, int ORDER>
-__device__ __forceinline__ void fit_truncate(const FitArgs& a, long b, cplx* lds, int lane, bool ok, double lmax) {
+// REFIT: A0 is added to every entry of the finished sum.
+template <int NX, int NU, int ORDER, bool REFIT = false>
+__device__ __forceinline__ void fit_truncate(const FitArgs& a, long b, cplx* lds, int lane, bool ok, double lmax,
+                                             const FitPrior& pr = FitPrior{}) {
   using L = FitLayout<NX, NU, ORDER>;
   constexpr int NZ = L::NZ, PITCH = L::PITCH;
   const cplx* V = lds + L::V;
@@ -257,6 +332,10 @@ __device__ __forceinline__ void fit_truncate(const FitArgs& a, long b, cplx* lds
 #pragma unroll
         for (int i = 0; i < NX; ++i) cmac(acc[i], C[i * PITCH + k], v);
       }
+      if constexpr (REFIT) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) acc[i] = cadd(acc[i], gld(pr.A0, i * NZ + l));
+      }
     }
     const long m0 = ((long)r * a.B + b) * NX * NZ;
     if (act) {
@@ -270,8 +349,8 @@ __device__ __forceinline__ void fit_truncate(const FitArgs& a, long b, cplx* lds
 // Phase 3: eigenvalues, then per rcond the truncated product
 // A = sum_{lam_k > rcond^2 max(lam)} (W[:, k] / lam_k) V[:, k]^H with W = C V; lane l holds column l of A and stores it along the nz
 // axis (coalesced).  ok = false: zero models and ranks.
-template <int NX, int NU, int ORDER>
-__device__ __forceinline__ void fit_models(const FitArgs& a, long b, cplx* lds, int lane, bool ok) {
+template <int NX, int NU, int ORDER, bool REFIT = false>
+__device__ __forceinline__ void fit_models(const FitArgs& a, long b, cplx* lds, int lane, bool ok, const FitPrior& pr = FitPrior{}) {
   using L = FitLayout<NX, NU, ORDER>;
   constexpr int NZ = L::NZ, PITCH = L::PITCH;
   cplx* G = lds + L::G;
@@ -305,7 +384,7 @@ __device__ __forceinline__ void fit_models(const FitArgs& a, long b, cplx* lds, 
     }
     wave_sync();
   }
-  fit_truncate<NX, NU, ORDER>(a, b, lds, lane, ok, lmax);
+  fit_truncate<NX, NU, ORDER, REFIT>(a, b, lds, lane, ok, lmax, pr);
 }
 
 }  // namespace m4q

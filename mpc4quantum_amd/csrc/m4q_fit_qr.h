@@ -44,8 +44,11 @@ __device__ __forceinline__ void givens_pair(cplx c, cplx s, cplx a, cplx b, cplx
 
 // Phase 1: the streaming QR.  R = 0, T = 0; every snapshot's row (z^H | y^H) is rotated into them, j = 0 .. nz - 1.
 // Returns false if R or T holds a non-finite entry (any non-finite sample produces one).
-template <int NX, int NU, int ORDER>
-__device__ __forceinline__ bool fit_qr_factor(const FitArgs& a, long b, cplx* lds, int lane) {
+// REFIT (m4q_fit.h): only t < steps of every experiment; R <- discount R, T <- discount T before a snapshot's rotations, every lane
+// on the entries it rotates; afterwards T[j][i] <- T[j][i] - sum_{k >= j} R[j][k] conj(A0[i][k]), k ascending, lane j on row j of R
+// and of T.  Returns false for a non-finite A0, too.
+template <int NX, int NU, int ORDER, bool REFIT = false>
+__device__ __forceinline__ bool fit_qr_factor(const FitArgs& a, long b, cplx* lds, int lane, const FitPrior& pr = FitPrior{}) {
   using L = FitLayout<NX, NU, ORDER>;
   constexpr int NZ = L::NZ, PITCH = L::PITCH;
   cplx* R = lds + L::G;
@@ -61,7 +64,22 @@ __device__ __forceinline__ bool fit_qr_factor(const FitArgs& a, long b, cplx* ld
 #pragma unroll
     for (int i = 0; i < NX; ++i) T[i * PITCH + l] = czero();
   }
+  [[maybe_unused]] int t = 0;
   fit_stream<NX, NU, ORDER>(a, b, lds, lane, [&](cplx z) {
+    if constexpr (REFIT) {
+      const bool taken = uniform(t < pr.steps);
+      if (++t == a.N) t = 0;
+      if (!taken) return;
+      if (act) {
+#pragma unroll 1
+        for (int i = 0; i < NZ; ++i)
+          if (i <= l) R[i * PITCH + l] = cscale(R[i * PITCH + l], pr.discount);
+      }
+      if (rhs_lane) {
+#pragma unroll 1
+        for (int j = 0; j < NZ; ++j) T[lt * PITCH + j] = cscale(T[lt * PITCH + j], pr.discount);
+      }
+    }
     cplx row = cconj(z);
     cplx rhs = cconj(XN[lt]);
 #pragma unroll 1
@@ -95,6 +113,28 @@ __device__ __forceinline__ bool fit_qr_factor(const FitArgs& a, long b, cplx* ld
     for (int i = 0; i < NX; ++i) ok = ok && finite_d(T[i * PITCH + l].re) && finite_d(T[i * PITCH + l].im);
   }
   wave_sync();
+  if constexpr (REFIT) {
+    const bool finite = !__any(!ok) && prior_finite<NX, NZ>(pr, l);
+    if (uniform(finite)) {
+      cplx d[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) d[i] = T[i * PITCH + l];
+#pragma unroll 1
+      for (int k = 0; k < NZ; ++k) {
+        if (k >= l) {
+          const cplx r = R[l * PITCH + k];
+#pragma unroll
+          for (int i = 0; i < NX; ++i) cmsub(d[i], r, cconj(gld(pr.A0, i * NZ + k)));
+        }
+      }
+      if (act) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) T[i * PITCH + l] = d[i];
+      }
+      wave_sync();
+    }
+    return finite;
+  }
   return !__any(!ok);
 }
 
@@ -147,8 +187,8 @@ __device__ __forceinline__ bool fit_qr_jacobi(cplx* M, cplx* V, int lane) {
 // Phase 3: lam_k = m_k^H m_k, the singular values sqrt(lam) in descending order (by rank-counting in LDS, Z's place; this route
 // needs no second pass over the data), W = T^H M divided by lam into T's place, then the truncated products of m4q_fit.h.
 // ok = false: zero models, ranks and singular values.
-template <int NX, int NU, int ORDER>
-__device__ __forceinline__ void fit_qr_models(const FitArgs& a, long b, cplx* lds, int lane, bool ok) {
+template <int NX, int NU, int ORDER, bool REFIT = false>
+__device__ __forceinline__ void fit_qr_models(const FitArgs& a, long b, cplx* lds, int lane, bool ok, const FitPrior& pr = FitPrior{}) {
   using L = FitLayout<NX, NU, ORDER>;
   constexpr int NZ = L::NZ, PITCH = L::PITCH;
   const cplx* M = lds + L::G;
@@ -200,7 +240,7 @@ __device__ __forceinline__ void fit_qr_models(const FitArgs& a, long b, cplx* ld
     }
   }
   wave_sync();
-  fit_truncate<NX, NU, ORDER>(a, b, lds, lane, ok, lmax);
+  fit_truncate<NX, NU, ORDER, REFIT>(a, b, lds, lane, ok, lmax, pr);
 }
 
 }  // namespace m4q

@@ -1591,6 +1591,48 @@ __global__ __launch_bounds__(64) void dmdc_fit_qr_kernel(FitArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The two fits against a prior model (m4q_dmdc_refit_batch, m4q_dmdc_refit_qr_batch; fit.py's last part is the definition): the
+// kernels above with the REFIT parts of their device functions (m4q_fit.h, m4q_fit_qr.h), the same LDS layout.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ FitPrior fit_prior(const RefitArgs& a, long b) {
+  const int steps = a.counts ? gld(a.counts, b) : a.fit.N;
+  return FitPrior{a.A0 + b * a.A0_stride, __builtin_amdgcn_readfirstlane(steps), gld(a.discount, b * a.discount_stride)};
+}
+
+template <int NX_, int NU_, int ORDER_>
+__global__ __launch_bounds__(64) void dmdc_refit_kernel(RefitArgs a) {
+  using L = FitLayout<NX_, NU_, ORDER_>;
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const int lane = threadIdx.x;
+  for (long b = blockIdx.x; b < a.fit.B; b += gridDim.x) {
+    wave_sync();                                   // the previous member's reads are done
+    const FitPrior pr = fit_prior(a, b);
+    const bool finite = fit_accumulate<NX_, NU_, ORDER_, true>(a.fit, b, lds, lane, pr);
+    bool converged = true;
+    if (uniform(finite)) converged = fit_jacobi<L::NZ, L::PITCH>(lds + L::G, lds + L::V, lane);
+    if (a.fit.svals) fit_svals<NX_, NU_, ORDER_, true>(a.fit, b, lds, lane, finite, pr);
+    fit_models<NX_, NU_, ORDER_, true>(a.fit, b, lds, lane, finite, pr);
+    if (lane == 0) gst(a.fit.status, b, !finite ? 3 : converged ? 0 : 1);
+  }
+}
+
+template <int NX_, int NU_, int ORDER_>
+__global__ __launch_bounds__(64) void dmdc_refit_qr_kernel(RefitArgs a) {
+  using L = FitLayout<NX_, NU_, ORDER_>;
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const int lane = threadIdx.x;
+  for (long b = blockIdx.x; b < a.fit.B; b += gridDim.x) {
+    wave_sync();                                   // the previous member's reads are done
+    const FitPrior pr = fit_prior(a, b);
+    const bool finite = fit_qr_factor<NX_, NU_, ORDER_, true>(a.fit, b, lds, lane, pr);
+    bool converged = true;
+    if (uniform(finite)) converged = fit_qr_jacobi<L::NZ, L::PITCH>(lds + L::G, lds + L::V, lane);
+    fit_qr_models<NX_, NU_, ORDER_, true>(a.fit, b, lds, lane, finite, pr);
+    if (lane == 0) gst(a.fit.status, b, !finite ? 3 : converged ? 0 : 1);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Recursive DMDc updates of B members (m4q_online_dmdc_batch; online.py: online_dmdc_reference is the definition): the frame of
 // dmdc_fit_kernel, the model A and the inverse Gram matrix P in dynamic LDS from the first snapshot to the last (OnlineLayout,
 // m4q_online.h).  HERM_: the conjugated form.
@@ -2147,6 +2189,8 @@ template <bool FITS, int N_ = NX>
 struct FitLaunch {
   static int run(const FitArgs&, hipStream_t) { return UNBUILT; }
   static int run_qr(const FitArgs&, hipStream_t) { return UNBUILT; }
+  static int run_refit(const RefitArgs&, hipStream_t) { return UNBUILT; }
+  static int run_refit_qr(const RefitArgs&, hipStream_t) { return UNBUILT; }
 };
 template <int N_>
 struct FitLaunch<true, N_> {
@@ -2164,11 +2208,27 @@ struct FitLaunch<true, N_> {
     hipLaunchKernelGGL((dmdc_fit_qr_kernel<N_, NU, ORDER>), dim3(a.B < 4096 ? a.B : 4096), dim3(64), lds, s, a);
     return -(int)hipGetLastError();
   }
+  static int run_refit(const RefitArgs& a, hipStream_t s) {
+    constexpr size_t lds = FitLayout<N_, NU, ORDER>::BYTES;
+    int rc = prep_lds(dmdc_refit_kernel<N_, NU, ORDER>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((dmdc_refit_kernel<N_, NU, ORDER>), dim3(a.fit.B < 4096 ? a.fit.B : 4096), dim3(64), lds, s, a);
+    return -(int)hipGetLastError();
+  }
+  static int run_refit_qr(const RefitArgs& a, hipStream_t s) {
+    constexpr size_t lds = FitLayout<N_, NU, ORDER>::BYTES;
+    int rc = prep_lds(dmdc_refit_qr_kernel<N_, NU, ORDER>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((dmdc_refit_qr_kernel<N_, NU, ORDER>), dim3(a.fit.B < 4096 ? a.fit.B : 4096), dim3(64), lds, s, a);
+    return -(int)hipGetLastError();
+  }
 };
 constexpr bool FIT_FITS = FitLayout<NX, NU, ORDER>::FITS;
 constexpr int FIT_LDS = FIT_FITS ? (int)FitLayout<NX, NU, ORDER>::BYTES : 0;
 static int launch_fit(const FitArgs& a, hipStream_t s) { return FitLaunch<FIT_FITS>::run(a, s); }
 static int launch_fit_qr(const FitArgs& a, hipStream_t s) { return FitLaunch<FIT_FITS>::run_qr(a, s); }
+static int launch_refit(const RefitArgs& a, hipStream_t s) { return FitLaunch<FIT_FITS>::run_refit(a, s); }
+static int launch_refit_qr(const RefitArgs& a, hipStream_t s) { return FitLaunch<FIT_FITS>::run_refit_qr(a, s); }
 template <bool FITS, int N_ = NX>
 struct OnlineLaunch {
   static int run(const OnlineArgs&, int, hipStream_t) { return UNBUILT; }
@@ -2214,6 +2274,8 @@ static int launch_observed_plant(const ObsPlantArgs&, hipStream_t) { return UNBU
 constexpr int FIT_LDS = 0;
 static int launch_fit(const FitArgs&, hipStream_t) { return UNBUILT; }
 static int launch_fit_qr(const FitArgs&, hipStream_t) { return UNBUILT; }
+static int launch_refit(const RefitArgs&, hipStream_t) { return UNBUILT; }
+static int launch_refit_qr(const RefitArgs&, hipStream_t) { return UNBUILT; }
 constexpr int ONLINE_LDS = 0;
 static int launch_online(const OnlineArgs&, int, hipStream_t) { return UNBUILT; }
 static int launch_linearize(const LinArgs&, hipStream_t) { return UNBUILT; }
@@ -2353,7 +2415,7 @@ static const ShapeOps* shape_ops() {
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
                                ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr,
-                               launch_plant_feedback, launch_model_feedback};
+                               launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr};
   return &ops;
 }
 

@@ -24,14 +24,6 @@ struct OnlineLayout {
   static constexpr bool FITS = NZ <= 64 && BYTES <= FIT_LDS_LIMIT;
 };
 
-// acc -= a * b
-__device__ __forceinline__ void cmsub(cplx& acc, cplx a, cplx b) {
-  acc.re = fma(-a.re, b.re, acc.re);
-  acc.re = fma(a.im, b.im, acc.re);
-  acc.im = fma(-a.re, b.im, acc.im);
-  acc.im = fma(-a.im, b.re, acc.im);
-}
-
 __device__ __forceinline__ bool finite_c(cplx a) { return finite_d(a.re) && finite_d(a.im); }
 
 // A = A0[b], P = P0[b] (or alpha I) into LDS, lane l its column

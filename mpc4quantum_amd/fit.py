@@ -42,7 +42,20 @@ a host call.  status 3: R or T has a non-finite entry.  Data that are exactly ra
 cap: null columns are rotated until they underflow; the models at the cap are good.
 
 status per member: 0 ok; 1 the Jacobi iteration hit its cap (the models are written from the last iterate); 3 non-finite data
-(G or C has a non-finite entry, which any non-finite sample produces): the models are zero and the rank is 0."""
+(G or C has a non-finite entry, which any non-finite sample produces): the models are zero and the rank is 0.
+
+Prior model (A0, discount, counts; m4q_dmdc_refit_batch / m4q_dmdc_refit_qr_batch): one DiscrepDMDc.fit_iteration (model.py),
+A <- A0 + (Y - A0 Z) pinv(Z, rcond) on the discounted stacks = A0 (I - Pi_r) + Y Z_r^+: the fit where the data excited the plant,
+the prior everywhere else.  With any of the three given (A0 defaults to 0, discount to 1):
+  counts      member b takes t < counts[b] of every experiment, as online_dmdc_batch does; the others stream past.
+  discount    snapshot s of the S taken has weight discount^(S-1-s), as a recurrence: before a snapshot is accumulated
+              G <- d2 G, C <- d2 C and the sums behind svals likewise, with d2 = discount * discount formed once per member, each a
+              rounded product of its own; the QR route: R <- discount R, T <- discount T before the snapshot's rotations.
+  discrepancy Gram route, after G and C are accumulated: D[i][l] = C[i][l] - sum_k A0[i][k] G[k][l], k ascending, the terms
+              subtracted one at a time from C[i][l] (as online.update forms r); D takes C's place.  QR route, after the Givens
+              phase: T[j][i] <- T[j][i] - sum_{k >= j} R[j][k] conj(A0[i][k]), k ascending.  Spectrum, ranks, svals (those of the
+              weighted stack) and truncated products as above; A0 is added once per entry at the end.
+status 3 also when A0 has a non-finite entry.  counts[b] = 0: models = A0, rank 0, status 0."""
 import numpy as np
 
 from . import _lib
@@ -84,12 +97,15 @@ def stack_snapshots(xs, u, order):
     return z.reshape(E * (N1 - 1), -1).T, xs[:, 1:, :].reshape(E * (N1 - 1), n).T
 
 
-def gram(Z, Y):
-    """G = sum z z^H and C = sum y z^H over the columns in their order."""
+def gram(Z, Y, d2=None):
+    """G = sum z z^H and C = sum y z^H over the columns in their order; d2: G <- d2 G, C <- d2 C before every column."""
     nz, S = Z.shape
     G = np.zeros((nz, nz), dtype=np.complex128)
     C = np.zeros((Y.shape[0], nz), dtype=np.complex128)
     for s in range(S):
+        if d2 is not None:
+            G *= d2
+            C *= d2
         G += np.outer(Z[:, s], Z[:, s].conj())
         C += np.outer(Y[:, s], Z[:, s].conj())
     iu = np.triu_indices(nz, 1)
@@ -138,12 +154,15 @@ def jacobi_hermitian(G):
     return G.diagonal().real.copy(), V, MAX_SWEEPS, False
 
 
-def singular_values(V, Z):
+def singular_values(V, Z, d2=None):
     """s_k = sqrt(sum over the snapshots, in their order, of |v_k^H z|^2), descending: the Rayleigh quotients v_k^H G v_k taken
-    from the data themselves, every term non-negative (the inner products summed over the rows of V in ascending index)."""
+    from the data themselves, every term non-negative (the inner products summed over the rows of V in ascending index).
+    d2: the sums are scaled by it before every snapshot, as gram() scales G."""
     nz, S = Z.shape
     acc = np.zeros(nz)
     for s in range(S):
+        if d2 is not None:
+            acc = acc * d2
         d = np.zeros(nz, dtype=np.complex128)
         for j in range(nz):
             d += V[j, :].conj() * Z[j, s]
@@ -175,14 +194,18 @@ def truncated_models(lam, V, C, rconds):
 
 
 # ---------------------------------------------------------------- the QR route (m4q_dmdc_fit_qr_batch, csrc/m4q_fit_qr.h)
-def givens_qr(Z, Y):
+def givens_qr(Z, Y, discount=None):
     """Row-wise Givens QR of the stacked data, one snapshot at a time in their order: the snapshot contributes the row
     (z^H | y^H) (the conjugated columns of Z [nz, S] and Y [n, S]), rotated into R [nz, nz] (upper triangular, real diagonal)
-    and T [nz, n] by nz dependent rotations.  Afterwards Z^H = Q R and T = Q^H Y^H, and R has Z's singular values."""
+    and T [nz, n] by nz dependent rotations.  Afterwards Z^H = Q R and T = Q^H Y^H, and R has Z's singular values.
+    discount: R <- discount R, T <- discount T before every snapshot's rotations."""
     nz, S = Z.shape
     R = np.zeros((nz, nz), dtype=np.complex128)
     T = np.zeros((nz, Y.shape[0]), dtype=np.complex128)
     for s in range(S):
+        if discount is not None:
+            R *= discount
+            T *= discount
         row = Z[:, s].conj()
         rhs = Y[:, s].conj()
         for j in range(nz):
@@ -263,6 +286,62 @@ def qr_models(M, V, T, rconds):
     return A, rank, lam
 
 
+# ---------------------------------------------------------------- the prior model (m4q_dmdc_refit_batch, m4q_dmdc_refit_qr_batch)
+def taken_snapshots(Z, Y, E, steps):
+    """The columns (e, t) with t < steps of Z [nz, E N] and Y [n, E N], in their order."""
+    N = Z.shape[1] // E
+    keep = (np.arange(E * N) % N) < steps
+    return Z[:, keep], Y[:, keep]
+
+
+def gram_discrepancy(G, C, A0):
+    """D = C - A0 G, the cross-Gram matrix of the discrepancy Y - A0 Z: the terms k = 0, 1, ... subtracted one at a time from C."""
+    D = C.copy()
+    for k in range(G.shape[0]):
+        D -= np.outer(A0[:, k], G[k, :])
+    return D
+
+
+def qr_discrepancy(R, T, A0):
+    """T - R A0^H, the discrepancy's Q^H (Y - A0 Z)^H: T[j][i] - sum_{k >= j} R[j][k] conj(A0[i][k]), k ascending."""
+    T = T.copy()
+    for k in range(R.shape[0]):
+        T[:k + 1] -= np.outer(R[:k + 1, k], A0[:, k].conj())
+    return T
+
+
+def _check_prior(B, N, n, nz, A0, discount, counts):
+    """Shapes and values of the prior's arguments; None when none is given, else a dict: "A0" [B|1, n, nz] (zero by default),
+    "discount" [B|1] (1 by default), "counts" [B] int32 or None, and the per-member flags."""
+    if A0 is None and discount is None and counts is None:
+        return None
+    if A0 is None:
+        A0 = np.zeros((n, nz), dtype=np.complex128)
+    A0 = np.ascontiguousarray(A0, dtype=np.complex128)
+    if A0.shape not in ((n, nz), (B, n, nz)):
+        raise ValueError("A0 must be [n, nz] = (%d, %d) or [B, n, nz] with B = %d, got %s" % (n, nz, B, A0.shape))
+    discount = np.asarray(1.0 if discount is None else discount, dtype=np.float64)
+    if discount.shape not in ((), (B,)):
+        raise ValueError("discount must be a scalar or [B] = (%d,), got shape %s" % (B, discount.shape))
+    if not np.all((discount > 0.0) & (discount <= 1.0)):
+        raise ValueError("discount must lie in (0, 1], got %s" % (discount,))
+    if counts is not None:
+        c = np.asarray(counts)
+        if c.shape != (B,) or not np.issubdtype(c.dtype, np.integer):
+            raise ValueError("counts must be [B] = (%d,) integers, got shape %s of %s" % (B, c.shape, c.dtype))
+        if np.any((c < 0) | (c > N)):
+            raise ValueError("counts must lie in [0, N = %d], got %s" % (N, c))
+        counts = np.ascontiguousarray(c, dtype=np.int32)
+    return {"A0": A0.reshape((-1, n, nz)), "A0_per": int(A0.ndim == 3 and B > 1), "discount": np.ascontiguousarray(discount.reshape(-1)),
+            "discount_per": int(discount.ndim == 1 and B > 1), "counts": counts}
+
+
+def _member_prior(prior, b, N):
+    """(A0 [n, nz], discount, steps) of member b."""
+    return (prior["A0"][b if prior["A0_per"] else 0], float(prior["discount"][b if prior["discount_per"] else 0]),
+            N if prior["counts"] is None else int(prior["counts"][b]))
+
+
 def _method(method):
     if method not in METHODS:
         raise ValueError("method must be one of %s, got %r" % (METHODS, method))
@@ -316,11 +395,12 @@ def _result(models, rank, svals, status, scalar):
     return {"models": models[0] if scalar else models, "rank": rank[0] if scalar else rank, "svals": svals, "status": status}
 
 
-def dmdc_fit_reference(xs, us, order, rcond, u_scale=None):
+def dmdc_fit_reference(xs, us, order, rcond, u_scale=None, A0=None, discount=None, counts=None):
     """The definition above in NumPy, member by member.  Arguments and result as dmdc_fit_batch, plus "sweeps" [B]."""
     xs, us, u_per, u_scale, rconds, scalar, order = _check(xs, us, order, rcond, u_scale)
     B, E, N1, n = xs.shape
     nz = n * size_of_library(order, us.shape[3])
+    prior = _check_prior(B, N1 - 1, n, nz, A0, discount, counts)
     R = rconds.shape[0]
     models = np.zeros((R, B, n, nz), dtype=np.complex128)
     rank = np.zeros((R, B), dtype=np.int32)
@@ -331,27 +411,37 @@ def dmdc_fit_reference(xs, us, order, rcond, u_scale=None):
         u = us[b if u_per else 0]
         if u_scale is not None:
             u = u_scale[b] * u
+        a0, d2 = None, None
         with np.errstate(all="ignore"):
             Z, Y = stack_snapshots(xs[b], u, order)
-            G, C = gram(Z, Y)
-        if not (np.all(np.isfinite(G)) and np.all(np.isfinite(C))):
+            if prior is not None:
+                a0, d, steps = _member_prior(prior, b, N1 - 1)
+                d2 = d * d
+                Z, Y = taken_snapshots(Z, Y, E, steps)
+            G, C = gram(Z, Y, d2)
+        if not (np.all(np.isfinite(G)) and np.all(np.isfinite(C)) and (a0 is None or np.all(np.isfinite(a0)))):
             status[b] = 3
             continue
+        if a0 is not None:
+            C = gram_discrepancy(G, C, a0)
         lam, V, sweeps[b], converged = jacobi_hermitian(G)
         status[b] = 0 if converged else 1
         models[:, b], rank[:, b] = truncated_models(lam, V, C, rconds)
-        svals[b] = singular_values(V, Z)
+        if a0 is not None:
+            models[:, b] += a0
+        svals[b] = singular_values(V, Z, d2)
     out = _result(models, rank, svals, status, scalar)
     out["sweeps"] = sweeps
     return out
 
 
-def dmdc_fit_qr_reference(xs, us, order, rcond, u_scale=None):
-    """The QR route's definition in NumPy, member by member (the module docstring's last part).  Arguments and result as
+def dmdc_fit_qr_reference(xs, us, order, rcond, u_scale=None, A0=None, discount=None, counts=None):
+    """The QR route's definition in NumPy, member by member (the module docstring's QR part).  Arguments and result as
     dmdc_fit_batch(method="qr"), plus "sweeps" [B]."""
     xs, us, u_per, u_scale, rconds, scalar, order = _check(xs, us, order, rcond, u_scale, "qr")
     B, E, N1, n = xs.shape
     nz = n * size_of_library(order, us.shape[3])
+    prior = _check_prior(B, N1 - 1, n, nz, A0, discount, counts)
     R = rconds.shape[0]
     models = np.zeros((R, B, n, nz), dtype=np.complex128)
     rank = np.zeros((R, B), dtype=np.int32)
@@ -362,22 +452,30 @@ def dmdc_fit_qr_reference(xs, us, order, rcond, u_scale=None):
         u = us[b if u_per else 0]
         if u_scale is not None:
             u = u_scale[b] * u
+        a0, d = None, None
         with np.errstate(all="ignore"):
             Z, Y = stack_snapshots(xs[b], u, order)
-            Rf, T = givens_qr(Z, Y)
-        if not (np.all(np.isfinite(Rf)) and np.all(np.isfinite(T))):
+            if prior is not None:
+                a0, d, steps = _member_prior(prior, b, N1 - 1)
+                Z, Y = taken_snapshots(Z, Y, E, steps)
+            Rf, T = givens_qr(Z, Y, d)
+        if not (np.all(np.isfinite(Rf)) and np.all(np.isfinite(T)) and (a0 is None or np.all(np.isfinite(a0)))):
             status[b] = 3
             continue
+        if a0 is not None:
+            T = qr_discrepancy(Rf, T, a0)
         M, V, sweeps[b], converged = jacobi_one_sided(Rf)
         status[b] = 0 if converged else 1
         models[:, b], rank[:, b], lam = qr_models(M, V, T, rconds)
+        if a0 is not None:
+            models[:, b] += a0
         svals[b] = np.sqrt(np.sort(lam)[::-1])
     out = _result(models, rank, svals, status, scalar)
     out["sweeps"] = sweeps
     return out
 
 
-def dmdc_fit_batch(xs, us, order, rcond, u_scale=None, method="gram"):
+def dmdc_fit_batch(xs, us, order, rcond, u_scale=None, method="gram", A0=None, discount=None, counts=None):
     """Fit B DMDc models on the device in one launch.
 
     xs [B, N + 1, n] or [B, E, N + 1, n] complex: E experiments of N steps per member; us [N, m] / [E, N, m] (shared by the
@@ -386,11 +484,16 @@ def dmdc_fit_batch(xs, us, order, rcond, u_scale=None, method="gram"):
     entry point takes, "rank" [R, B] ([B]), "svals" [B, nz] (the singular values of the stacked data, descending) and "status" [B]
     (0 ok, 1 the eigen-iteration hit its cap, 3 non-finite data: zero models, rank 0).
     method "gram" (m4q_dmdc_fit_batch): from the Gram matrix of the data, error O(eps kappa^2), rcond in [1e-7, 1);
-    method "qr" (m4q_dmdc_fit_qr_batch): from a QR of the data themselves, error O(eps kappa), rcond in [1e-12, 1)."""
+    method "qr" (m4q_dmdc_fit_qr_batch): from a QR of the data themselves, error O(eps kappa), rcond in [1e-12, 1).
+    A0 [n, nz] or [B, n, nz], discount (a scalar or [B], in (0, 1]), counts [B] integers in [0, N]: the fit against a prior model
+    (the module docstring's last part; m4q_dmdc_refit_batch / m4q_dmdc_refit_qr_batch): "models" are A0 + the truncated fit of
+    Y - A0 Z on the snapshots t < counts[b], weighted discount^(age); "svals" and "rank" those of the weighted stack; status 3
+    also for a non-finite A0.  With all three None the call is today's."""
     xs, us, u_per, u_scale, rconds, scalar, order = _check(xs, us, order, rcond, u_scale, _method(method))
     B, E, N1, n = xs.shape
     m = us.shape[3]
     nz = n * size_of_library(order, m)
+    prior = _check_prior(B, N1 - 1, n, nz, A0, discount, counts)
     R = rconds.shape[0]
     models = np.empty((R, B, n, nz), dtype=np.complex128)
     rank = np.empty((R, B), dtype=np.int32)
@@ -398,10 +501,16 @@ def dmdc_fit_batch(xs, us, order, rcond, u_scale=None, method="gram"):
     status = np.empty(B, dtype=np.int32)
     dp, ip = _lib._dp, _lib._ip
     L = _lib.lib()
-    entry = L.m4q_dmdc_fit_qr_batch if method == "qr" else L.m4q_dmdc_fit_batch
-    _lib.check(entry(B, n, m, order, E, N1 - 1, xs.ctypes.data_as(dp), us.ctypes.data_as(dp), u_per,
-                     None if u_scale is None else u_scale.ctypes.data_as(dp), rconds.ctypes.data_as(dp), R,
-                     models.ctypes.data_as(dp), rank.ctypes.data_as(ip), svals.ctypes.data_as(dp), status.ctypes.data_as(ip)))
+    args = (B, n, m, order, E, N1 - 1, xs.ctypes.data_as(dp), us.ctypes.data_as(dp), u_per,
+            None if u_scale is None else u_scale.ctypes.data_as(dp), rconds.ctypes.data_as(dp), R,
+            models.ctypes.data_as(dp), rank.ctypes.data_as(ip), svals.ctypes.data_as(dp), status.ctypes.data_as(ip))
+    if prior is None:
+        entry = L.m4q_dmdc_fit_qr_batch if method == "qr" else L.m4q_dmdc_fit_batch
+    else:
+        entry = L.m4q_dmdc_refit_qr_batch if method == "qr" else L.m4q_dmdc_refit_batch
+        args += (prior["A0"].ctypes.data_as(dp), prior["A0_per"], prior["discount"].ctypes.data_as(dp), prior["discount_per"],
+                 None if prior["counts"] is None else prior["counts"].ctypes.data_as(ip))
+    _lib.check(entry(*args))
     return _result(models, rank, svals, status, scalar)
 
 
@@ -421,16 +530,45 @@ def prediction_losses(xs, models, us, order, u_scale=None):
     return losses
 
 
-def train_models_batch(xs, us, order, rconds=np.logspace(-6, -1, 10), u_scale=None, method="gram"):
+def train_models_batch(xs, us, order, rconds=np.logspace(-6, -1, 10), u_scale=None, method="gram", A0=None):
     """The reference's hyper-parameter search (its tests/util_training.train_model) for an ensemble: one fit call covers all
     rconds, every candidate is rolled along the training controls, and each member keeps the model that loses least (the first
     of equals, as the reference's `loss < smallest_loss`).  Returns a dict: "models" [B, n, nz], "rcond" [B], "index" [B] (into
-    rconds), "losses" [R, B], "status" [B].  method: dmdc_fit_batch's."""
+    rconds), "losses" [R, B], "status" [B].  method: dmdc_fit_batch's.  A0 [n, nz] or [B, n, nz]: every fit of the grid is made
+    against this prior model (dmdc_fit_batch's A0); the selection is the same."""
     xs4, us4, _, u_scale, rconds, _, order = _check(xs, us, order, np.atleast_1d(rconds), u_scale, _method(method))
-    fit = dmdc_fit_batch(xs4, us4, order, rconds, u_scale, method)
+    fit = dmdc_fit_batch(xs4, us4, order, rconds, u_scale, method, A0=A0)
     losses = prediction_losses(xs4, fit["models"], us4, order, u_scale)
     finite = np.where(np.isfinite(losses), losses, np.inf)
     index = np.argmin(finite, axis=0)
     members = np.arange(xs4.shape[0])
     return {"models": np.ascontiguousarray(fit["models"][index, members]), "rcond": rconds[index], "index": index,
             "losses": losses, "status": fit["status"]}
+
+
+def refit_models_batch(run, models, order, clock, rcond, discount=1.0, method="gram", layout="auto", reference=False):
+    """ONE update of every member's model from its own closed-loop run: what DiscrepDMDc.from_bootstrap(A0) holds after the run's
+    snapshots and one fit_iteration, A0 + (Y - A0 Z) pinv(Z, rcond) on the discounted stacks, in one call of dmdc_fit_batch with
+    counts = steps_done and A0 = models.
+
+    run: the result dict of mpc_batch (xs [B, n, n_steps + 1], us [B, m, n_steps]) or of a session's results() (time axis second),
+    read as stream_models_batch reads it; models [n, nz] or [B, n, nz]: what the loops were handed; clock: the run's StepClock;
+    rcond, discount, method as dmdc_fit_batch.  reference=True evaluates the NumPy definition instead.  Returns dmdc_fit_batch's
+    dict.  ValueError for clock.measure_freq > 1: the unmeasured states of such a run are the model's own predictions, not data.
+    The reference's matrix_rank gate (no update while the states seen span fewer than dim_x directions) is not applied: at a
+    truncating rcond the update is then A0 + the fit of the discrepancy on the directions seen."""
+    if int(getattr(clock, "measure_freq", 1)) > 1:
+        raise ValueError("refit_models_batch needs measure_freq == 1: with measure_freq = %d the unmeasured states of the run are "
+                         "predictions of the model, not data" % clock.measure_freq)
+    models = np.asarray(models, dtype=np.complex128)
+    if models.ndim not in (2, 3):
+        raise ValueError("models must be [n, nz] or [B, n, nz], got shape %s" % (models.shape,))
+    from .online import _run_arrays
+    xs, us = _run_arrays(run, models.shape[-2], layout)
+    counts = np.asarray(run["steps_done"])
+    if models.ndim == 3 and models.shape[0] == 1 and xs.shape[0] != 1:
+        models = models[0]
+    if reference:
+        fn = dmdc_fit_qr_reference if _method(method) == "qr" else dmdc_fit_reference
+        return fn(xs, us, order, rcond, A0=models, discount=discount, counts=counts)
+    return dmdc_fit_batch(xs, us, order, rcond, method=method, A0=models, discount=discount, counts=counts)

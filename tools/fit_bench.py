@@ -2,6 +2,7 @@
 """The batched DMDc fit on the device against the host loop it replaces.
 
     python tools/fit_bench.py [--method gram|qr] [--members 65536] [--host-members 1024] [--repeats 3] [--once]
+    python tools/fit_bench.py --prior [--members 65536] [--repeats 5] [--cutoffs 10]
 
 Config 3's plant (the three-level transmon under two drives), `members` of them with per-member detuning (op0 scaled) and drive
 calibration (u_scale), E = 3 training experiments of N = 40 held-control steps from random full-rank states, one smooth pulse set
@@ -14,7 +15,12 @@ at 65,536 members) per repeat, the host loop `DiscrepDMDc.from_data` over the sa
 members and scaled to the ensemble, and the largest difference between the two on those members at the cut-offs where their ranks
 agree.  No threshold is set: nothing upstream fits an ensemble.
 --once runs the device fit exactly once and times nothing: the run to put under `rocprofv3 --kernel-trace --stats`, a run of its
-own, whose kernel statistics give dmdc_fit_kernel's (dmdc_fit_qr_kernel's) time without the copies."""
+own, whose kernel statistics give dmdc_fit_kernel's (dmdc_fit_qr_kernel's) time without the copies.
+--prior times the fit against a prior model (m4q_dmdc_refit_batch / m4q_dmdc_refit_qr_batch: A0 = the nominal model of the ensemble
+from m4q_discretize_batch, discount 0.98, full counts) against the plain fit of the same build on the same inputs, both routes: after
+one warm-up call of each of the four entry points the calls alternate plain, prior, plain, ... `repeats` times; the medians of the
+wall times and their ratio are printed per route.  --cutoffs K fits the first K points of the grid: with one, the 2.5 GB of models
+that ten cut-offs copy back no longer hide the kernels."""
 import argparse
 import os
 import sys
@@ -58,6 +64,33 @@ def host_fit(xs, us, u_scale):
     return out
 
 
+def prior_bench(B, repeats, cutoffs):
+    xs, us, u_scale = training_data(B)
+    p = configs.build(3, batch=1, host_models=False, drift_scale=0.125)
+    A0 = m4q.discretize_homogeneous_batch(list(p["generators"]), p["dt"], 1)[0]
+    rconds = RCONDS[:cutoffs]
+    for method in fit.METHODS:
+        calls = {"plain": lambda: m4q.dmdc_fit_batch(xs, us, 1, rconds, u_scale=u_scale, method=method),
+                 "prior": lambda: m4q.dmdc_fit_batch(xs, us, 1, rconds, u_scale=u_scale, method=method, A0=A0, discount=0.98)}
+        warm = {k: f() for k, f in calls.items()}
+        print("fit_bench --prior method=%s B=%d n=9 m=2 E=%d N=%d R=%d: status counts plain %s prior %s, max |A_prior - A_plain| %.3g"
+              % (method, B, E, N, len(rconds), np.bincount(warm["plain"]["status"], minlength=4).tolist(),
+                 np.bincount(warm["prior"]["status"], minlength=4).tolist(), np.abs(warm["prior"]["models"] - warm["plain"]["models"]).max()),
+              flush=True)
+        del warm
+        times = {k: [] for k in calls}
+        for r in range(repeats):
+            for k, f in calls.items():
+                t0 = time.perf_counter()
+                f()
+                times[k].append(time.perf_counter() - t0)
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        for k in calls:
+            print("fit_bench --prior method=%s %s call wall ms: %s  median %.2f" %
+                  (method, k, " ".join("%.2f" % (1e3 * t) for t in times[k]), 1e3 * med[k]), flush=True)
+        print("fit_bench --prior method=%s median prior / median plain = %.3f" % (method, med["prior"] / med["plain"]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--method", choices=fit.METHODS, default="gram")
@@ -65,7 +98,11 @@ def main():
     ap.add_argument("--host-members", type=int, default=1024)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--prior", action="store_true")
+    ap.add_argument("--cutoffs", type=int, default=len(RCONDS))
     a = ap.parse_args()
+    if a.prior:
+        return prior_bench(a.members, max(a.repeats, 5), max(1, min(a.cutoffs, len(RCONDS))))
     B, Bh = a.members, min(a.host_members, a.members)
     xs, us, u_scale = training_data(B)
     out = m4q.dmdc_fit_batch(xs, us, 1, RCONDS, u_scale=u_scale, method=a.method)   # warm-up (and, with --once, the only run)
