@@ -145,6 +145,25 @@ M4Q_API int m4q_linearize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t
                         int32_t model_per_instance, const double* X, const double* U, double* A_ls, double* B_ls,
                         double* Delta_ls);
 
+/* The PLANT's own discrete-time Jacobians along B trajectories, in one launch: where m4q_linearize_batch linearises a model (a
+ * truncated discretisation, or a fit), this linearises the held-control step x+ = f(x, u) of the two unitary device plants
+ * exactly, from U = expm(-i dts[t] (H0 + sum_k v_k H_k)) and its Frechet derivatives dU_k (one exponential of the (1 + m) d block
+ * matrix, as the rollout gradients).  plant_linearize.py: plant_linearize_reference is the definition.
+ * Member b at point t: state X[b][t], controls u = U[b|.][t], the member sees v_k = u_scale[b][k] u_k.
+ *   A = (U (x) U^*) (x) I_cols (cols = 1: HAMILTONIAN, n = d^2; cols = d^2: PROCESS, n = d^4) - it does not depend on the state;
+ *   B[:, k] = u_scale[b][k] vec(dU_k R U^H + U R dU_k^H), R = mat(x): the derivative with respect to the UNSCALED control u_k;
+ *   Delta = -B u (summed with k ascending), so that A x + B u + Delta = f(x, u) to rounding (f(x, u) = A x holds exactly).
+ * dts [T] r, X [B][T][n] c, U [B|1][T][m] r (u_per_instance), u_scale [B][m] r or NULL, op0 and ops as m4q_plant_rollout_batch
+ * -> A_ls [B][T][n][n] c, B_ls [B][T][n][m] c, Delta_ls [B][T][n] c, the layouts of m4q_linearize_batch: they go into
+ * m4q_quad_program_batch unchanged.  Each output may be NULL (A is 16 n^2 bytes per point and not always wanted), not all three.
+ * M4Q_E_BADARG: B or T < 1 (or B T beyond 2^31 - 1); dts, X, U, op0 or ops missing; all outputs NULL; a plant_kind that is no device plant; M4Q_PLANT_PROCESS
+ * on a dim_x that is no fourth power.  M4Q_E_UNSUPPORTED: no compiled shape; dim_x not a square; M4Q_PLANT_GENERATOR (no kernel:
+ * linearise its discretised model, m4q_discretize_batch then m4q_linearize_batch).  All checked before a device is asked for. */
+M4Q_API int m4q_plant_linearize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
+                              const double* X, const double* U, int32_t u_per_instance, const double* u_scale,
+                              const double* op0, const double* ops, int32_t plant_per_instance,
+                              double* A_ls, double* B_ls, double* Delta_ls);
+
 /* replaces quad_program (optimize.py:12-60 statement; lqr.py:14-79 arithmetic) for B problems.
  * x_init [B][n] c, X_bm [B|1][T+1][n] c, U_bm [B|1][T][m] r, Q_ls [T+1][n][n] c, R_ls [T][m][m] c,
  * A_ls [B][T][n][n] c, B_ls [B][T][n][m] c, Delta_ls [B][T][n] c (NULL = zero),

@@ -156,6 +156,20 @@ struct GradReduceArgs {
   M4Q_P(double) out_last; long last_stride;        // element nm of chunk c -> out_last[c last_stride]
 };
 
+// The plant's own linearisation along trajectories (m4q_plant_linearize_batch; m4q_plant_lin.h, plant_linearize.py is the
+// definition): the work unit is a (member, point) pair, B T of them.  Member b at point t: state X[b][t], controls U[b|.][t] as the
+// caller passed them (the member sees u_scale[b][k] u_k; u_scale may be null), step length dts[t].  Each output may be null.
+struct PlantLinArgs {
+  int B, T, kind;
+  M4Q_P(const double) dts;                         // [T]
+  M4Q_P(const cplx) X;                             // [B][T][n]
+  M4Q_P(const double) U; long u_stride;            // [B|1][T][m] (u_stride T m or 0)
+  M4Q_P(const double) u_scale;                     // [B][m] or null
+  M4Q_P(const cplx) op0; long op0_stride;          // plant operators, as PlantArgs
+  M4Q_P(const cplx) ops; long ops_stride;
+  M4Q_P(cplx) A_ls; M4Q_P(cplx) B_ls; M4Q_P(cplx) D_ls;      // [B][T][n][n], [B][T][n][m], [B][T][n], as LinArgs
+};
+
 // A stored feedback law closing the loop of a rollout (m4q_plant_feedback_batch, m4q_model_feedback_batch; m4q_feedback.h,
 // feedback.py is the definition).  `roll` is the rollout without its control sequence (roll.u is u_ref, roll.u_stride its
 // stride): at step t the member commands u_t = clip(Re(K_t [x_t - x_ref[t] ; 1]) + u_ref[t]) and sees u_scale[b][k] u_t[k].
@@ -286,6 +300,7 @@ struct ShapeOps {
   int (*launch_model_feedback)(const FeedbackArgs&, hipStream_t);  // (the shapes of launch_model_rollout)
   int (*launch_refit)(const RefitArgs&, hipStream_t);              // dmdc_refit_kernel, dmdc_refit_qr_kernel: the shapes and the
   int (*launch_refit_qr)(const RefitArgs&, hipStream_t);           // LDS of launch_fit
+  int (*launch_plant_linearize)(const PlantLinArgs&, hipStream_t); // (the shapes of launch_plant_grad; no generator plant)
 };
 
 }  // namespace m4q

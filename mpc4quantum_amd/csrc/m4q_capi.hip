@@ -1435,6 +1435,41 @@ int m4q_plant_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
   return st.finish(sh->launch_plant_grad(a, nullptr), "plant rollout gradient");
 }
 
+int m4q_plant_linearize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
+                              const double* X, const double* U, int32_t u_per_instance, const double* u_scale,
+                              const double* op0, const double* ops, int32_t plant_per_instance,
+                              double* A_ls, double* B_ls, double* Delta_ls) {
+  const char* who = "m4q_plant_linearize_batch";
+  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d", dim_x, dim_u);
+  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  if (B < 1 || T < 1) return fail(M4Q_E_BADARG, "%s: B and T must be at least 1 (got %d, %d)", who, B, T);
+  if ((int64_t)B * T > INT32_MAX) return fail(M4Q_E_BADARG, "%s: B T = %lld points do not fit one launch", who, (long long)B * T);
+  if (!dts || !X || !U || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, X, U, op0 and ops are required", who);
+  if (!A_ls && !B_ls && !Delta_ls) return fail(M4Q_E_BADARG, "%s: nothing to return (A_ls, B_ls and Delta_ls are all NULL)", who);
+  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_linearize_batch: plant_kind %d is not a device plant")) return rc;
+  if (plant_kind == M4Q_PLANT_GENERATOR)
+    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no linearisation kernel (its block matrix has (1 + m) n > 16 columns): "
+                "linearise its discretised model with m4q_discretize_batch and m4q_linearize_batch", who);
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x), BT = (size_t)B * T;
+  const Extent eu(B, u_per_instance, (size_t)T * m), e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  Stage st;
+  m4q::PlantLinArgs a{};
+  a.B = B; a.T = T; a.kind = plant_kind;
+  a.dts = st.in<double>(dts, T);
+  a.X = st.in<cplx>(X, BT * n);
+  a.U = st.in<double>(U, eu.count); a.u_stride = eu.stride;
+  if (u_scale) a.u_scale = st.in<double>(u_scale, (size_t)B * m);
+  a.op0 = st.in<cplx>(op0, e0.count); a.op0_stride = e0.stride;
+  a.ops = st.in<cplx>(ops, ek.count); a.ops_stride = ek.stride;
+  if (A_ls) a.A_ls = st.out<cplx>(A_ls, BT * n * n);
+  if (B_ls) a.B_ls = st.out<cplx>(B_ls, BT * n * m);
+  if (Delta_ls) a.D_ls = st.out<cplx>(Delta_ls, BT * n);
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_plant_linearize(a, nullptr), "plant linearize");
+}
+
 int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* u,
                                  int32_t u_per_instance, const double* u_scale, const double* models, int32_t model_per_instance,
                                  const double* W, const double* target, int32_t target_per_instance, int32_t q_mode,

@@ -11,6 +11,7 @@
 #include "m4q_fit_qr.h"
 #include "m4q_online.h"
 #include "m4q_grad.h"
+#include "m4q_plant_lin.h"
 #include "m4q_noise.h"
 #include "m4q_observe.h"
 #include "m4q_tile3.h"
@@ -1943,6 +1944,65 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NX == 9 ? 1 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The plant's own discrete-time Jacobians along trajectories (m4q_plant_linearize_batch; plant_linearize.py:
+// plant_linearize_reference is the definition), Hamiltonian and process plants.  The work unit is a (member, point) pair: row g of
+// quad `quad` works on unit 4 quad + g = b T + t, whatever member that falls in; a row past the last unit repeats it and stores
+// nothing.  A is written 16 consecutive entries of its row-major [n][n] block at a time, one per lane.
+template <int PLANT>
+constexpr int plant_lin_lds_elems() {
+  constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;
+  return plant_lin_scratch_elems<NX, NU, D>();
+}
+// (d = 3: one wave per SIMD, as plant_rollout_grad_kernel - the same expm_cols<9> of the block matrix)
+template <int PLANT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NX == 9 ? 1 : WAVES, 8))) void plant_linearize_kernel(PlantLinArgs a) {
+  static_assert(PLANT == PLANT_HAMILTONIAN || PLANT == PLANT_PROCESS, "the generator plant has no linearisation kernel");
+  constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;
+  constexpr int NC = PLANT == PLANT_PROCESS ? D * D : 1;
+  constexpr int NN = NX * NX;
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const LaneGeo L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* scratch = lds + g * plant_lin_lds_elems<PLANT>();
+  const int units = a.B * a.T;                       // (the host keeps B T inside an int)
+  const int nquads = quads_of(units);
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const QuadRow r(quad, g, units);                 // r.b: this row's unit
+    const int b0 = (int)(r.q0 / a.T);                // the quad's first member (wave-uniform)
+    const int b = (int)(r.b / a.T), t = (int)(r.b - (long)b * a.T);
+    const unsigned bl = (unsigned)(b - b0);
+    const GView op0 = gview(a.op0, b0 * a.op0_stride, bl * (unsigned)a.op0_stride);
+    const GView ops = gview(a.ops, b0 * a.ops_stride, bl * (unsigned)a.ops_stride);
+    double u[NU], sc[NU];
+#pragma unroll
+    for (int k = 0; k < NU; ++k) {
+      u[k] = gld(a.U, b * a.u_stride + (long)t * NU + k);
+      sc[k] = a.u_scale ? gld(a.u_scale, (long)b * NU + k) : 1.0;
+    }
+    const cplx x = gld(a.X, r.b * NX + j);
+    cplx Bj[NU], dlt;
+    plant_lin_point<NX, NU, D, NC>(x, u, sc, op0, ops, gld(a.dts, t), scratch, j, jj, Bj, dlt);
+    const bool st = r.valid && L.lane_ok;
+    if (a.B_ls != nullptr && st) {
+#pragma unroll
+      for (int k = 0; k < NU; ++k) gst(a.B_ls, (r.b * NX + j) * NU + k, Bj[k]);
+    }
+    if (a.D_ls != nullptr && st) gst(a.D_ls, r.b * NX + j, dlt);
+    if (a.A_ls != nullptr) {
+#pragma unroll
+      for (int e0 = 0; e0 < NN; e0 += 16) {
+        const int e = e0 + jj;
+        const int ec = e < NN ? e : NN - 1;
+        const int i = ec / NX;
+        const cplx val = plant_lin_entry<D, NC>(scratch, i, ec - i * NX);
+        if (r.valid && e < NN) gst(a.A_ls, r.b * NN + e, val);
+      }
+    }
+    wave_sync();                                   // the row's reads of its LDS block are done
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // The measurement noise of B members at one column of xs (noise.py: MeasurementNoise.sample), one component per lane, by the
 // device function the closed loop calls: a run's noise realisation without the run.
 __global__ __launch_bounds__(64) void noise_sample_kernel(NoiseArgs a) {
@@ -2370,6 +2430,27 @@ static int launch_plant_grad(const GradArgs& a, hipStream_t s) {
     return UNBUILT;
   }
 }
+// a linearisation kernel over quads of (member, point) pairs
+template <class K>
+static int launch_plant_lin(K kern, const PlantLinArgs& a, size_t lds, hipStream_t s) {
+  int rc = prep_lds(kern, lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid_for(a.B * a.T)), dim3(64), lds, s, a);
+  return -(int)hipGetLastError();
+}
+static int launch_plant_linearize(const PlantLinArgs& a, hipStream_t s) {
+  if constexpr (!SQUARE) {
+    return UNBUILT;
+  } else {
+    if (a.kind == PLANT_HAMILTONIAN)
+      return launch_plant_lin(plant_linearize_kernel<PLANT_HAMILTONIAN>, a, sizeof(cplx) * (size_t)(ROWS * plant_lin_lds_elems<PLANT_HAMILTONIAN>()), s);
+    if constexpr (QUARTIC) {
+      if (a.kind == PLANT_PROCESS)
+        return launch_plant_lin(plant_linearize_kernel<PLANT_PROCESS>, a, sizeof(cplx) * (size_t)(ROWS * plant_lin_lds_elems<PLANT_PROCESS>()), s);
+    }
+    return UNBUILT;
+  }
+}
 #ifndef M4Q_NO_AUX
 static int launch_model_grad(const GradArgs& a, hipStream_t s) { return launch_grad(model_rollout_grad_kernel, a, MODEL_LDS, s); }
 #else
@@ -2382,6 +2463,7 @@ static int launch_plant_rollout(const RollArgs&, hipStream_t) { return UNBUILT; 
 static int launch_plant_feedback(const FeedbackArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
+static int launch_plant_linearize(const PlantLinArgs&, hipStream_t) { return UNBUILT; }
 #endif
 
 #if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
@@ -2415,7 +2497,7 @@ static const ShapeOps* shape_ops() {
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
                                ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr,
-                               launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr};
+                               launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr, launch_plant_linearize};
   return &ops;
 }
 

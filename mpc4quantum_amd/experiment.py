@@ -102,6 +102,13 @@ def _gradient_batch(exp, x0s, ts, us, W, target, op0, u_scale, figure, weights, 
                                     figure=figure, weights=weights, reduce=reduce, scale_grad=scale_grad)
 
 
+def _linearize_batch(exp, X, U, ts_or_dt, u_scale, outputs, op0):
+    """linearize_batch of the two unitary device plants: the plant's own operators() unless per-member op0 [B, k, k] is given."""
+    from .plant_linearize import plant_linearize_batch
+    own0, ops = exp.operators()
+    return plant_linearize_batch(X, U, own0 if op0 is None else op0, ops, ts_or_dt, exp.plant_kind, u_scale=u_scale, outputs=outputs)
+
+
 class QExperiment(Experiment):
     """Closed-system plant: H0 and H1_list are d x d Hermitian (ndarray or qutip.Qobj)."""
 
@@ -208,6 +215,14 @@ class QExperiment(Experiment):
         discretised model (model_rollout_grad_batch)."""
         return _gradient_batch(self, x0s, ts, us, W, target, op0, u_scale, figure, weights, reduce, scale_grad)
 
+    def linearize_batch(self, X, U, ts_or_dt, u_scale=None, outputs=("A", "B", "Delta"), op0=None):
+        """The exact Jacobians of this plant's held-control step along trajectories, for an ensemble in one launch
+        (plant_linearize_batch): X [B, T, n] the points (ensemble axis first, then time), U [T, m] or [B, T, m] the controls held
+        from each, ts_or_dt a scalar dt or a time grid of T + 1 points, u_scale and op0 as simulate_batch.  Returns (A, B, Delta),
+        None for an output not asked for.  With collapse operators the plant is a generator plant, which is refused: linearise the
+        discretised model (WrapModel.linearize_batch)."""
+        return _linearize_batch(self, X, U, ts_or_dt, u_scale, outputs, op0)
+
 
 class LExperiment(QExperiment):
     """Open-system plant: x' = (L0 + sum_k u_k L_k) x with n x n generators on vec_r(rho)."""
@@ -221,6 +236,11 @@ class LExperiment(QExperiment):
         """Refused: the generator plant has no gradient kernel."""
         raise ValueError("LExperiment.gradient_batch: the generator plant has no control gradient on the device - discretise the "
                          "generators (discretize_homogeneous) and take the gradient of the model with model_rollout_grad_batch")
+
+    def linearize_batch(self, *args, **kwargs):
+        """Refused: the generator plant has no linearisation kernel."""
+        raise ValueError("LExperiment.linearize_batch: the generator plant has no linearisation of its own on the device - discretise "
+                         "the generators (discretize_homogeneous) and linearise the model with WrapModel.linearize_batch")
 
     def f(self, t, x, u):
         L = self.H0 + sum(h * uk for h, uk in zip(self.H1_list, np.reshape(u, -1)))
@@ -351,6 +371,11 @@ class QSynthesis(Experiment):
         """The figure of simulate_batch's rollout and its gradient with respect to the held controls, for an ensemble in one launch
         (plant_rollout_grad_batch on the process plant): arguments and the returned dict as QExperiment.gradient_batch."""
         return _gradient_batch(self, x0s, ts, us, W, target, op0, u_scale, figure, weights, reduce, scale_grad)
+
+    def linearize_batch(self, X, U, ts_or_dt, u_scale=None, outputs=("A", "B", "Delta"), op0=None):
+        """The exact Jacobians of the process plant's held-control step along trajectories, for an ensemble in one launch
+        (plant_linearize_batch): arguments and the returned tuple as QExperiment.linearize_batch, X [B, T, d^4] process vectors."""
+        return _linearize_batch(self, X, U, ts_or_dt, u_scale, outputs, op0)
 
 
 def split_blocks(bmatrix, nrows, ncols):

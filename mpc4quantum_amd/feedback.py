@@ -163,6 +163,62 @@ class FeedbackLaw:
                                             None if (u_prev is None or du is None) else law.u_prev[None], sat, du, exact=exact)
         return cls.from_quad_program(gains[0], X_targ, U_targ, sat, du, u_prev)
 
+    @classmethod
+    def along_plant_trajectory(cls, op0, ops, dt_or_ts, X_nom, U_nom, X_targ, U_targ, Q_ls, R_ls, sat, du=None, u_prev=None,
+                               kind=_lib.PLANT_HAMILTONIAN, u_scale=None, exact=False):
+        """The plant-side twin of along_trajectory: TVLQR around nominal trajectories with the PLANT's own Jacobians - one
+        plant_linearize_batch (the exact linearisation of the step the law will run on), one quad_program_batch, the gains wrapped.
+
+        op0, ops, dt_or_ts, kind, u_scale as plant_linearize_batch.  One nominal, X_nom [N + 1, n] (or [N, n]) and U_nom [N, m],
+        gives one law, as along_trajectory; per-member nominals X_nom [B, N + 1, n] (or [B, N, n]), U_nom [B, N, m] - for instance
+        the xs, us of a finished mpc_batch run - give a per-member law, with per-member operators, u_scale [B, m] and u_prev [B, m]
+        where given.  X_targ [N + 1, n] and U_targ [N, m], shared or with a leading B; Q_ls, R_ls, sat, du, exact as
+        along_trajectory.  The Jacobians pass through the host between the two launches."""
+        from .optimize import quad_program_batch
+        from .plant_linearize import plant_linearize_batch
+        X_nom = np.asarray(X_nom, dtype=np.complex128)
+        U_nom = np.asarray(U_nom)
+        if np.iscomplexobj(U_nom):
+            raise TypeError("U_nom must be real")
+        U_nom = np.ascontiguousarray(U_nom, dtype=np.float64)
+        per = X_nom.ndim == 3
+        if X_nom.ndim not in (2, 3) or U_nom.ndim != X_nom.ndim or min(X_nom.shape) < 1 or min(U_nom.shape) < 1 \
+                or X_nom.shape[-2] not in (U_nom.shape[-2], U_nom.shape[-2] + 1) or (per and X_nom.shape[0] != U_nom.shape[0]):
+            raise ValueError("X_nom must be [N + 1, n] (or [N, n]) and U_nom [N, m], both with or both without a leading B, got %s "
+                             "and %s" % (X_nom.shape, U_nom.shape))
+        if not per:
+            X_nom, U_nom = X_nom[None], U_nom[None]
+        B, N, m = U_nom.shape
+        n = X_nom.shape[2]
+        X_targ = np.asarray(X_targ, dtype=np.complex128)
+        U_targ = np.asarray(U_targ)
+        if np.iscomplexobj(U_targ):
+            raise TypeError("U_targ must be real")
+        U_targ = np.asarray(U_targ, dtype=np.float64)
+        lead = (B,) if per else ()
+        if X_targ.shape not in ((N + 1, n), lead + (N + 1, n)) or U_targ.shape not in ((N, m), lead + (N, m)):
+            raise ValueError("X_targ must be [N + 1, n] = (%d, %d) and U_targ [N, m] = (%d, %d), shared or with the nominal's leading "
+                             "B, got %s and %s" % (N + 1, n, N, m, X_targ.shape, U_targ.shape))
+        if X_targ.ndim == 3 or U_targ.ndim == 3:      # (the QP takes both per member or both shared)
+            X_targ, U_targ = np.broadcast_to(X_targ, (B, N + 1, n)), np.broadcast_to(U_targ, (B, N, m))
+        Q_ls, R_ls = np.asarray(Q_ls, dtype=np.complex128), np.asarray(R_ls, dtype=np.complex128)
+        if Q_ls.shape == (n, n):
+            Q_ls = np.broadcast_to(Q_ls, (N + 1, n, n))
+        if R_ls.shape == (m, m):
+            R_ls = np.broadcast_to(R_ls, (N, m, m))
+        if Q_ls.shape != (N + 1, n, n) or R_ls.shape != (N, m, m):
+            raise ValueError("Q_ls must be [N + 1, n, n] or [n, n] and R_ls [N, m, m] or [m, m], got %s and %s" % (Q_ls.shape, R_ls.shape))
+        law = cls(np.zeros(lead + (N, n + 1, m)), np.broadcast_to(X_targ, lead + (N + 1, n)), np.broadcast_to(U_targ, lead + (N, m)),
+                  sat, du, u_prev)                    # (the law's own checks, before the library)
+        if law.prev_members is not None and not (per and law.prev_members == B):
+            raise ValueError("u_prev must be [m]%s, got %s" % (" or [B, m] with B = %d" % B if per else " (one nominal: one QP)",
+                                                               law.u_prev.shape))
+        A_ls, B_ls, D_ls = plant_linearize_batch(X_nom[:, :N], U_nom, op0, ops, dt_or_ts, kind, u_scale)
+        band = u_prev is not None and du is not None
+        _, _, _, gains = quad_program_batch(X_nom[:, 0], X_targ.reshape(-1, N + 1, n), U_targ.reshape(-1, N, m), Q_ls, R_ls, A_ls, B_ls, D_ls,
+                                            np.broadcast_to(law.u_prev, (B, m)) if band else None, sat, du, exact=exact)
+        return cls.from_quad_program(gains if per else gains[0], X_targ, U_targ, sat, du, u_prev)
+
 
 # ---------------------------------------------------------------- the definitions
 def _plant_step(kind, x, v, op0, ops, dt):
