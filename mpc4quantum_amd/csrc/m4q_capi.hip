@@ -957,13 +957,17 @@ int m4q_session_qp_stats(m4q_session* s, int64_t* out6) {
     fprintf(stderr, "m4q: exact QP: %llu row sweeps in %llu wavefront passes (x4 rows = %llu): lane efficiency %.2f\n", q[2], q[7],
             4 * q[7], q[7] ? (double)q[2] / (4.0 * (double)q[7]) : 0.0);
   if (std::getenv("M4Q_PHASE_TRACE")) {          // -DM4Q_DEV_PHASE_CLOCK builds: wavefront time per phase of the main loop, 100 MHz ticks
-    static const char* names[16] = {"draw/resume", "backward | exact: adjoint pass", "forward", "handover", "line search", "step done (plant, shift)", "publish",
-                                    "passes", "guess update", "passes with a line search", "exact: pinned sweep", "exact: policy rollout",
-                                    "exact: ratio rollout", "exact: blend", "exact: open rollout", "exact: bookkeeping + copies"};
+    static const char* names[16] = {"draw/resume", "backward | exact: adjoint pass", "forward", "handover", "line search", "step done (plant)", "publish",
+                                    "passes", "guess update", "passes with a line search",
+                                    // (a name "a | b": a in a clipped kernel, b in an exact one.  Slots 10, 11 and 13 are parts of "step done"
+                                    //  in a clipped kernel - slot 5 is then the rest of it, the passes in which no row ends a step)
+                                    "step: bookkeeping, us | exact: pinned sweep", "step: plant to xs | exact: policy rollout",
+                                    "exact: ratio rollout", "step: exit, rest | exact: blend", "exact: open rollout",
+                                    "exact: bookkeeping + copies"};
     unsigned long long tot = 0;
     for (int i = 0; i < 16; ++i) tot += (i == 7 || i == 9) ? 0 : q[8 + i];
     for (int i = 0; i < 16; ++i)
-      fprintf(stderr, "m4q phase %-30s %14llu %s  %5.1f %%\n", names[i], q[8 + i], (i == 7 || i == 9) ? "     " : "ticks",
+      fprintf(stderr, "m4q phase %-44s %14llu %s  %5.1f %%\n", names[i], q[8 + i], (i == 7 || i == 9) ? "     " : "ticks",
               (i != 7 && i != 9 && tot) ? 100.0 * (double)q[8 + i] / (double)tot : 0.0);
   }
   return check_watchdog(s);

@@ -287,6 +287,15 @@ constexpr PrioMap prio_map() {
   if (TILE && !EXACT && NX == 9 && PLANT == PLANT_HAMILTONIAN) return PrioMap{0, 1, 1, 1, 1, 1};
   return PrioMap{0, 0, 0, 0, 0, 0};
 }
+// Which kernels store a finished SQP step's guess one node down in the guess update itself (see `shift_now` in mpc_kernel) instead
+// of shifting it in a second pass of the step-done block.  The clipped kernels: config 3 -1.9 %, config 5's share -2.0 %, configs 2
+// and 4 inside their spread.  The exact kernels keep the two passes: they carry 150-250 spilled registers, the shifted stores add
+// 3-9 more at n = 8, 9, and --exact-qp (config 3) did not come out faster - 185.97 / 185.48 / 184.90 ms against the parent's
+// 180.44 / 185.89 / 183.18 in one alternated call, +1.2 % in the mean inside a 3 % spread (profiles/r08_ab_experiments.txt).
+template <bool EXACT>
+constexpr bool shift_in_update() {
+  return !EXACT;
+}
 // Development builds (-DM4Q_DEV_PHASE_CLOCK): PhaseClock (m4q_device.h) sums the 100 MHz clock over the phases of the main loop; every
 // wavefront adds its sums to queue[8..23] (u64) on exit; M4Q_PHASE_TRACE=1 makes m4q_session_qp_stats print them.
 #if defined(M4Q_DEV_PHASE_CLOCK)
@@ -296,6 +305,7 @@ constexpr PrioMap prio_map() {
 #endif
 #define M4Q_PHASE_DECL PhaseClock pc;
 #define M4Q_PHASE_MARK(i) pc.mark(i);
+#define M4Q_PHASE_MARK_CLIP(i) if constexpr (!EXACT) pc.mark(i);      // (slots 10, 11, 13: the exact solve's own in an exact kernel)
 template <class S, int PLANT, bool EXACT, bool TL = false, bool TILE = false, bool SG = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_SG : TILE ? WAVES_TILE : WAVES, 8))) void mpc_kernel(MpcArgs) {
   static_assert(!TL || (sizeof(S) == sizeof(double) && SQUARE), "the traceless path is a real path of a d x d density matrix");
@@ -408,6 +418,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
   // (the levels change at the phase boundaries of the main loop only, outside every lane-dependent branch: s_setprio ignores EXEC)
   constexpr PrioMap PRIO = prio_map<S, PLANT, EXACT, TL, TILE, SG>();
   constexpr bool PRIO_ON = PRIO.any();
+  constexpr bool SHIFT_IN_UPDATE = shift_in_update<EXACT>();
   static_assert(!EXACT || !PRIO_ON, "the exact solve's phases are those of box_qp_iterate: no levels there yet");
   GView Xg, Ug, Xo, Uo, gains, Xalt, Ualt, pin_stat;
   {
@@ -903,6 +914,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
     issue_prio<PRIO_ON && PRIO.update != PRIO.line_search, PRIO.update>();
     M4Q_PHASE_MARK(4)
     const bool upd = solved && !fail && use_ls;       // warm steps wrote the shifted guess in the rollout
+    // a row whose SQP step ends with this update (the step-done block below tests the same): its next step starts from
+    // shift_guess of the updated guess (mpc.py:71-73,271-272: drop node 0, repeat the last), which is the updated guess stored one
+    // node lower - the update stores it there, and no second pass reads and writes the guess again.
+    bool shift_now = false;
+    if constexpr (SHIFT_IN_UPDATE) {
+      KArgs* a = kargs();
+      shift_now = upd && (fin || iter >= a->max_iter);
+    }
+    // Element e of the updated array goes to e - (node width) where e is past node 0, and the last node also to e; rows that go
+    // on iterating store at e.  In place this is safe, and what it rests on is this.  Across trips of the loops below: a trip
+    // stores at or below the addresses it loaded, never into what a later trip loads.  Within a trip, across lanes: the store
+    // of group u to e - n hits an address that ANOTHER lane of the row loads in group u or u - 1 of the same trip (n <= the 16
+    // or 32 elements a group spans).  Every load of the trip is issued before its first store (the sched_barrier; the compiler
+    // may not sink a load of the same buffer below a store), vector loads return in order, and group u's store waits for
+    // group u's own data - so groups <= u have been read by all lanes when it is issued.  An edit that stores before the
+    // barrier, shifts by more than one group, or gives the lanes of a row different trips breaks this.
+    const int xsh = shift_now ? NS : 0, ush = shift_now ? NU : 0;
     // X_guess += alpha (X_opt - X_guess) (mpc.py:228-229)
     // (these small per-element passes are latency bound: unrolled so that several loads are in flight)
     // (the row's 16 lanes share the (T + 1) NS contiguous elements, and a batch of U elements per lane issues all its loads
@@ -927,7 +955,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
               double r[2];
 #pragma unroll
               for (int h = 0; h < 2; ++h) r[h] = cadd(xg[u][h], cscale(csub(xo[u][h], xg[u][h]), alpha));
-              stn<2>(Xg, e0 + 32 * u, r);
+              const int e = e0 + 32 * u;               // (NS even: a pair lies within one node)
+              if (e >= xsh) stn<2>(Xg, e - xsh, r);
+              if (shift_now && e >= T * NS) stn<2>(Xg, e, r);
             }
           }
         }
@@ -945,8 +975,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int u = 0; u < U; ++u)
-          if (e0 + 16 * u < count) Xg.st<S>(e0 + 16 * u, cadd(xg[u], cscale(csub(xo[u], xg[u]), alpha)));
+        for (int u = 0; u < U; ++u) {
+          if (e0 + 16 * u < count) {
+            const S r = cadd(xg[u], cscale(csub(xo[u], xg[u]), alpha));
+            const int e = e0 + 16 * u;
+            if (e >= xsh) Xg.st<S>(e - xsh, r);
+            if (shift_now && e >= T * NS) Xg.st<S>(e, r);
+          }
+        }
       }
     }
     if constexpr (NU % 2 == 0) {
@@ -968,7 +1004,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
               double r[2];
 #pragma unroll
               for (int h = 0; h < 2; ++h) r[h] = ug[u][h] + alpha * (uo[u][h] - ug[u][h]);
-              stn<2>(Ug, e0 + 32 * u, r);
+              const int e = e0 + 32 * u;
+              if (e >= ush) stn<2>(Ug, e - ush, r);
+              if (shift_now && e >= (T - 1) * NU) stn<2>(Ug, e, r);
             }
           }
         }
@@ -987,8 +1025,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
           }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int u = 0; u < V; ++u)
-            if (e0 + 16 * u < cu) Ug.st<double>(e0 + 16 * u, ug[u] + alpha * (uo[u] - ug[u]));
+          for (int u = 0; u < V; ++u) {
+            if (e0 + 16 * u < cu) {
+              const double r = ug[u] + alpha * (uo[u] - ug[u]);
+              const int e = e0 + 16 * u;
+              if (e >= ush) Ug.st<double>(e - ush, r);
+              if (shift_now && e >= (T - 1) * NU) Ug.st<double>(e, r);
+            }
+          }
         }
       }
     }
@@ -996,7 +1040,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
     issue_prio<PRIO_ON && PRIO.step_done != PRIO.update, PRIO.step_done>();
 
     M4Q_PHASE_MARK(8)
-    // ---- rows that finished their MPC step: apply, propagate, shift ----
+    // ---- rows that finished their MPC step: apply, propagate, shift (where the guess update has not) ----
     bool step_done;
     {
       KArgs* a = kargs();
@@ -1018,6 +1062,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
           for (int k = 0; k < NU; ++k) gst(a->us, b * sUs + (long)step * NU + k, uapp[k]);
         }
       }
+      M4Q_PHASE_MARK_CLIP(10)
       if constexpr (PLANT != PLANT_NONE) {
         // (step+1) % measure_freq == 0: propagate the plant from the last measured state over the last measure_freq
         // intervals (mpc.py:252-260); the held controls are stacked newest first against an increasing time grid
@@ -1067,26 +1112,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
         if (ok && measure) { x_meas = rn; if constexpr (TL) tau = tnew; }
         if (ok && lane_io) gst(a->xs, b * sXs + (long)(step + 1) * NX + jio, xn);
       }
-      // shift_guess (mpc.py:71-73,271-272): drop column 0, repeat the last
-      const bool shift_now = ok && use_ls;          // (a warm step's rollout has already shifted)
-      if (shift_now && lane_ok) {
-        for (int t0 = 0; t0 < T; t0 += 8) {
-          S buf[8];
+      M4Q_PHASE_MARK_CLIP(11)
+      // shift_guess (mpc.py:71-73,271-272): drop column 0, repeat the last.  SHIFT_IN_UPDATE: the guess update above stored this
+      // row's guess one node down already (a warm step's rollout did); else a second pass, here
+      if constexpr (!SHIFT_IN_UPDATE) {
+        const bool shift_late = ok && use_ls;
+        if (shift_late && lane_ok) {
+          for (int t0 = 0; t0 < T; t0 += 8) {
+            S buf[8];
 #pragma unroll
-          for (int q = 0; q < 8; ++q) buf[q] = Xg.ld<S>((t0 + q + 1 <= T ? t0 + q + 1 : T) * NS + j);
+            for (int q = 0; q < 8; ++q) buf[q] = Xg.ld<S>((t0 + q + 1 <= T ? t0 + q + 1 : T) * NS + j);
 #pragma unroll
-          for (int q = 0; q < 8; ++q)
-            if (t0 + q < T) Xg.st<S>((t0 + q) * NS + j, buf[q]);
+            for (int q = 0; q < 8; ++q)
+              if (t0 + q < T) Xg.st<S>((t0 + q) * NS + j, buf[q]);
+          }
         }
-      }
-      if (shift_now && jj < NU) {
-        for (int t0 = 0; t0 + 1 < T; t0 += 8) {
-          double buf[8];
+        if (shift_late && jj < NU) {
+          for (int t0 = 0; t0 + 1 < T; t0 += 8) {
+            double buf[8];
 #pragma unroll
-          for (int q = 0; q < 8; ++q) buf[q] = Ug.ld<double>((t0 + q + 1 < T ? t0 + q + 1 : T - 1) * NU + jj);
+            for (int q = 0; q < 8; ++q) buf[q] = Ug.ld<double>((t0 + q + 1 < T ? t0 + q + 1 : T - 1) * NU + jj);
 #pragma unroll
-          for (int q = 0; q < 8; ++q)
-            if (t0 + q + 1 < T) Ug.st<double>((t0 + q) * NU + jj, buf[q]);
+            for (int q = 0; q < 8; ++q)
+              if (t0 + q + 1 < T) Ug.st<double>((t0 + q) * NU + jj, buf[q]);
+          }
         }
       }
       if (ok) done_steps = step + 1;
@@ -1128,6 +1177,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
         const S rn = Basis<S, TL>::template to_state<NX, DD>(xc, scratch, j, jj, tnew);
         if (carry) { x_cur = rn; if constexpr (TL) tau = tnew; }
       }
+      M4Q_PHASE_MARK_CLIP(13)
     }
 
     issue_prio<PRIO_ON && PRIO.publish != PRIO.step_done, PRIO.publish>();
