@@ -39,9 +39,11 @@ class PlantCase:
             p = configs.build(4, batch=1)
             op0, ops, self.dt, self.sat = p["plant_op0"][0], p["plant_ops"][0][:int(name[-1])], p["dt"], p["sat"]
         else:
-            assert name == "16-1-process"
+            assert name in ("16-1-process", "16-2-process", "16-3-process")
             p = configs.synthesis(1)
             op0, ops, self.dt, self.sat = 0.15 * SZ, p["plant_ops"][0], p["dt"], p["sat"]
+            if name != "16-1-process":                            # two or three drives, as kernel_variants.process_scenario(nu=3)
+                ops = np.stack([0.5 * SX, 0.5 * SY, 0.5 * SZ])[:int(name[3])]
             self.kind, self.step = _lib.PLANT_PROCESS, _process_step
         self.op0, self.ops = np.array(op0, dtype=complex), np.array(ops, dtype=complex)
         self.d, self.m = self.op0.shape[0], self.ops.shape[0]

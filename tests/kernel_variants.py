@@ -6,8 +6,10 @@ below, and which objects go into libm4q_hip_gen.so follows build.py.  tests/test
 both files to the text these mirrors were written against, so a new shape or a changed rule changes the matrix or fails there.
 
 closed_loop_cells() is what tests/test_gpu_variant_matrix.py runs one teacher-forced case of each; entry_point_cells() lists the
-single-kernel entry points (linearize, quad_program, discretize, plant_step) per shape.  scenario() gives seeded, well-conditioned
-host inputs for every closed-loop shape in the configs.build dict layout.  pieces() mirrors how one launch cuts a member's run into
+single-kernel entry points (linearize, quad_program, discretize, plant_step) per shape; aux_cells() lists every instance of the
+auxiliary kernel families (rollouts, gradients, feedback laws, plant linearisation, the four fits, the online update) from mirrors
+of M4Q_NO_AUX, FitLayout / OnlineLayout and the plant dispatch: what tests/test_gpu_aux_matrix.py runs one case of each.
+scenario() gives seeded, well-conditioned host inputs for every closed-loop shape in the configs.build dict layout.  pieces() mirrors how one launch cuts a member's run into
 work items (tests/test_gpu_launch_schedule.py); _planned() / _check_planned() plan exits on a member's own stored states and check
 them (tests/test_gpu_exit_condition.py, tests/test_gpu_launch_schedule.py)."""
 import importlib.util
@@ -155,6 +157,98 @@ def entry_point_cells():
     cells += [EntryCell("discretize", nx, nu, o, "-") for nx, nu, o, po in sh if not po and o <= 2]
     pm = sorted({(nx, nu) for nx, nu, o, po in sh if square(nx)})
     cells += [EntryCell("plant", nx, nu, 0, kind) for (nx, nu), kind in itertools.product(pm, (HAMILTONIAN, GENERATOR))]
+    return cells
+
+
+# ---------------------------------------------------------------- the auxiliary families
+# (rollouts, gradients, stored feedback laws, plant linearisation, the four DMDc fits, the online update)
+REFUSED = "refused"                      # the kind of a cell whose entry point refuses the shape or plant before any launch
+PLAIN, HERMITIAN_FORM = "plain", "hermitian-form"                     # online_dmdc_kernel<.., HERM>: HERM = false, true
+MODEL_FAMILIES = ("model_rollout", "model_grad", "model_feedback")
+FIT_FAMILIES = ("fit", "fit_qr", "refit", "refit_qr")
+PLANT_FAMILIES = ("plant_rollout", "plant_feedback", "plant_grad", "plant_linearize")
+FIT_LDS_LIMIT = 160 * 1024
+AUX_GRID = 4096                          # every auxiliary launch caps its grid here and loops
+ROWS = 4                                 # members per wavefront of a quad kernel (m4q_mpc.h)
+QUAD_WRAP = AUX_GRID * ROWS              # grid_for: a quad kernel takes its second trip from this member on
+
+
+def n_lifted(nu, order):
+    """PowTab<NU, ORDER>::NP: the monomials of degree 1 .. order in nu controls, C(nu + order, order) - 1."""
+    from math import comb
+    return comb(nu + order, order) - 1
+
+
+def lifted_size(nx, nu, order):
+    """static constexpr int NZ = NX * (1 + PowTab<NU, ORDER>::NP);"""
+    return nx * (1 + n_lifted(nu, order))
+
+
+def fit_lds_bytes(nx, nu, order):
+    """FitLayout: G = 0, V = G + NZ * PITCH, C = V + NZ * PITCH, Z = C + NX * PITCH, XN = Z + NZ, LAM = XN + NX;
+    ELEMS = LAM + (NZ + 1) / 2; BYTES = sizeof(cplx) * ELEMS."""
+    nz = lifted_size(nx, nu, order)
+    pitch = nz | 1
+    lam = 2 * nz * pitch + nx * pitch + nz + nx
+    return 16 * (lam + (nz + 1) // 2)
+
+
+def online_lds_bytes(nx, nu, order):
+    """OnlineLayout: P = 0, A = P + NZ * PITCH, Z = A + NX * PITCH, XN = Z + NZ, PZ = XN + NX, W = PZ + NZ, R = W + NZ, GR = R + NX;
+    ELEMS = GR + NX; BYTES = sizeof(cplx) * ELEMS."""
+    nz = lifted_size(nx, nu, order)
+    pitch = nz | 1
+    gr = nz * pitch + nx * pitch + nz + nx + nz + nz + nx
+    return 16 * (gr + nx)
+
+
+def fit_fits(nx, nu, order):
+    """static constexpr bool FITS = NZ <= 64 && BYTES <= FIT_LDS_LIMIT;  (FitLayout)"""
+    return lifted_size(nx, nu, order) <= 64 and fit_lds_bytes(nx, nu, order) <= FIT_LDS_LIMIT
+
+
+def online_fits(nx, nu, order):
+    """static constexpr bool FITS = NZ <= 64 && BYTES <= FIT_LDS_LIMIT;  (OnlineLayout)"""
+    return lifted_size(nx, nu, order) <= 64 and online_lds_bytes(nx, nu, order) <= FIT_LDS_LIMIT
+
+
+def plant_kinds(nx):
+    """launch_by_plant / launch_plant_feedback: nothing where !SQUARE; the Hamiltonian plant, the process plant where QUARTIC, and
+    the generator plant otherwise.  (These kernels live in the shape's own object - the plant-only one included -, not in the gen
+    object, which holds closed-loop kernels alone: M4Q_NO_AUX.)"""
+    if not square(nx):
+        return []
+    return [HAMILTONIAN, GENERATOR] + ([PROCESS] if quartic(nx) else [])
+
+
+AuxCell = namedtuple("AuxCell", "family nx nu order kind")
+
+
+def aux_cell_id(c):
+    return "%s-%d-%d-%d-%s" % c
+
+
+def aux_cells():
+    """Every auxiliary kernel instance the library holds, and every (shape, plant) an auxiliary entry point refuses by rule: the
+    list of record of what tests/test_gpu_aux_matrix.py runs.  Model-side families per (nx, nu, order) object built without
+    M4Q_NO_AUX; fit and online families where their layout FITS, a REFUSED cell where it does not; plant families per (nx, nu) -
+    find_shape_any_order picks one object for all orders, plant-only shapes included - and plant kind, order 0, with the generator
+    plant REFUSED by the gradient and linearisation entry points."""
+    sh = shapes()
+    cells = []
+    for nx, nu, order, plant_only in sh:
+        if plant_only:                                          # M4Q_PLANT_ONLY defines M4Q_NO_AUX: the plant families alone
+            continue
+        cells += [AuxCell(f, nx, nu, order, "-") for f in MODEL_FAMILIES]
+        cells += [AuxCell(f, nx, nu, order, "-" if fit_fits(nx, nu, order) else REFUSED) for f in FIT_FAMILIES]
+        if online_fits(nx, nu, order):
+            cells += [AuxCell("online", nx, nu, order, form) for form in (PLAIN, HERMITIAN_FORM)]
+        else:
+            cells.append(AuxCell("online", nx, nu, order, REFUSED))
+    for nx, nu in sorted({(nx, nu) for nx, nu, o, po in sh if square(nx)}):
+        for kind in plant_kinds(nx):
+            cells += [AuxCell(f, nx, nu, 0, kind) for f in ("plant_rollout", "plant_feedback")]
+            cells += [AuxCell(f, nx, nu, 0, REFUSED if kind == GENERATOR else kind) for f in ("plant_grad", "plant_linearize")]
     return cells
 
 

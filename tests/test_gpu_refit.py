@@ -17,14 +17,13 @@ import mpc4quantum_amd as m4q
 from mpc4quantum_amd import fit
 from tests.test_fit_host import model_bounds as gram_bounds
 from tests.test_fit_qr_host import model_bounds as qr_bounds
-from tests.test_refit_host import CASES, FIELDS, closed_form, load_case, prior_args, weighted_stacks
+from tests.aux_matrix_cases import FIT_B as B, FIT_N as N, synthetic   # (synthetic() lives with the cases of the auxiliary matrix)
+from tests.test_refit_host import CASES, FIELDS, load_case, prior_args
 
 pytestmark = pytest.mark.gpu
 
 ROUTES = {"gram": (fit.dmdc_fit_reference, gram_bounds), "qr": (fit.dmdc_fit_qr_reference, qr_bounds)}
 SHAPES = [(4, 1, 1), (4, 1, 2), (9, 2, 1), (16, 1, 2), (16, 3, 1)]
-GRID = np.logspace(-6, -1, 101)
-B, E, N = 5, 2, 24
 
 
 def device(c, route, **kw):
@@ -42,45 +41,6 @@ def same(a, b, members_a=slice(None), members_b=slice(None)):
         ax = {"models": 1, "rank": 1, "svals": 0, "status": 0}[f]
         x, y = np.moveaxis(a[f], ax, 0)[members_a], np.moveaxis(b[f], ax, 0)[members_b]
         assert np.array_equal(x, y), f
-
-
-def synthetic(n, m, order):
-    """A case in load_case's form: B bilinear members a few per cent apart under shared weak random controls; the prior of member
-    b is the true model of member b + 1.  svals, rank and sens come from NumPy's SVD of the weighted stacks, A from its pinv, and
-    the cut-offs are those of 101 points over the training grid's range [1e-6, 1e-1] that are a factor 1.2 clear of every singular
-    value of every member: the lowest, the middle one and the highest (the lowest rank)."""
-    rng = np.random.default_rng(1000 * n + 10 * m + order)
-    P = m4q.size_of_library(order, m) - 1
-    nz = n * (1 + P)
-    A = rng.standard_normal((n, n)) + 1j * rng.standard_normal((n, n))
-    common = np.concatenate([A * (0.9 / np.abs(np.linalg.eigvals(A)).max()),
-                             0.3 * (rng.standard_normal((n, n * P)) + 1j * rng.standard_normal((n, n * P))) / np.sqrt(n)], axis=1)
-    models = common[None] + 0.03 * (rng.standard_normal((B, n, nz)) + 1j * rng.standard_normal((B, n, nz))) / np.sqrt(n)
-    us = (1e-3 if nz == 64 else 1e-2) * rng.uniform(-1, 1, (E, N, m))   # weak: a gap opens between the state and the control block
-    xs = np.zeros((B, E, N + 1, n), dtype=complex)
-    xs[:, :, 0] = rng.standard_normal((B, E, n)) + 1j * rng.standard_normal((B, E, n))
-    pu = fit.lift_controls(us, order)
-    for t in range(N):
-        z = np.concatenate([xs[:, :, t, None, :], pu[None, :, t, :, None] * xs[:, :, t, None, :]], axis=2).reshape(B, E, nz)
-        xs[:, :, t + 1] = np.einsum("bij,bej->bei", models, z)
-    c = dict(xs=xs, us=us, order=order, u_scale=None, A0=np.ascontiguousarray(np.roll(models, -1, axis=0)), discount=0.95,
-             counts=np.array([N, N - 5, N, N - 1, N - 9], dtype=np.int32))
-    stacks = [weighted_stacks(c, b) for b in range(B)]
-    svals = np.stack([np.concatenate([np.linalg.svd(Z * w, compute_uv=False), np.zeros(max(0, nz - Z.shape[1]))]) for Z, _, w in stacks])
-    ok = [rc for rc in GRID if np.all((svals >= 1.2 * rc * svals[:, :1]) | (svals <= rc * svals[:, :1] / 1.2))]
-    assert ok, "no cut-off of the grid is clear of every singular value"
-    rank = np.stack([(svals > rc * svals[:, :1]).sum(axis=1) for rc in ok])
-    pick = sorted({0, len(ok) // 2, len(ok) - 1})
-    c.update(rconds=np.array(ok)[pick], rank=rank[pick].astype(np.int32), svals=svals)
-    assert (c["rank"] < nz).any(), "no admissible cut-off truncates"
-    c["A"] = np.zeros((len(pick), B, n, nz), dtype=complex)
-    c["A"] = closed_form(c)
-    sens = np.zeros(c["rank"].shape)
-    for _ in range(3):                                                         # the rule of tests/test_fit_qr_host.py: three draws
-        jit = dict(c, xs=xs * (1 + 1e-15 * rng.standard_normal(xs.shape)), us=us * (1 + 1e-15 * rng.standard_normal(us.shape)))
-        sens = np.maximum(sens, np.abs(closed_form(jit) - c["A"]).max(axis=(2, 3)))
-    c["sens"] = sens
-    return c
 
 
 @pytest.fixture(scope="module")

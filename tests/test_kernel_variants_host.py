@@ -1,5 +1,5 @@
-"""CPU checks of tests/kernel_variants.py (the matrix tests/test_gpu_variant_matrix.py runs) and of the input shapes
-EnsembleSession.build_models and mpc_batch_sharded accept.
+"""CPU checks of tests/kernel_variants.py (the matrices tests/test_gpu_variant_matrix.py and tests/test_gpu_aux_matrix.py run) and of the
+input shapes EnsembleSession.build_models and mpc_batch_sharded accept.
 
 The rule lines of m4q_kernels.hip and build.py must read exactly as the Python mirrors assume: a new shape changes the matrix,
 a changed rule fails here - neither can leave a compiled variant untested without notice."""
@@ -139,6 +139,153 @@ def test_spot_check_of_the_cells():
     assert qp == {(4, 1), (4, 2), (9, 2), (16, 3), (16, 1), (8, 2)}
     assert {(c.nx, c.nu, c.order) for c in entry if c.kind == "discretize"} == {
         (4, 1, 1), (4, 1, 2), (4, 2, 1), (9, 2, 1), (9, 2, 2), (16, 3, 1), (16, 1, 1), (16, 1, 2), (8, 2, 1)}
+
+
+# ---------------------------------------------------------------- the auxiliary families
+def test_aux_rule_lines_read_as_mirrored():
+    """What kernel_variants.aux_cells() mirrors, by exact text: which objects hold the auxiliary kernels at all, the two layouts
+    that decide where the fit and online kernels are built, the plant dispatch, the refusals and the grid cap."""
+    k, b, capi = _src("m4q_kernels.hip"), _src("build.py"), _src("m4q_capi.hip")
+    fit_h, online_h = _src("m4q_fit.h"), _src("m4q_online.h")
+    # plant-only shapes and the gen object hold no auxiliary kernel but the plant families
+    assert k.count("#if defined(M4Q_PLANT_ONLY) || defined(M4Q_VARIANT_GEN)\n#define M4Q_NO_AUX 1\n") == 1
+    assert b.count('(["-DM4Q_PLANT_ONLY"] if plant_only else [])') == 1
+    assert b.count('return [(int(a), int(b), int(c), "plant-only" in rest)') == 1
+    assert k.count("#ifndef M4Q_NO_AUX\nstatic int launch_model_grad(const GradArgs& a, hipStream_t s) { return launch_grad("
+                   "model_rollout_grad_kernel, a, MODEL_LDS, s); }\n") == 1
+    for line in ("static int launch_model_rollout(const RollArgs& a, hipStream_t s) { return launch_aux(model_rollout_kernel, a, MODEL_LDS, s); }",
+                 "static int launch_model_feedback(const FeedbackArgs& a, hipStream_t s) { return launch_feedback(model_feedback_kernel, a, "
+                 "MODEL_LDS, s); }"):
+        assert k.count(line) == 1, line
+    # FitLayout / OnlineLayout
+    assert fit_h.count("constexpr size_t FIT_LDS_LIMIT = 160 * 1024;") == 1
+    for text, line, n in ((fit_h, "  static constexpr int NZ = NX * (1 + PowTab<NU, ORDER>::NP);", 1),
+                          (fit_h, "  static constexpr int PITCH = NZ | 1;", 1),
+                          (fit_h, "  static constexpr int G = 0, V = G + NZ * PITCH, C = V + NZ * PITCH, Z = C + NX * PITCH, XN = Z + NZ, "
+                                  "LAM = XN + NX;", 1),
+                          (fit_h, "  static constexpr int ELEMS = LAM + (NZ + 1) / 2;", 1),
+                          (fit_h, "  static constexpr size_t BYTES = sizeof(cplx) * (size_t)ELEMS;", 1),
+                          (fit_h, "  static constexpr bool FITS = NZ <= 64 && BYTES <= FIT_LDS_LIMIT;", 1),
+                          (online_h, "  static constexpr int NZ = NX * (1 + PowTab<NU, ORDER>::NP);", 1),
+                          (online_h, "  static constexpr int PITCH = NZ | 1;", 1),
+                          (online_h, "  static constexpr int P = 0, A = P + NZ * PITCH, Z = A + NX * PITCH, XN = Z + NZ, PZ = XN + NX, "
+                                     "W = PZ + NZ, R = W + NZ, GR = R + NX;", 1),
+                          (online_h, "  static constexpr int ELEMS = GR + NX;", 1),
+                          (online_h, "  static constexpr size_t BYTES = sizeof(cplx) * (size_t)ELEMS;", 1),
+                          (online_h, "  static constexpr bool FITS = NZ <= 64 && BYTES <= FIT_LDS_LIMIT;", 1)):
+        assert text.count(line) == n, line
+    for line in ("constexpr bool FIT_FITS = FitLayout<NX, NU, ORDER>::FITS;",
+                 "constexpr int FIT_LDS = FIT_FITS ? (int)FitLayout<NX, NU, ORDER>::BYTES : 0;",
+                 "constexpr bool ONLINE_FITS = OnlineLayout<NX, NU, ORDER>::FITS;",
+                 "constexpr int ONLINE_LDS = ONLINE_FITS ? (int)OnlineLayout<NX, NU, ORDER>::BYTES : 0;",
+                 "  static int run(const OnlineArgs& a, int hermitian, hipStream_t s) { return hermitian ? go<true>(a, s) : go<false>(a, s); }"):
+        assert k.count(line) == 1, line
+    assert capi.count("  if (sh->fit_lds_bytes == 0)\n    return fail(M4Q_E_UNSUPPORTED, ") == 1
+    assert capi.count("  if (sh->online_lds_bytes == 0)\n    return fail(M4Q_E_UNSUPPORTED, ") == 1
+    # the plant dispatch: launch_by_plant (plant_kernel, plant_rollout_kernel) and launch_plant_feedback
+    body = k[k.index("static int launch_by_plant("):k.index("static int launch_plant(const PlantArgs& a")]
+    for line in ("  if constexpr (!SQUARE) {\n    return UNBUILT;\n",
+                 "    if (a.kind == PLANT_HAMILTONIAN) return launch_aux(kernel_of(ic<PLANT_HAMILTONIAN>{}), a, lds, s);\n",
+                 "    if (a.kind == PLANT_PROCESS) {\n      if constexpr (QUARTIC) return launch_aux(kernel_of(ic<PLANT_PROCESS>{}), a, lds, s);\n"
+                 "      else return UNBUILT;\n    }\n",
+                 "    return launch_aux(kernel_of(ic<PLANT_GENERATOR>{}), a, lds, s);\n"):
+        assert body.count(line) == 1, line
+    body = k[k.index("static int launch_plant_feedback(const FeedbackArgs& a"):k.index("static int launch_noise(")]
+    for line in ("  if constexpr (!SQUARE) {\n    return UNBUILT;\n",
+                 "    if (a.roll.kind == PLANT_HAMILTONIAN) return launch_feedback(plant_feedback_kernel<PLANT_HAMILTONIAN>, a, lds, s);\n",
+                 "    if (a.roll.kind == PLANT_PROCESS) {\n      if constexpr (QUARTIC) return launch_feedback(plant_feedback_kernel<PLANT_PROCESS>, "
+                 "a, lds, s);\n      else return UNBUILT;\n    }\n",
+                 "    return launch_feedback(plant_feedback_kernel<PLANT_GENERATOR>, a, lds, s);\n"):
+        assert body.count(line) == 1, line
+    # the gradient and the linearisation: Hamiltonian, process where QUARTIC, nothing else - and the entry points refuse the generator
+    body = k[k.index("static int launch_plant_grad("):k.index("// a linearisation kernel over quads")]
+    assert body.count("    if (a.roll.kind == PLANT_HAMILTONIAN)\n      return launch_grad(plant_rollout_grad_kernel<PLANT_HAMILTONIAN>, ") == 1
+    assert body.count("    if constexpr (QUARTIC) {\n      if (a.roll.kind == PLANT_PROCESS)\n        return launch_grad("
+                      "plant_rollout_grad_kernel<PLANT_PROCESS>, ") == 1
+    assert body.count("    return UNBUILT;\n") == 2 and "PLANT_GENERATOR" not in body
+    body = k[k.index("static int launch_plant_linearize("):k.index("#ifndef M4Q_NO_AUX\nstatic int launch_model_grad(")]
+    assert body.count("    if (a.kind == PLANT_HAMILTONIAN)\n      return launch_plant_lin(plant_linearize_kernel<PLANT_HAMILTONIAN>, ") == 1
+    assert body.count("    if constexpr (QUARTIC) {\n      if (a.kind == PLANT_PROCESS)\n        return launch_plant_lin("
+                      "plant_linearize_kernel<PLANT_PROCESS>, ") == 1
+    assert body.count("    return UNBUILT;\n") == 2 and "PLANT_GENERATOR" not in body
+    assert capi.count('  if (plant_kind == M4Q_PLANT_GENERATOR)\n    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no gradient '
+                      'kernel ') == 1
+    assert capi.count('  if (plant_kind == M4Q_PLANT_GENERATOR)\n    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no '
+                      'linearisation kernel ') == 1
+    # one object per (n, m) serves every plant family, plant-only shapes included; the model families need the shape's own object
+    assert capi.count("  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);") == 5
+    assert capi.count("    if (s->nx == nx && s->nu == nu && s->order == order && (plant_ok || !s->plant_only)) return s;") == 1
+    # the grid cap of every auxiliary launch
+    assert k.count("constexpr int ROWS = 4;") == 1
+    assert k.count("  const int nquads = (B + ROWS - 1) / ROWS;\n  return nquads < 4096 ? (nquads > 0 ? nquads : 1) : 4096;\n") == 1
+    assert k.count("dim3(a.B < 4096 ? a.B : 4096), dim3(64), lds, s, a);") == 3          # fit, fit_qr, online
+    assert k.count("dim3(a.fit.B < 4096 ? a.fit.B : 4096), dim3(64), lds, s, a);") == 2  # refit, refit_qr
+    assert k.count("dim3(grid_for(a.B)), dim3(64), lds, s, a);") == 1 and k.count("dim3(grid_for(a.roll.B)), dim3(64), lds, s, a);") == 2
+    assert k.count("dim3(grid_for(a.B * a.T)), dim3(64), lds, s, a);") == 1
+    assert (kv.AUX_GRID, kv.ROWS, kv.QUAD_WRAP, kv.FIT_LDS_LIMIT) == (4096, 4, 16384, 160 * 1024)
+
+
+def test_aux_mirrors_agree_with_the_rule_text():
+    for nu, order in ((1, 1), (2, 1), (3, 1), (1, 2), (2, 2), (1, 3), (1, 4)):
+        assert kv.n_lifted(nu, order) == size_of_library(order, nu) - 1
+    assert [kv.lifted_size(*s[:3]) for s in kv.shapes()] == [8, 12, 12, 27, 54, 64, 32, 48, 64, 80, 24, 48]
+    # FitLayout at (16, 3, 1), the largest that fits: 2 * 64 * 65 + 16 * 65 + 64 + 16 + 32 complex entries
+    assert kv.fit_lds_bytes(16, 3, 1) == 16 * 9472 and kv.fit_lds_bytes(16, 3, 1) <= kv.FIT_LDS_LIMIT < kv.fit_lds_bytes(16, 1, 4)
+    assert kv.online_lds_bytes(4, 1, 1) == 16 * (8 * 9 + 4 * 9 + 8 + 4 + 8 + 8 + 4 + 4)
+    assert kv.fit_fits(16, 3, 1) and kv.online_fits(16, 1, 3) and not kv.fit_fits(16, 1, 4) and not kv.online_fits(16, 1, 4)
+    assert kv.plant_kinds(8) == [] and kv.plant_kinds(9) == [kv.HAMILTONIAN, kv.GENERATOR]
+    assert kv.plant_kinds(16) == [kv.HAMILTONIAN, kv.GENERATOR, kv.PROCESS]
+
+
+def test_spot_check_of_the_aux_cells():
+    cells = kv.aux_cells()
+    ids = [kv.aux_cell_id(c) for c in cells]
+    assert len(ids) == len(set(ids))
+    by = {}
+    for c in cells:
+        by.setdefault(c.family, []).append(c)
+    assert set(by) == set(kv.MODEL_FAMILIES) | set(kv.FIT_FAMILIES) | set(kv.PLANT_FAMILIES) | {"online"}
+    model_shapes = [(4, 1, 1), (4, 1, 2), (4, 2, 1), (9, 2, 1), (9, 2, 2), (16, 3, 1), (16, 1, 1), (16, 1, 2), (16, 1, 3), (16, 1, 4), (8, 2, 1)]
+    fitting = [s for s in model_shapes if s != (16, 1, 4)]
+    for f in kv.MODEL_FAMILIES:                                    # the eleven objects with the model kernels, (16, 1, 4) among them
+        assert [(c.nx, c.nu, c.order, c.kind) for c in by[f]] == [s + ("-",) for s in model_shapes]
+    for f in kv.FIT_FAMILIES:                                      # the ten fitting shapes; (16, 1, 4), nz = 80, refused
+        assert [(c.nx, c.nu, c.order) for c in by[f] if c.kind == "-"] == fitting
+        assert [(c.nx, c.nu, c.order) for c in by[f] if c.kind == kv.REFUSED] == [(16, 1, 4)] and len(by[f]) == 11
+    for form in (kv.PLAIN, kv.HERMITIAN_FORM):
+        assert [(c.nx, c.nu, c.order) for c in by["online"] if c.kind == form] == fitting
+    assert [(c.nx, c.nu, c.order) for c in by["online"] if c.kind == kv.REFUSED] == [(16, 1, 4)] and len(by["online"]) == 21
+    # (16, 2): the plant families alone
+    assert {c.family for c in cells if (c.nx, c.nu) == (16, 2)} == set(kv.PLANT_FAMILIES)
+    assert not any(c.nx == 8 for f in kv.PLANT_FAMILIES for c in by[f])
+    nm = [(4, 1), (4, 2), (9, 2), (16, 1), (16, 2), (16, 3)]
+    for f in ("plant_rollout", "plant_feedback"):
+        for kind in (kv.HAMILTONIAN, kv.GENERATOR):
+            assert [(c.nx, c.nu) for c in by[f] if c.kind == kind] == nm
+        assert not any(c.kind == kv.REFUSED for c in by[f])
+    for f in ("plant_grad", "plant_linearize"):
+        assert [(c.nx, c.nu) for c in by[f] if c.kind == kv.HAMILTONIAN] == nm
+        assert [(c.nx, c.nu) for c in by[f] if c.kind == kv.REFUSED] == nm and not any(c.kind == kv.GENERATOR for c in by[f])
+    for f in kv.PLANT_FAMILIES:                                    # the process cells: the quartic (n, m)
+        assert [(c.nx, c.nu) for c in by[f] if c.kind == kv.PROCESS] == [(16, 1), (16, 2), (16, 3)]
+        assert all(c.order == 0 for c in by[f])
+    assert len(cells) == 3 * 11 + 4 * 11 + 21 + 4 * (2 * 6 + 3)
+
+
+def test_a_dropped_shape_changes_the_aux_cells(monkeypatch, tmp_path):
+    """aux_cells() on a copy of build.py and m4q_shapes.inc with one shape line deleted loses that shape's cells and no other (the
+    rule lines themselves are pinned above: an edited one fails there)."""
+    import shutil
+    full = kv.aux_cells()
+    for name in ("build.py", "m4q_shapes.inc"):
+        shutil.copy(os.path.join(kv.CSRC, name), tmp_path / name)
+    inc = tmp_path / "m4q_shapes.inc"
+    assert inc.read_text().count("M4Q_SHAPE(16, 1, 3)\n") == 1
+    inc.write_text(inc.read_text().replace("M4Q_SHAPE(16, 1, 3)\n", ""))
+    monkeypatch.setattr(kv, "CSRC", str(tmp_path))
+    fewer = kv.aux_cells()
+    assert set(full) - set(fewer) == {c for c in full if (c.nx, c.nu, c.order) == (16, 1, 3)} and set(fewer) <= set(full)
+    assert len(full) - len(fewer) == 3 + 4 + 2
 
 
 def test_every_closed_loop_shape_has_a_scenario():
