@@ -179,6 +179,27 @@ M4Q_API int m4q_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int3
                            const double* Delta_ls, const double* u_prev, double* X_opt, double* U_opt, double* cost,
                            double* gains);
 
+/* The QP of m4q_quad_program_batch posed on the linearisation m4q_plant_linearize_batch would return along each member's own
+ * nominal trajectory, in ONE call: A_ls, B_ls and Delta_ls never exist on the host.  Two launches on one stream: the first leaves
+ * the d x d propagator U_t (A_t = (U_t (x) U_t^*) (x) I_cols is formed from it where it is used: 16 d^2 bytes per point instead
+ * of 16 n^2), B_t and Delta_t in device workspaces, the second is the Riccati sweep and rollout of m4q_quad_program_batch over
+ * them.  plant_linearize.py: plant_quad_program_reference is the definition.
+ * The plant side as m4q_plant_linearize_batch: dts [T] r, X [B][T][n] c (the linearisation points), U [B|1][T][m] r
+ * (u_per_instance), u_scale [B][m] r or NULL, op0, ops, plant_per_instance.  The QP side as m4q_quad_program_batch: qp_flags, sat,
+ * du, x_init [B][n] c (NULL: X[b][0]), X_bm, U_bm, bm_per_instance, Q_ls, R_ls, u_prev [B][m] r or NULL
+ * -> X_opt [B][T+1][n] c, U_opt [B][T][m] r, cost [B] r, gains [B][T][n+1][m] c (NULL to skip).  M4Q_QP_EXACT_BOX as there: the same
+ * workspace and 4 GiB limit, the same meaning of the gains.
+ * M4Q_E_BADARG: B or T < 1 (or B T beyond 2^31 - 1); a required array missing; sat not positive; qp_flags that
+ * m4q_quad_program_batch refuses; a plant_kind that is no device plant; M4Q_PLANT_PROCESS on a dim_x that is no fourth power.
+ * M4Q_E_UNSUPPORTED: no compiled shape; dim_x not a square; a plant-only shape (no QP kernel); M4Q_PLANT_GENERATOR (no kernel:
+ * m4q_discretize_batch + m4q_linearize_batch + m4q_quad_program_batch).  All checked before a device is asked for. */
+M4Q_API int m4q_plant_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
+                                 const double* X, const double* U, int32_t u_per_instance, const double* u_scale,
+                                 const double* op0, const double* ops, int32_t plant_per_instance,
+                                 int32_t qp_flags, double sat, double du, const double* x_init, const double* X_bm,
+                                 const double* U_bm, int32_t bm_per_instance, const double* Q_ls, const double* R_ls,
+                                 const double* u_prev, double* X_opt, double* U_opt, double* cost, double* gains);
+
 /* replaces vectorize.discretize_homogeneous (vectorize.py:8-49) for B operator sets: the Taylor/Dyson expansion of
  * exp(dt (G_0 + sum_k u_k G_k)) to `order`, binned by control monomial.
  * generators [B|1][1+m][n][n] c, scaled per member by scales [B][1+m] r when given (NULL = 1) -> models [B][n][n(1+P)] c */

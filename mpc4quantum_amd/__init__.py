@@ -20,6 +20,7 @@ from .mpc import (StepClock, complex_to_real, complex_to_real_op, iqp_line_searc
                   real_to_complex, real_to_complex_op, shift_guess, val_to_str)
 from .optimize import quad_program, quad_program_batch  # noqa: F401
 from .plant_linearize import plant_linearize_batch, plant_linearize_reference  # noqa: F401
+from .plant_linearize import plant_quad_program_batch, plant_quad_program_reference  # noqa: F401
 from .rollout import model_rollout_batch, plant_rollout_batch  # noqa: F401
 from .session import EnsembleSession  # noqa: F401
 from .vectorize import discretize_homogeneous, discretize_homogeneous_batch, liouvillian, vectorize_me  # noqa: F401

@@ -170,6 +170,28 @@ struct PlantLinArgs {
   M4Q_P(cplx) A_ls; M4Q_P(cplx) B_ls; M4Q_P(cplx) D_ls;      // [B][T][n][n], [B][T][n][m], [B][T][n], as LinArgs
 };
 
+// The QP of QpArgs on the linearisation PlantLinArgs describes, in two launches on one stream and no host in between
+// (m4q_plant_quad_program_batch; m4q_plant_qp.h): plant_factor_kernel writes U_t, B_t and Delta_t of every (member, point) pair
+// into the three workspaces, plant_qp_kernel sweeps each member over them.  x_init null: member b starts from X[b][0].
+struct PlantQpArgs {
+  int B, T, kind, flags;
+  double sat, du;
+  M4Q_P(const double) dts;                         // the plant side, as PlantLinArgs
+  M4Q_P(const cplx) X;
+  M4Q_P(const double) U; long u_stride;
+  M4Q_P(const double) u_scale;
+  M4Q_P(const cplx) op0; long op0_stride;
+  M4Q_P(const cplx) ops; long ops_stride;
+  M4Q_P(const cplx) x_init;                        // the QP side, as QpArgs ([B][n] or null)
+  M4Q_P(const cplx) X_bm; long xbm_stride;
+  M4Q_P(const double) U_bm; long ubm_stride;
+  M4Q_P(const cplx) Q_ls; M4Q_P(const cplx) R_ls;
+  M4Q_P(const double) u_prev;
+  M4Q_P(cplx) U_ws; M4Q_P(cplx) B_ws; M4Q_P(cplx) D_ws;      // workspaces [B][T][d][d], [B][T][n][m], [B][T][n]: never copied back
+  M4Q_P(cplx) X_opt; M4Q_P(double) U_opt; M4Q_P(double) cost; M4Q_P(cplx) gains;
+  M4Q_P(cplx) X_alt; M4Q_P(double) U_alt; M4Q_P(double) pin_stat; M4Q_P(int) sweep_counts;   // QP_EXACT_BOX, as QpArgs
+};
+
 // A stored feedback law closing the loop of a rollout (m4q_plant_feedback_batch, m4q_model_feedback_batch; m4q_feedback.h,
 // feedback.py is the definition).  `roll` is the rollout without its control sequence (roll.u is u_ref, roll.u_stride its
 // stride): at step t the member commands u_t = clip(Re(K_t [x_t - x_ref[t] ; 1]) + u_ref[t]) and sees u_scale[b][k] u_t[k].
@@ -301,6 +323,7 @@ struct ShapeOps {
   int (*launch_refit)(const RefitArgs&, hipStream_t);              // dmdc_refit_kernel, dmdc_refit_qr_kernel: the shapes and the
   int (*launch_refit_qr)(const RefitArgs&, hipStream_t);           // LDS of launch_fit
   int (*launch_plant_linearize)(const PlantLinArgs&, hipStream_t); // (the shapes of launch_plant_grad; no generator plant)
+  int (*launch_plant_qp)(const PlantQpArgs&, hipStream_t);         // (square shapes that hold qp_kernel; no generator plant)
 };
 
 }  // namespace m4q

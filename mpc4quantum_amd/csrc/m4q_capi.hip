@@ -1474,6 +1474,80 @@ int m4q_plant_linearize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t p
   return st.finish(sh->launch_plant_linearize(a, nullptr), "plant linearize");
 }
 
+int m4q_plant_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
+                                 const double* X, const double* U, int32_t u_per_instance, const double* u_scale,
+                                 const double* op0, const double* ops, int32_t plant_per_instance,
+                                 int32_t qp_flags, double sat, double du, const double* x_init, const double* X_bm,
+                                 const double* U_bm, int32_t bm_per_instance, const double* Q_ls, const double* R_ls,
+                                 const double* u_prev, double* X_opt, double* U_opt, double* cost, double* gains) {
+  const char* who = "m4q_plant_quad_program_batch";
+  // (the lookup admits plant-only shapes so that theirs is a refusal of its own: such an object holds no QP kernel)
+  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, true);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "%s: no kernel for dim_x=%d dim_u=%d", who, dim_x, dim_u);
+  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  if (sh->plant_only)
+    return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d dim_u=%d is a plant-only shape, it has no QP kernel", who, dim_x, dim_u);
+  if (B < 1 || T < 1) return fail(M4Q_E_BADARG, "%s: B and T must be at least 1 (got %d, %d)", who, B, T);
+  if ((int64_t)B * T > INT32_MAX) return fail(M4Q_E_BADARG, "%s: B T = %lld points do not fit one launch", who, (long long)B * T);
+  if (!dts || !X || !U || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, X, U, op0 and ops are required", who);
+  if (!X_bm || !U_bm || !Q_ls || !R_ls || !X_opt || !U_opt || !cost)
+    return fail(M4Q_E_BADARG, "%s: X_bm, U_bm, Q_ls, R_ls, X_opt, U_opt and cost are required", who);
+  if (!(sat > 0)) return fail(M4Q_E_BADARG, "%s: sat must be positive", who);
+  if (check_qp_flags(qp_flags)) {
+    const std::string why = m4q_last_error();
+    return fail(M4Q_E_BADARG, "%s: %s", who, why.c_str());
+  }
+  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_quad_program_batch: plant_kind %d is not a device plant")) {
+    if (plant_kind == M4Q_PLANT_PROCESS) return fail(rc, "%s: M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", who, dim_x);
+    return rc;
+  }
+  if (plant_kind == M4Q_PLANT_GENERATOR)
+    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no kernel here (its block matrix has (1 + m) n > 16 columns): "
+                "use m4q_discretize_batch + m4q_linearize_batch + m4q_quad_program_batch", who);
+  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x), BT = (size_t)B * T, BT1 = (size_t)B * (T + 1);
+  if ((qp_flags & M4Q_QP_EXACT_BOX) && (double)BT1 * n * 16 * 2 >= 4294967296.0)
+    return fail(M4Q_E_BADARG, "%s: M4Q_QP_EXACT_BOX: batch too large for one call (trajectory workspace must stay below 4 GiB)", who);
+  if (int rc = need_device()) return rc;
+  const Extent eu(B, u_per_instance, (size_t)T * m), e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  const Extent xbm(B, bm_per_instance, (size_t)(T + 1) * n), ubm(B, bm_per_instance, (size_t)T * m);
+  Stage st;
+  m4q::PlantQpArgs a{};
+  a.B = B; a.T = T; a.kind = plant_kind; a.flags = qp_flags; a.sat = sat; a.du = du;
+  a.dts = st.in<double>(dts, T);
+  a.X = st.in<cplx>(X, BT * n);
+  a.U = st.in<double>(U, eu.count); a.u_stride = eu.stride;
+  if (u_scale) a.u_scale = st.in<double>(u_scale, (size_t)B * m);
+  a.op0 = st.in<cplx>(op0, e0.count); a.op0_stride = e0.stride;
+  a.ops = st.in<cplx>(ops, ek.count); a.ops_stride = ek.stride;
+  if (x_init) a.x_init = st.in<cplx>(x_init, (size_t)B * n);
+  a.X_bm = st.in<cplx>(X_bm, xbm.count); a.xbm_stride = xbm.stride;
+  a.U_bm = st.in<double>(U_bm, ubm.count); a.ubm_stride = ubm.stride;
+  a.Q_ls = st.in<cplx>(Q_ls, (size_t)(T + 1) * n * n); a.R_ls = st.in<cplx>(R_ls, (size_t)T * m * m);
+  if (u_prev) a.u_prev = st.in<double>(u_prev, (size_t)B * m);
+  // the linearisation stays on the device: U_t (d x d, whatever the plant: k = d), B_t and Delta_t
+  a.U_ws = st.out<cplx>(nullptr, BT * k * k); a.B_ws = st.out<cplx>(nullptr, BT * n * m); a.D_ws = st.out<cplx>(nullptr, BT * n);
+  std::vector<int> sweeps;                                  // diagnostic (M4Q_QP_TRACE): pinned sweeps per instance
+  if (qp_flags & M4Q_QP_EXACT_BOX) {
+    if (getenv("M4Q_QP_TRACE")) {
+      sweeps.resize(B);
+      a.sweep_counts = st.out<int>(sweeps.data(), B);
+    }
+    a.X_alt = st.out<cplx>(nullptr, 2 * BT1 * n); a.U_alt = st.out<double>(nullptr, 2 * BT * m);
+    a.pin_stat = st.out<double>(nullptr, BT * m);
+  }
+  a.X_opt = st.out<cplx>(X_opt, BT1 * n); a.U_opt = st.out<double>(U_opt, BT * m); a.cost = st.out<double>(cost, B);
+  a.gains = st.out<cplx>(gains, BT * (n + 1) * m);          // (workspace when the caller wants no gains)
+  if (st.error()) return st.error();
+  const int rc = st.finish(sh->launch_plant_qp(a, nullptr), "plant qp");
+  if (!rc && !sweeps.empty()) {
+    long sum = 0;
+    int mx = 0;
+    for (int v : sweeps) { sum += v; mx = v > mx ? v : mx; }
+    fprintf(stderr, "m4q: exact box QP on the plant: %d instances, pinned sweeps mean %.2f max %d\n", B, (double)sum / B, mx);
+  }
+  return rc;
+}
+
 int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* u,
                                  int32_t u_per_instance, const double* u_scale, const double* models, int32_t model_per_instance,
                                  const double* W, const double* target, int32_t target_per_instance, int32_t q_mode,

@@ -12,6 +12,7 @@
 #include "m4q_online.h"
 #include "m4q_grad.h"
 #include "m4q_plant_lin.h"
+#include "m4q_plant_qp.h"
 #include "m4q_noise.h"
 #include "m4q_observe.h"
 #include "m4q_tile3.h"
@@ -2052,6 +2053,132 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NX == 9 ? 1 
   }
 }
 
+#ifndef M4Q_NO_AUX
+// ---------------------------------------------------------------------------------------------
+// The QP on the plant's own linearisation (m4q_plant_quad_program_batch; m4q_plant_qp.h): two launches on one stream.  They stay
+// two kernels: the linearisation has B T independent units at the register budget of the block exponential (one wave per SIMD at
+// n = 9), the sweep is serial per member at qp_kernel's budget - fused, the sweep would inherit the exponential's occupancy.
+//
+// plant_factor_kernel: plant_linearize_kernel's work layout and LDS; in place of A it leaves the propagator U_t - the first d^2
+// entries of F, one per lane at consecutive addresses - beside B_t and Delta_t, all three in device workspaces.
+template <int PLANT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NX == 9 ? 1 : WAVES, 8))) void plant_factor_kernel(PlantQpArgs a) {
+  static_assert(PLANT == PLANT_HAMILTONIAN || PLANT == PLANT_PROCESS, "the generator plant has no linearisation kernel");
+  constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;
+  constexpr int NC = PLANT == PLANT_PROCESS ? D * D : 1;
+  static_assert(D * D <= 16, "one entry of U per lane of the row");
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const LaneGeo L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* scratch = lds + g * plant_lin_lds_elems<PLANT>();
+  const int units = a.B * a.T;                       // (the host keeps B T inside an int)
+  const int nquads = quads_of(units);
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const QuadRow r(quad, g, units);                 // r.b: this row's unit
+    const int b0 = (int)(r.q0 / a.T);                // the quad's first member (wave-uniform)
+    const int b = (int)(r.b / a.T), t = (int)(r.b - (long)b * a.T);
+    const unsigned bl = (unsigned)(b - b0);
+    const GView op0 = gview(a.op0, b0 * a.op0_stride, bl * (unsigned)a.op0_stride);
+    const GView ops = gview(a.ops, b0 * a.ops_stride, bl * (unsigned)a.ops_stride);
+    double u[NU], sc[NU];
+#pragma unroll
+    for (int k = 0; k < NU; ++k) {
+      u[k] = gld(a.U, b * a.u_stride + (long)t * NU + k);
+      sc[k] = a.u_scale ? gld(a.u_scale, (long)b * NU + k) : 1.0;
+    }
+    const cplx x = gld(a.X, r.b * NX + j);
+    cplx Bj[NU], dlt;
+    plant_lin_point<NX, NU, D, NC>(x, u, sc, op0, ops, gld(a.dts, t), scratch, j, jj, Bj, dlt);
+    if (r.valid && L.lane_ok) {
+#pragma unroll
+      for (int k = 0; k < NU; ++k) gst(a.B_ws, (r.b * NX + j) * NU + k, Bj[k]);
+      gst(a.D_ws, r.b * NX + j, dlt);
+    }
+    const cplx ue = scratch[jj < D * D ? jj : D * D - 1];
+    if (r.valid && jj < D * D) gst(a.U_ws, r.b * (D * D) + jj, ue);
+    wave_sync();                                   // the row's reads of its LDS block are done
+  }
+}
+
+// plant_qp_kernel: qp_kernel's body on PlantProv - A_t formed from U_t - with x_init defaulting to X[b][0].  Written beside
+// qp_kernel, not shared with it, so that qp_kernel's code stays what it was.
+template <int PLANT>
+__global__ __launch_bounds__(64) M4Q_OCC void plant_qp_kernel(PlantQpArgs a) {
+  static_assert(PLANT == PLANT_HAMILTONIAN || PLANT == PLANT_PROCESS, "the generator plant has no linearisation kernel");
+  constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;
+  constexpr int NC = PLANT == PLANT_PROCESS ? D * D : 1;
+  const LaneGeo L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  const int T = a.T;
+  const int nquads = quads_of(a.B);
+  CostRef<cplx> cost;
+  cost.Q = (const cplx*)a.Q_ls; cost.Qf = (const cplx*)a.Q_ls + (long)T * NX * NX; cost.q_stride = (long)NX * NX;
+  cost.R = (const cplx*)a.R_ls; cost.r_stride = (long)NU * NU;
+  const unsigned sX = (unsigned)(T + 1) * NX, sU = (unsigned)T * NU, sG = (unsigned)T * (NX + 1) * NU;
+  const unsigned sP = (unsigned)T * D * D, sB = (unsigned)T * NX * NU, sD = (unsigned)T * NX;
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const QuadRow r(quad, g, a.B);
+    PlantProv<NX, NU, D, NC> prov;
+    prov.U_ls = gview(a.U_ws, r.q0 * sP, r.gl * sP);
+    prov.B_ls = gview(a.B_ws, r.q0 * sB, r.gl * sB);
+    prov.D_ls = gview(a.D_ws, r.q0 * sD, r.gl * sD);
+    prov.j = j;
+    Window win;
+    win.xbm = gview(a.X_bm, r.q0 * a.xbm_stride, r.gl * (unsigned)a.xbm_stride);
+    win.ubm = gview(a.U_bm, r.q0 * a.ubm_stride, r.gl * (unsigned)a.ubm_stride);
+    const GView gains = gview(a.gains, r.q0 * sG, r.gl * sG);
+    const GView Xo = gview(a.X_opt, r.q0 * sX, r.gl * sX);
+    const GView Uo = gview(a.U_opt, r.q0 * sU, r.gl * sU);
+    const bool st = r.valid && L.lane_ok;
+    riccati_backward<cplx, NX, NU>(prov, T, win, cost, a.flags, gains, j, st);
+    wave_sync();
+    double lo0[NU], hi0[NU], u_first[NU];
+#pragma unroll
+    for (int k = 0; k < NU; ++k) {
+      const bool band = (a.flags & QP_DU_BAND) != 0 && a.u_prev != nullptr;
+      const double up = band ? gld(a.u_prev, r.b * NU + k) : 0.0;
+      lo0[k] = band ? up - a.du : -a.sat;
+      hi0[k] = band ? up + a.du : a.sat;
+    }
+    const cplx x0 = a.x_init ? gld(a.x_init, r.b * NX + j) : gld(a.X, r.b * ((long)T * NX) + j);
+    const bool exact = (a.flags & QP_EXACT_BOX) != 0;
+    // (the exact solver's ping-pong workspace, as qp_kernel)
+    const GView Xa = gview(exact ? a.X_alt : a.X_opt, r.q0 * sX, r.gl * sX);
+    const GView Ua = gview(exact ? a.U_alt : a.U_opt, r.q0 * sU, r.gl * sU);
+    const double obj = rollout_forward<cplx, NX, NU, true>(prov, T, x0, win, cost, a.flags, gains, a.sat, lo0, hi0, Xa, Ua, j, st,
+                                                              u_first);
+    wave_sync();
+    double obj_out = obj;
+    if (exact) {
+      const GView Xb = gview(a.X_alt, r.q0 * sX, r.gl * sX + (unsigned)a.B * sX);
+      const GView Ub = gview(a.U_alt, r.q0 * sU, r.gl * sU + (unsigned)a.B * sU);
+      const GView stat = gview(a.pin_stat, r.q0 * sU, r.gl * sU);
+      PinCtx<NU> pin;
+      pin.stat = stat;
+      pin.box.sat = a.sat;
+#pragma unroll
+      for (int k = 0; k < NU; ++k) { pin.lo0[k] = lo0[k]; pin.hi0[k] = hi0[k]; }
+      BoxQpRow row;
+      if (r.valid) row.begin(obj);
+      while (__any(row.busy())) box_qp_iterate<cplx, NX, NU>(prov, T, x0, win, cost, a.flags, gains, pin, Xa, Ua, Xb, Ub, row, j, jj, L.lane_ok);
+      obj_out = row.Jk;
+      const QpStats& stats = row.stats;
+      GView Xs = Xa, Us = Ua;
+      Xs.off = row.cur_is_a() ? Xa.off : Xb.off;
+      Us.off = row.cur_is_a() ? Ua.off : Ub.off;
+      if (st) {
+        for (int t = 0; t <= T; ++t) Xo.st<cplx>(t * NX + j, Xs.ld<cplx>(t * NX + j));
+        if (j == 0)
+          for (int i = 0; i < T * NU; ++i) Uo.st<double>(i, Us.ld<double>(i));
+      }
+      if (r.valid && jj == 0 && a.sweep_counts) gst(a.sweep_counts, r.b, stats.sweeps);
+      wave_sync();
+    }
+    if (r.valid && jj == 0) gst(a.cost, r.b, obj_out);
+  }
+}
+#endif  // M4Q_NO_AUX
+
 // ---------------------------------------------------------------------------------------------
 // The measurement noise of B members at one column of xs (noise.py: MeasurementNoise.sample), one component per lane, by the
 // device function the closed loop calls: a run's noise realisation without the run.
@@ -2516,6 +2643,37 @@ static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant_linearize(const PlantLinArgs&, hipStream_t) { return UNBUILT; }
 #endif
 
+#ifndef M4Q_NO_AUX
+// the two kernels of the QP on the plant's own linearisation, on one stream: the factors of every (member, point) pair, then the
+// sweep over quads of members (launch_aux's launch)
+template <class KF, class KQ>
+static int launch_plant_qp_pair(KF factor, KQ sweep, const PlantQpArgs& a, size_t lds, hipStream_t s) {
+  int rc = prep_lds(factor, lds);
+  if (rc) return rc;
+  const int units = a.B * a.T;
+  hipLaunchKernelGGL(factor, dim3(grid_for(units)), dim3(64), lds, s, a);
+  if (hipError_t e = hipGetLastError()) return -(int)e;
+  return launch_aux(sweep, a, 0, s);
+}
+static int launch_plant_qp(const PlantQpArgs& a, hipStream_t s) {
+  if constexpr (!SQUARE) {
+    return UNBUILT;
+  } else {
+    if (a.kind == PLANT_HAMILTONIAN)
+      return launch_plant_qp_pair(plant_factor_kernel<PLANT_HAMILTONIAN>, plant_qp_kernel<PLANT_HAMILTONIAN>, a,
+                                  sizeof(cplx) * (size_t)(ROWS * plant_lin_lds_elems<PLANT_HAMILTONIAN>()), s);
+    if constexpr (QUARTIC) {
+      if (a.kind == PLANT_PROCESS)
+        return launch_plant_qp_pair(plant_factor_kernel<PLANT_PROCESS>, plant_qp_kernel<PLANT_PROCESS>, a,
+                                    sizeof(cplx) * (size_t)(ROWS * plant_lin_lds_elems<PLANT_PROCESS>()), s);
+    }
+    return UNBUILT;
+  }
+}
+#else
+static int launch_plant_qp(const PlantQpArgs&, hipStream_t) { return UNBUILT; }
+#endif
+
 #if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
 // coords: complex generators; real n x n (lifted to the Hermitian basis); real (n-1) x (n-1) (their traceless blocks)
 static int launch_discretize(const DiscArgs& a, Coords coords, hipStream_t s) {
@@ -2547,7 +2705,7 @@ static const ShapeOps* shape_ops() {
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
                                ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr,
-                               launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr, launch_plant_linearize};
+                               launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr, launch_plant_linearize, launch_plant_qp};
   return &ops;
 }
 

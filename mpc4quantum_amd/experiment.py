@@ -109,6 +109,14 @@ def _linearize_batch(exp, X, U, ts_or_dt, u_scale, outputs, op0):
     return plant_linearize_batch(X, U, own0 if op0 is None else op0, ops, ts_or_dt, exp.plant_kind, u_scale=u_scale, outputs=outputs)
 
 
+def _quad_program_batch(exp, X, U, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, du, u_prev, x_init, u_scale, exact, gains, op0):
+    """quad_program_batch of the two unitary device plants, on their own linearisation: operators as _linearize_batch."""
+    from .plant_linearize import plant_quad_program_batch
+    own0, ops = exp.operators()
+    return plant_quad_program_batch(X, U, own0 if op0 is None else op0, ops, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, du=du, u_prev=u_prev,
+                                    x_init=x_init, kind=exp.plant_kind, u_scale=u_scale, exact=exact, gains=gains)
+
+
 class QExperiment(Experiment):
     """Closed-system plant: H0 and H1_list are d x d Hermitian (ndarray or qutip.Qobj)."""
 
@@ -223,6 +231,13 @@ class QExperiment(Experiment):
         discretised model (WrapModel.linearize_batch)."""
         return _linearize_batch(self, X, U, ts_or_dt, u_scale, outputs, op0)
 
+    def quad_program_batch(self, X, U, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, du=None, u_prev=None, x_init=None, u_scale=None,
+                           exact=False, gains=True, op0=None):
+        """The QP of quad_program_batch on this plant's own Jacobians along X, U, for an ensemble in one device call
+        (plant_quad_program_batch): X, U, ts_or_dt, u_scale, op0 as linearize_batch, the rest as plant_quad_program_batch.  Returns
+        (X_opt, U_opt, cost, gains).  With collapse operators the plant is a generator plant, which is refused as it is there."""
+        return _quad_program_batch(self, X, U, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, du, u_prev, x_init, u_scale, exact, gains, op0)
+
 
 class LExperiment(QExperiment):
     """Open-system plant: x' = (L0 + sum_k u_k L_k) x with n x n generators on vec_r(rho)."""
@@ -241,6 +256,12 @@ class LExperiment(QExperiment):
         """Refused: the generator plant has no linearisation kernel."""
         raise ValueError("LExperiment.linearize_batch: the generator plant has no linearisation of its own on the device - discretise "
                          "the generators (discretize_homogeneous) and linearise the model with WrapModel.linearize_batch")
+
+    def quad_program_batch(self, *args, **kwargs):
+        """Refused: the generator plant has no linearisation kernel."""
+        raise ValueError("LExperiment.quad_program_batch: the generator plant has no linearisation of its own on the device - "
+                         "discretise the generators (discretize_homogeneous), linearise the model with WrapModel.linearize_batch and "
+                         "solve with quad_program_batch")
 
     def f(self, t, x, u):
         L = self.H0 + sum(h * uk for h, uk in zip(self.H1_list, np.reshape(u, -1)))
@@ -376,6 +397,12 @@ class QSynthesis(Experiment):
         """The exact Jacobians of the process plant's held-control step along trajectories, for an ensemble in one launch
         (plant_linearize_batch): arguments and the returned tuple as QExperiment.linearize_batch, X [B, T, d^4] process vectors."""
         return _linearize_batch(self, X, U, ts_or_dt, u_scale, outputs, op0)
+
+    def quad_program_batch(self, X, U, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, du=None, u_prev=None, x_init=None, u_scale=None,
+                           exact=False, gains=True, op0=None):
+        """The QP of quad_program_batch on the process plant's own Jacobians along X, U, for an ensemble in one device call
+        (plant_quad_program_batch): arguments and the returned tuple as QExperiment.quad_program_batch, X [B, T, d^4]."""
+        return _quad_program_batch(self, X, U, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, du, u_prev, x_init, u_scale, exact, gains, op0)
 
 
 def split_blocks(bmatrix, nrows, ncols):

@@ -173,9 +173,24 @@ class FeedbackLaw:
         gives one law, as along_trajectory; per-member nominals X_nom [B, N + 1, n] (or [B, N, n]), U_nom [B, N, m] - for instance
         the xs, us of a finished mpc_batch run - give a per-member law, with per-member operators, u_scale [B, m] and u_prev [B, m]
         where given.  X_targ [N + 1, n] and U_targ [N, m], shared or with a leading B; Q_ls, R_ls, sat, du, exact as
-        along_trajectory.  The Jacobians pass through the host between the two launches."""
+        along_trajectory.  The Jacobians pass through the host between the two launches (along_plant_trajectory_fused: they do not)."""
+        return cls._plant_trajectory_law(False, op0, ops, dt_or_ts, X_nom, U_nom, X_targ, U_targ, Q_ls, R_ls, sat, du, u_prev, kind, u_scale,
+                                         exact)
+
+    @classmethod
+    def along_plant_trajectory_fused(cls, op0, ops, dt_or_ts, X_nom, U_nom, X_targ, U_targ, Q_ls, R_ls, sat, du=None, u_prev=None,
+                                     kind=_lib.PLANT_HAMILTONIAN, u_scale=None, exact=False):
+        """along_plant_trajectory (same arguments, same checks, the same law within the project's tolerance) in ONE device call:
+        plant_quad_program_batch, the linearisation and the QP with the Jacobians left on the device."""
+        return cls._plant_trajectory_law(True, op0, ops, dt_or_ts, X_nom, U_nom, X_targ, U_targ, Q_ls, R_ls, sat, du, u_prev, kind, u_scale,
+                                         exact)
+
+    @classmethod
+    def _plant_trajectory_law(cls, fused, op0, ops, dt_or_ts, X_nom, U_nom, X_targ, U_targ, Q_ls, R_ls, sat, du, u_prev, kind, u_scale,
+                              exact):
+        """along_plant_trajectory and along_plant_trajectory_fused: the checks, then the two calls or the one."""
         from .optimize import quad_program_batch
-        from .plant_linearize import plant_linearize_batch
+        from .plant_linearize import plant_linearize_batch, plant_quad_program_batch
         X_nom = np.asarray(X_nom, dtype=np.complex128)
         U_nom = np.asarray(U_nom)
         if np.iscomplexobj(U_nom):
@@ -213,8 +228,14 @@ class FeedbackLaw:
         if law.prev_members is not None and not (per and law.prev_members == B):
             raise ValueError("u_prev must be [m]%s, got %s" % (" or [B, m] with B = %d" % B if per else " (one nominal: one QP)",
                                                                law.u_prev.shape))
-        A_ls, B_ls, D_ls = plant_linearize_batch(X_nom[:, :N], U_nom, op0, ops, dt_or_ts, kind, u_scale)
         band = u_prev is not None and du is not None
+        if fused:
+            _, _, _, gains = plant_quad_program_batch(X_nom[:, :N], U_nom, op0, ops, dt_or_ts, X_targ.reshape(-1, N + 1, n),
+                                                      U_targ.reshape(-1, N, m), Q_ls, R_ls, sat, du=du if band else None,
+                                                      u_prev=np.broadcast_to(law.u_prev, (B, m)) if band else None, x_init=X_nom[:, 0],
+                                                      kind=kind, u_scale=u_scale, exact=exact)
+            return cls.from_quad_program(gains if per else gains[0], X_targ, U_targ, sat, du, u_prev)
+        A_ls, B_ls, D_ls = plant_linearize_batch(X_nom[:, :N], U_nom, op0, ops, dt_or_ts, kind, u_scale)
         _, _, _, gains = quad_program_batch(X_nom[:, 0], X_targ.reshape(-1, N + 1, n), U_targ.reshape(-1, N, m), Q_ls, R_ls, A_ls, B_ls, D_ls,
                                             np.broadcast_to(law.u_prev, (B, m)) if band else None, sat, du, exact=exact)
         return cls.from_quad_program(gains if per else gains[0], X_targ, U_targ, sat, du, u_prev)
