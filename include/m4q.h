@@ -200,6 +200,28 @@ M4Q_API int m4q_plant_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u
                                  const double* U_bm, int32_t bm_per_instance, const double* Q_ls, const double* R_ls,
                                  const double* u_prev, double* X_opt, double* U_opt, double* cost, double* gains);
 
+/* Controls optimised on the plant itself: a Gauss-Newton SQP for B members in ONE call.  Each iteration is the QP of
+ * m4q_plant_quad_program_batch on the plant's Jacobians along the member's current trajectory, then a line search on the TRUE plant
+ * over the `steps` candidates clip(U + 2^-j (U_opt - U)), j = 0 .. steps-1: the smallest j attaining the least cost wins, is accepted
+ * if that cost is below the current one, and the member stops as converged when the decrease is at most tol times the cost.  The
+ * plant, the targets, the weights, x0 and U0 are staged once; the iterate and the workspaces stay on the device and the launches
+ * follow one another on one stream without a host synchronisation.  plant_sqp.py: plant_sqp_reference is the definition.
+ * The plant side as m4q_plant_quad_program_batch, with x0 [B][n] c and the first guess U0 [B|1][T][m] r (u_per_instance; clipped into
+ * the bounds) in place of X, U and x_init; the QP side as there; iters in 1..64, steps in 1..8, tol >= 0
+ * -> X [B][T+1][n] c, U [B][T][m] r, cost [B] r, cost_hist [B][iters+1] r (entry 0: the first guess; unused entries repeat the last
+ * cost), alpha_hist [B][iters] r (the accepted step lengths; unused entries 0), n_iter [B], status [B] (0 iterations used up,
+ * 1 converged, 2 no candidate lowered the cost: U, X and cost are kept, 3 the first cost was not finite), gains [B][T][n+1][m] c
+ * (NULL to skip): the QP's at the returned (X, U), whatever the status.
+ * M4Q_E_BADARG, M4Q_E_UNSUPPORTED: what m4q_plant_quad_program_batch refuses; iters, steps or tol outside their ranges; x0 or U0
+ * missing.  All checked before a device is asked for. */
+M4Q_API int m4q_plant_sqp_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
+                        const double* x0, const double* U0, int32_t u_per_instance, const double* u_scale,
+                        const double* op0, const double* ops, int32_t plant_per_instance,
+                        int32_t qp_flags, double sat, double du, const double* X_bm, const double* U_bm, int32_t bm_per_instance,
+                        const double* Q_ls, const double* R_ls, const double* u_prev, int32_t iters, int32_t steps, double tol,
+                        double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
+                        double* gains);
+
 /* replaces vectorize.discretize_homogeneous (vectorize.py:8-49) for B operator sets: the Taylor/Dyson expansion of
  * exp(dt (G_0 + sum_k u_k G_k)) to `order`, binned by control monomial.
  * generators [B|1][1+m][n][n] c, scaled per member by scales [B][1+m] r when given (NULL = 1) -> models [B][n][n(1+P)] c */

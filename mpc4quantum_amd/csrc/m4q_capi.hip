@@ -1548,6 +1548,96 @@ int m4q_plant_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
   return rc;
 }
 
+int m4q_plant_sqp_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
+                        const double* x0, const double* U0, int32_t u_per_instance, const double* u_scale,
+                        const double* op0, const double* ops, int32_t plant_per_instance,
+                        int32_t qp_flags, double sat, double du, const double* X_bm, const double* U_bm, int32_t bm_per_instance,
+                        const double* Q_ls, const double* R_ls, const double* u_prev, int32_t iters, int32_t steps, double tol,
+                        double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
+                        double* gains) {
+  const char* who = "m4q_plant_sqp_batch";
+  // the refusals of m4q_plant_quad_program_batch, whose launcher every iteration goes through, then the loop's own
+  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, true);
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "%s: no kernel for dim_x=%d dim_u=%d", who, dim_x, dim_u);
+  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  if (sh->plant_only)
+    return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d dim_u=%d is a plant-only shape, it has no QP kernel", who, dim_x, dim_u);
+  if (B < 1 || T < 1) return fail(M4Q_E_BADARG, "%s: B and T must be at least 1 (got %d, %d)", who, B, T);
+  if ((int64_t)B * T > INT32_MAX) return fail(M4Q_E_BADARG, "%s: B T = %lld points do not fit one launch", who, (long long)B * T);
+  if (!x0 || !U0) return fail(M4Q_E_BADARG, "%s: x0 and U0, the initial states and the first guess, are required", who);
+  if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, op0 and ops are required", who);
+  if (!X_bm || !U_bm || !Q_ls || !R_ls) return fail(M4Q_E_BADARG, "%s: X_bm, U_bm, Q_ls and R_ls are required", who);
+  if (!X || !U || !cost || !cost_hist || !alpha_hist || !n_iter || !status)
+    return fail(M4Q_E_BADARG, "%s: X, U, cost, cost_hist, alpha_hist, n_iter and status are required", who);
+  if (!(sat > 0)) return fail(M4Q_E_BADARG, "%s: sat must be positive", who);
+  if (check_qp_flags(qp_flags)) {
+    const std::string why = m4q_last_error();
+    return fail(M4Q_E_BADARG, "%s: %s", who, why.c_str());
+  }
+  if (iters < 1 || iters > 64) return fail(M4Q_E_BADARG, "%s: iters must be in 1..64, got %d", who, iters);
+  if (steps < 1 || steps > 8) return fail(M4Q_E_BADARG, "%s: steps must be in 1..8, got %d", who, steps);
+  if (!(tol >= 0) || !std::isfinite(tol)) return fail(M4Q_E_BADARG, "%s: tol must be finite and not negative", who);
+  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_sqp_batch: plant_kind %d is not a device plant")) {
+    if (plant_kind == M4Q_PLANT_PROCESS) return fail(rc, "%s: M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", who, dim_x);
+    return rc;
+  }
+  if (plant_kind == M4Q_PLANT_GENERATOR)
+    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no kernel here (its block matrix has (1 + m) n > 16 columns): "
+                "optimise on its discretised model", who);
+  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x), BT = (size_t)B * T, BT1 = (size_t)B * (T + 1);
+  if ((qp_flags & M4Q_QP_EXACT_BOX) && (double)BT1 * n * 16 * 2 >= 4294967296.0)
+    return fail(M4Q_E_BADARG, "%s: M4Q_QP_EXACT_BOX: batch too large for one call (trajectory workspace must stay below 4 GiB)", who);
+  if (int rc = need_device()) return rc;
+  const Extent eu(B, u_per_instance, (size_t)T * m), e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  const Extent xbm(B, bm_per_instance, (size_t)(T + 1) * n), ubm(B, bm_per_instance, (size_t)T * m);
+  Stage st;
+  // staged once: the plant, the targets, the weights, x0 and U0; the iterate and every workspace live on the device
+  m4q::PlantSqpArgs s{};
+  s.B = B; s.T = T; s.kind = plant_kind; s.flags = qp_flags; s.iters = iters; s.steps = steps; s.sat = sat; s.du = du; s.tol = tol;
+  s.dts = st.in<double>(dts, T);
+  s.x0 = st.in<cplx>(x0, (size_t)B * n);
+  s.U0 = st.in<double>(U0, eu.count); s.u0_stride = eu.stride;
+  if (u_scale) s.u_scale = st.in<double>(u_scale, (size_t)B * m);
+  s.op0 = st.in<cplx>(op0, e0.count); s.op0_stride = e0.stride;
+  s.ops = st.in<cplx>(ops, ek.count); s.ops_stride = ek.stride;
+  s.X_bm = st.in<cplx>(X_bm, xbm.count); s.xbm_stride = xbm.stride;
+  s.U_bm = st.in<double>(U_bm, ubm.count); s.ubm_stride = ubm.stride;
+  s.Q_ls = st.in<cplx>(Q_ls, (size_t)(T + 1) * n * n); s.R_ls = st.in<cplx>(R_ls, (size_t)T * m * m);
+  if (u_prev) s.u_prev = st.in<double>(u_prev, (size_t)B * m);
+  s.X = st.out<cplx>(X, BT1 * n); s.U = st.out<double>(U, BT * m); s.cost = st.out<double>(cost, B);
+  s.cost_hist = st.out<double>(cost_hist, (size_t)B * (iters + 1)); s.alpha_hist = st.out<double>(alpha_hist, (size_t)B * iters);
+  s.n_iter = st.out<int>(n_iter, B); s.status = st.out<int>(status, B);
+  s.X_lin = st.out<cplx>(nullptr, BT * n);
+  double* U_qp = st.out<double>(nullptr, BT * m);
+  s.U_qp = U_qp;
+  // the QP of every iteration: m4q_plant_quad_program_batch's block on the iterate
+  m4q::PlantQpArgs a{};
+  a.B = B; a.T = T; a.kind = plant_kind; a.flags = qp_flags; a.sat = sat; a.du = du;
+  a.dts = s.dts; a.X = s.X_lin; a.U = s.U; a.u_stride = (long)(T * m); a.u_scale = s.u_scale;
+  a.op0 = s.op0; a.op0_stride = s.op0_stride; a.ops = s.ops; a.ops_stride = s.ops_stride;
+  a.x_init = s.x0; a.X_bm = s.X_bm; a.xbm_stride = s.xbm_stride; a.U_bm = s.U_bm; a.ubm_stride = s.ubm_stride;
+  a.Q_ls = s.Q_ls; a.R_ls = s.R_ls; a.u_prev = s.u_prev;
+  a.U_ws = st.out<cplx>(nullptr, BT * k * k); a.B_ws = st.out<cplx>(nullptr, BT * n * m); a.D_ws = st.out<cplx>(nullptr, BT * n);
+  if (qp_flags & M4Q_QP_EXACT_BOX) {
+    a.X_alt = st.out<cplx>(nullptr, 2 * BT1 * n); a.U_alt = st.out<double>(nullptr, 2 * BT * m);
+    a.pin_stat = st.out<double>(nullptr, BT * m);
+  }
+  a.X_opt = st.out<cplx>(nullptr, BT1 * n); a.U_opt = U_qp; a.cost = st.out<double>(nullptr, B);
+  a.gains = st.out<cplx>(gains, BT * (n + 1) * m);          // (workspace when the caller wants no gains)
+  if (st.error()) return st.error();
+  // one stream, no host synchronisation in between: the initial roll, then QP and step per iteration, then the gains' QP
+  s.iter = -1;
+  int rc = sh->launch_plant_sqp_step(s, nullptr);
+  for (int i = 0; i < iters && !rc; ++i) {
+    rc = sh->launch_plant_qp(a, nullptr);
+    if (rc) break;
+    s.iter = i;
+    rc = sh->launch_plant_sqp_step(s, nullptr);
+  }
+  if (!rc && gains) rc = sh->launch_plant_qp(a, nullptr);
+  return st.finish(rc, "plant sqp");
+}
+
 int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* u,
                                  int32_t u_per_instance, const double* u_scale, const double* models, int32_t model_per_instance,
                                  const double* W, const double* target, int32_t target_per_instance, int32_t q_mode,

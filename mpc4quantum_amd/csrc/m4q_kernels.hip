@@ -2177,6 +2177,9 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_qp_kernel(PlantQpArgs a) {
     if (r.valid && jj == 0) gst(a.cost, r.b, obj_out);
   }
 }
+
+// plant_sqp_step_kernel: the line search, the decision and the hand-over between two of these QPs (m4q_plant_sqp_batch)
+#include "m4q_plant_sqp.h"
 #endif  // M4Q_NO_AUX
 
 // ---------------------------------------------------------------------------------------------
@@ -2670,8 +2673,22 @@ static int launch_plant_qp(const PlantQpArgs& a, hipStream_t s) {
     return UNBUILT;
   }
 }
+// the step between two of them (m4q_plant_sqp.h): launch_aux's launch over quads of members, the rollouts' LDS
+static int launch_plant_sqp_step(const PlantSqpArgs& a, hipStream_t s) {
+  if constexpr (!SQUARE) {
+    return UNBUILT;
+  } else {
+    constexpr size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
+    if (a.kind == PLANT_HAMILTONIAN) return launch_aux(plant_sqp_step_kernel<PLANT_HAMILTONIAN>, a, lds, s);
+    if constexpr (QUARTIC) {
+      if (a.kind == PLANT_PROCESS) return launch_aux(plant_sqp_step_kernel<PLANT_PROCESS>, a, lds, s);
+    }
+    return UNBUILT;
+  }
+}
 #else
 static int launch_plant_qp(const PlantQpArgs&, hipStream_t) { return UNBUILT; }
+static int launch_plant_sqp_step(const PlantSqpArgs&, hipStream_t) { return UNBUILT; }
 #endif
 
 #if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
@@ -2705,7 +2722,8 @@ static const ShapeOps* shape_ops() {
   static const ShapeOps ops = {NX, NU, ORDER, NP, DD, HAS_TILE ? 1 : 0, HAS_SG ? 1 : 0, plant_only, mpc_lds_bytes, launch_mpc, launch_linearize, launch_qp, launch_plant,
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
                                ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr,
-                               launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr, launch_plant_linearize, launch_plant_qp};
+                               launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr, launch_plant_linearize, launch_plant_qp,
+                               launch_plant_sqp_step};
   return &ops;
 }
 

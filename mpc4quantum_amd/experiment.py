@@ -117,6 +117,14 @@ def _quad_program_batch(exp, X, U, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, du, u_
                                     x_init=x_init, kind=exp.plant_kind, u_scale=u_scale, exact=exact, gains=gains)
 
 
+def _sqp_batch(exp, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0):
+    """plant_sqp_batch of the two unitary device plants: operators as _linearize_batch."""
+    from .plant_sqp import plant_sqp_batch
+    own0, ops = exp.operators()
+    return plant_sqp_batch(x0, U0, own0 if op0 is None else op0, ops, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters=iters, steps=steps,
+                           tol=tol, du=du, u_prev=u_prev, kind=exp.plant_kind, u_scale=u_scale, exact=exact, gains=gains)
+
+
 class QExperiment(Experiment):
     """Closed-system plant: H0 and H1_list are d x d Hermitian (ndarray or qutip.Qobj)."""
 
@@ -237,6 +245,13 @@ class QExperiment(Experiment):
         (plant_quad_program_batch): X, U, ts_or_dt, u_scale, op0 as linearize_batch, the rest as plant_quad_program_batch.  Returns
         (X_opt, U_opt, cost, gains).  With collapse operators the plant is a generator plant, which is refused as it is there."""
         return _quad_program_batch(self, X, U, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, du, u_prev, x_init, u_scale, exact, gains, op0)
+
+    def sqp_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters=10, steps=6, tol=1e-9, du=None, u_prev=None, u_scale=None,
+                  exact=False, gains=False, op0=None):
+        """Controls optimised on this plant itself by a Gauss-Newton SQP, for an ensemble in one device call (plant_sqp_batch):
+        x0 [B, n], U0 [T, m] or [B, T, m], ts_or_dt, u_scale, op0 as linearize_batch, the rest as plant_sqp_batch.  Returns its
+        dict.  With collapse operators the plant is a generator plant, which is refused as it is there."""
+        return _sqp_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0)
 
 
 class LExperiment(QExperiment):
@@ -403,6 +418,12 @@ class QSynthesis(Experiment):
         """The QP of quad_program_batch on the process plant's own Jacobians along X, U, for an ensemble in one device call
         (plant_quad_program_batch): arguments and the returned tuple as QExperiment.quad_program_batch, X [B, T, d^4]."""
         return _quad_program_batch(self, X, U, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, du, u_prev, x_init, u_scale, exact, gains, op0)
+
+    def sqp_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters=10, steps=6, tol=1e-9, du=None, u_prev=None, u_scale=None,
+                  exact=False, gains=False, op0=None):
+        """Controls optimised on the process plant itself by a Gauss-Newton SQP, for an ensemble in one device call
+        (plant_sqp_batch): arguments and the returned dict as QExperiment.sqp_batch, x0 [B, d^4] process vectors."""
+        return _sqp_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0)
 
 
 def split_blocks(bmatrix, nrows, ncols):
