@@ -222,6 +222,23 @@ M4Q_API int m4q_plant_sqp_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t
                         double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
                         double* gains);
 
+/* m4q_plant_sqp_batch with a CLOSED-LOOP line search: an iLQR on the plant itself for B members in ONE call.  The loop, the
+ * statuses, the histories, the tol rule and the tie rule are m4q_plant_sqp_batch's; only the candidates differ.  Candidate j,
+ * a = 2^-j, runs the QP's law on the true plant around the iterate (Xbar, Ubar): from x_0 = x0, for a control the QP leaves free
+ *     u_t = clip(Ubar_t + a (Re(K_t (Xbar_t - xb_t)) + Re(k_t) + ub_t - Ubar_t) + Re(K_t (x_t - Xbar_t)))
+ * with [K_t; k_t] the gains of this iteration's QP, and for a control M4Q_QP_EXACT_BOX left on a bound (its slot of the gains holds
+ * a multiplier row) u_t = clip(Ubar_t + a (U_opt_t - Ubar_t)).  At a = 1 a free control is the stored law of
+ * m4q_plant_feedback_batch on the plant; as a -> 0 the candidate is the iterate.  The gains never leave the device between the QP
+ * and the forward pass.  plant_ilqr.py: plant_ilqr_reference is the definition.
+ * Arguments, outputs and refusals: those of m4q_plant_sqp_batch, in its order.  All checked before a device is asked for. */
+M4Q_API int m4q_plant_ilqr_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
+                         const double* x0, const double* U0, int32_t u_per_instance, const double* u_scale,
+                         const double* op0, const double* ops, int32_t plant_per_instance,
+                         int32_t qp_flags, double sat, double du, const double* X_bm, const double* U_bm, int32_t bm_per_instance,
+                         const double* Q_ls, const double* R_ls, const double* u_prev, int32_t iters, int32_t steps, double tol,
+                         double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
+                         double* gains);
+
 /* replaces vectorize.discretize_homogeneous (vectorize.py:8-49) for B operator sets: the Taylor/Dyson expansion of
  * exp(dt (G_0 + sum_k u_k G_k)) to `order`, binned by control monomial.
  * generators [B|1][1+m][n][n] c, scaled per member by scales [B][1+m] r when given (NULL = 1) -> models [B][n][n(1+P)] c */

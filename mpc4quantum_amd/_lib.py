@@ -67,6 +67,9 @@ PROTOTYPES = {
     "m4q_plant_sqp_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _i32,
                                       _i32, C.c_double, C.c_double, _dp, _dp, _i32, _dp, _dp, _dp, _i32, _i32, C.c_double,
                                       _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]),
+    "m4q_plant_ilqr_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _i32,
+                                       _i32, C.c_double, C.c_double, _dp, _dp, _i32, _dp, _dp, _dp, _i32, _i32, C.c_double,
+                                       _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]),
     "m4q_quad_program_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _dp, _dp, _dp, _i32,
                                          _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "m4q_discretize_batch": (C.c_int, [_i32, _i32, _i32, _i32, C.c_double, _dp, _i32, _dp, _dp]),

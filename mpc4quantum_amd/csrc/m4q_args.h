@@ -216,6 +216,29 @@ struct PlantSqpArgs {
   M4Q_P(int) n_iter; M4Q_P(int) status;            // [B]
 };
 
+// The step of the iLQR on the plant itself (m4q_plant_ilqr_batch; m4q_plant_ilqr.h, plant_ilqr.py is the definition): PlantSqpArgs'
+// place between two QPs of PlantQpArgs, its fields with its meanings, and `gains`, that block's gains [B][T][n + 1][m] - the
+// candidates are the QP's law run on the plant around the iterate (X_lin, U), not points of the line from U to U_qp.
+struct PlantIlqrArgs {
+  int B, T, kind, flags, iter, iters, steps;
+  double sat, du, tol;
+  M4Q_P(const double) dts;
+  M4Q_P(const cplx) x0;
+  M4Q_P(const double) U0; long u0_stride;
+  M4Q_P(const double) u_scale;
+  M4Q_P(const cplx) op0; long op0_stride;
+  M4Q_P(const cplx) ops; long ops_stride;
+  M4Q_P(const cplx) X_bm; long xbm_stride;
+  M4Q_P(const double) U_bm; long ubm_stride;
+  M4Q_P(const cplx) Q_ls; M4Q_P(const cplx) R_ls;
+  M4Q_P(const double) u_prev;
+  M4Q_P(const double) U_qp;                        // [B][T][m]: the QP's U_opt (what a pinned control of the exact mode goes to)
+  M4Q_P(const cplx) gains;                         // [B][T][n + 1][m]: the QP's rows
+  M4Q_P(double) U; M4Q_P(cplx) X_lin; M4Q_P(cplx) X;
+  M4Q_P(double) cost; M4Q_P(double) cost_hist; M4Q_P(double) alpha_hist;
+  M4Q_P(int) n_iter; M4Q_P(int) status;
+};
+
 // A stored feedback law closing the loop of a rollout (m4q_plant_feedback_batch, m4q_model_feedback_batch; m4q_feedback.h,
 // feedback.py is the definition).  `roll` is the rollout without its control sequence (roll.u is u_ref, roll.u_stride its
 // stride): at step t the member commands u_t = clip(Re(K_t [x_t - x_ref[t] ; 1]) + u_ref[t]) and sees u_scale[b][k] u_t[k].
@@ -349,6 +372,7 @@ struct ShapeOps {
   int (*launch_plant_linearize)(const PlantLinArgs&, hipStream_t); // (the shapes of launch_plant_grad; no generator plant)
   int (*launch_plant_qp)(const PlantQpArgs&, hipStream_t);         // (square shapes that hold qp_kernel; no generator plant)
   int (*launch_plant_sqp_step)(const PlantSqpArgs&, hipStream_t);  // (the shapes and plants of launch_plant_qp)
+  int (*launch_plant_ilqr_step)(const PlantIlqrArgs&, hipStream_t);    // (likewise)
 };
 
 }  // namespace m4q

@@ -1548,14 +1548,20 @@ int m4q_plant_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
   return rc;
 }
 
-int m4q_plant_sqp_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
-                        const double* x0, const double* U0, int32_t u_per_instance, const double* u_scale,
-                        const double* op0, const double* ops, int32_t plant_per_instance,
-                        int32_t qp_flags, double sat, double du, const double* X_bm, const double* U_bm, int32_t bm_per_instance,
-                        const double* Q_ls, const double* R_ls, const double* u_prev, int32_t iters, int32_t steps, double tol,
-                        double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
-                        double* gains) {
-  const char* who = "m4q_plant_sqp_batch";
+// m4q_plant_sqp_batch and m4q_plant_ilqr_batch are one call - refusals, staging, launches - around two step kernels: S is the
+// step's argument block (PlantSqpArgs, or PlantIlqrArgs, which also reads the QP's gains), `step` its launcher in ShapeOps
+extern "C++" {
+static void bind_gains(m4q::PlantSqpArgs&, const cplx*) {}
+static void bind_gains(m4q::PlantIlqrArgs& s, const cplx* gains) { s.gains = gains; }
+template <class S>
+static int plant_descent_batch(const char* who, const char* what, int (*m4q::ShapeOps::*step)(const S&, hipStream_t),
+                               int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
+                               const double* x0, const double* U0, int32_t u_per_instance, const double* u_scale,
+                               const double* op0, const double* ops, int32_t plant_per_instance,
+                               int32_t qp_flags, double sat, double du, const double* X_bm, const double* U_bm, int32_t bm_per_instance,
+                               const double* Q_ls, const double* R_ls, const double* u_prev, int32_t iters, int32_t steps, double tol,
+                               double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
+                               double* gains) {
   // the refusals of m4q_plant_quad_program_batch, whose launcher every iteration goes through, then the loop's own
   const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, true);
   if (!sh) return fail(M4Q_E_UNSUPPORTED, "%s: no kernel for dim_x=%d dim_u=%d", who, dim_x, dim_u);
@@ -1577,7 +1583,7 @@ int m4q_plant_sqp_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_k
   if (iters < 1 || iters > 64) return fail(M4Q_E_BADARG, "%s: iters must be in 1..64, got %d", who, iters);
   if (steps < 1 || steps > 8) return fail(M4Q_E_BADARG, "%s: steps must be in 1..8, got %d", who, steps);
   if (!(tol >= 0) || !std::isfinite(tol)) return fail(M4Q_E_BADARG, "%s: tol must be finite and not negative", who);
-  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_sqp_batch: plant_kind %d is not a device plant")) {
+  if (int rc = check_device_plant_kind(plant_kind, dim_x, (std::string(who) + ": plant_kind %d is not a device plant").c_str())) {
     if (plant_kind == M4Q_PLANT_PROCESS) return fail(rc, "%s: M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", who, dim_x);
     return rc;
   }
@@ -1592,7 +1598,7 @@ int m4q_plant_sqp_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_k
   const Extent xbm(B, bm_per_instance, (size_t)(T + 1) * n), ubm(B, bm_per_instance, (size_t)T * m);
   Stage st;
   // staged once: the plant, the targets, the weights, x0 and U0; the iterate and every workspace live on the device
-  m4q::PlantSqpArgs s{};
+  S s{};
   s.B = B; s.T = T; s.kind = plant_kind; s.flags = qp_flags; s.iters = iters; s.steps = steps; s.sat = sat; s.du = du; s.tol = tol;
   s.dts = st.in<double>(dts, T);
   s.x0 = st.in<cplx>(x0, (size_t)B * n);
@@ -1624,18 +1630,46 @@ int m4q_plant_sqp_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_k
   }
   a.X_opt = st.out<cplx>(nullptr, BT1 * n); a.U_opt = U_qp; a.cost = st.out<double>(nullptr, B);
   a.gains = st.out<cplx>(gains, BT * (n + 1) * m);          // (workspace when the caller wants no gains)
+  bind_gains(s, a.gains);                                   // (the closed-loop step runs the law the QP just wrote)
   if (st.error()) return st.error();
   // one stream, no host synchronisation in between: the initial roll, then QP and step per iteration, then the gains' QP
   s.iter = -1;
-  int rc = sh->launch_plant_sqp_step(s, nullptr);
+  int rc = (sh->*step)(s, nullptr);
   for (int i = 0; i < iters && !rc; ++i) {
     rc = sh->launch_plant_qp(a, nullptr);
     if (rc) break;
     s.iter = i;
-    rc = sh->launch_plant_sqp_step(s, nullptr);
+    rc = (sh->*step)(s, nullptr);
   }
   if (!rc && gains) rc = sh->launch_plant_qp(a, nullptr);
-  return st.finish(rc, "plant sqp");
+  return st.finish(rc, what);
+}
+}  // extern "C++"
+
+int m4q_plant_sqp_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
+                        const double* x0, const double* U0, int32_t u_per_instance, const double* u_scale,
+                        const double* op0, const double* ops, int32_t plant_per_instance,
+                        int32_t qp_flags, double sat, double du, const double* X_bm, const double* U_bm, int32_t bm_per_instance,
+                        const double* Q_ls, const double* R_ls, const double* u_prev, int32_t iters, int32_t steps, double tol,
+                        double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
+                        double* gains) {
+  return plant_descent_batch<m4q::PlantSqpArgs>("m4q_plant_sqp_batch", "plant sqp", &m4q::ShapeOps::launch_plant_sqp_step, B, dim_x, dim_u,
+                                                plant_kind, T, dts, x0, U0, u_per_instance, u_scale, op0, ops, plant_per_instance, qp_flags,
+                                                sat, du, X_bm, U_bm, bm_per_instance, Q_ls, R_ls, u_prev, iters, steps, tol, X, U, cost,
+                                                cost_hist, alpha_hist, n_iter, status, gains);
+}
+
+int m4q_plant_ilqr_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
+                         const double* x0, const double* U0, int32_t u_per_instance, const double* u_scale,
+                         const double* op0, const double* ops, int32_t plant_per_instance,
+                         int32_t qp_flags, double sat, double du, const double* X_bm, const double* U_bm, int32_t bm_per_instance,
+                         const double* Q_ls, const double* R_ls, const double* u_prev, int32_t iters, int32_t steps, double tol,
+                         double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
+                         double* gains) {
+  return plant_descent_batch<m4q::PlantIlqrArgs>("m4q_plant_ilqr_batch", "plant ilqr", &m4q::ShapeOps::launch_plant_ilqr_step, B, dim_x, dim_u,
+                                                 plant_kind, T, dts, x0, U0, u_per_instance, u_scale, op0, ops, plant_per_instance, qp_flags,
+                                                 sat, du, X_bm, U_bm, bm_per_instance, Q_ls, R_ls, u_prev, iters, steps, tol, X, U, cost,
+                                                 cost_hist, alpha_hist, n_iter, status, gains);
 }
 
 int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* u,

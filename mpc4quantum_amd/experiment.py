@@ -125,6 +125,14 @@ def _sqp_batch(exp, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps,
                            tol=tol, du=du, u_prev=u_prev, kind=exp.plant_kind, u_scale=u_scale, exact=exact, gains=gains)
 
 
+def _ilqr_batch(exp, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0):
+    """plant_ilqr_batch of the two unitary device plants: operators as _linearize_batch."""
+    from .plant_ilqr import plant_ilqr_batch
+    own0, ops = exp.operators()
+    return plant_ilqr_batch(x0, U0, own0 if op0 is None else op0, ops, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters=iters, steps=steps,
+                            tol=tol, du=du, u_prev=u_prev, kind=exp.plant_kind, u_scale=u_scale, exact=exact, gains=gains)
+
+
 class QExperiment(Experiment):
     """Closed-system plant: H0 and H1_list are d x d Hermitian (ndarray or qutip.Qobj)."""
 
@@ -252,6 +260,12 @@ class QExperiment(Experiment):
         x0 [B, n], U0 [T, m] or [B, T, m], ts_or_dt, u_scale, op0 as linearize_batch, the rest as plant_sqp_batch.  Returns its
         dict.  With collapse operators the plant is a generator plant, which is refused as it is there."""
         return _sqp_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0)
+
+    def ilqr_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters=10, steps=6, tol=1e-9, du=None, u_prev=None, u_scale=None,
+                   exact=False, gains=False, op0=None):
+        """sqp_batch with the line search run in closed loop - each QP's gains applied on this plant itself (plant_ilqr_batch):
+        the same arguments, the same dict, the same refusal of a generator plant."""
+        return _ilqr_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0)
 
 
 class LExperiment(QExperiment):
@@ -424,6 +438,12 @@ class QSynthesis(Experiment):
         """Controls optimised on the process plant itself by a Gauss-Newton SQP, for an ensemble in one device call
         (plant_sqp_batch): arguments and the returned dict as QExperiment.sqp_batch, x0 [B, d^4] process vectors."""
         return _sqp_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0)
+
+    def ilqr_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters=10, steps=6, tol=1e-9, du=None, u_prev=None, u_scale=None,
+                   exact=False, gains=False, op0=None):
+        """sqp_batch with the line search run in closed loop on the process plant (plant_ilqr_batch): arguments and the returned
+        dict as QExperiment.ilqr_batch, x0 [B, d^4] process vectors."""
+        return _ilqr_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0)
 
 
 def split_blocks(bmatrix, nrows, ncols):
