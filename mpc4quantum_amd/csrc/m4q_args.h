@@ -192,13 +192,15 @@ struct PlantQpArgs {
   M4Q_P(cplx) X_alt; M4Q_P(double) U_alt; M4Q_P(double) pin_stat; M4Q_P(int) sweep_counts;   // QP_EXACT_BOX, as QpArgs
 };
 
-// The step of the SQP on the plant itself (m4q_plant_sqp_batch; m4q_plant_sqp.h, plant_sqp.py is the definition), launched between
-// two QPs of PlantQpArgs on the same device buffers: U is that block's U (u_stride T m), X_lin its X, x0 its x_init, U_qp its U_opt.
-// iter < 0: the initial roll of clip(U0); iter >= 0: the line search of iteration iter over `steps` candidates, the member's
-// decision and the hand-over of the accepted trajectory.  status: 0 running (at the end: iterations used up), 1 converged,
-// 2 no descent, 3 the first cost was not finite; a member whose status is not 0 keeps what it has.
-struct PlantSqpArgs {
-  int B, T, kind, flags, iter, iters, steps;
+// The step of the SQP and of the iLQR on the plant itself (m4q_plant_sqp_batch, m4q_plant_ilqr_batch; m4q_plant_step.h, plant_sqp.py
+// is the definition), launched between two QPs of PlantQpArgs on the same device buffers: U is that block's U (u_stride T m), X_lin
+// its X, x0 its x_init, U_qp its U_opt, gains its gains.  iter < 0: the initial roll of clip(U0); iter >= 0: the line search of
+// iteration iter over `steps` candidates, the member's decision and the hand-over of the accepted trajectory.  closed 0: the
+// candidates are points of the line from U to U_qp (the SQP); 1: the QP's law run on the plant around the iterate (X_lin, U) (the
+// iLQR).  Like kind it picks the kernel: the launcher reads it, no kernel does.  status: 0 running (at the end: iterations used
+// up), 1 converged, 2 no descent, 3 the first cost was not finite; a member whose status is not 0 keeps what it has.
+struct PlantStepArgs {
+  int B, T, kind, flags, iter, iters, steps, closed;
   double sat, du, tol;
   M4Q_P(const double) dts;                         // the plant side, as PlantLinArgs
   M4Q_P(const cplx) x0;                            // [B][n]
@@ -210,33 +212,11 @@ struct PlantSqpArgs {
   M4Q_P(const double) U_bm; long ubm_stride;
   M4Q_P(const cplx) Q_ls; M4Q_P(const cplx) R_ls;
   M4Q_P(const double) u_prev;
-  M4Q_P(const double) U_qp;                        // [B][T][m]: the QP's U_opt
+  M4Q_P(const double) U_qp;                        // [B][T][m]: the QP's U_opt (closed: what a pinned control of the exact mode goes to)
+  M4Q_P(const cplx) gains;                         // [B][T][n + 1][m]: the QP's rows, read when closed
   M4Q_P(double) U; M4Q_P(cplx) X_lin; M4Q_P(cplx) X;                   // the iterate: [B][T][m], [B][T][n], [B][T + 1][n]
   M4Q_P(double) cost; M4Q_P(double) cost_hist; M4Q_P(double) alpha_hist;   // [B], [B][iters + 1], [B][iters]
   M4Q_P(int) n_iter; M4Q_P(int) status;            // [B]
-};
-
-// The step of the iLQR on the plant itself (m4q_plant_ilqr_batch; m4q_plant_ilqr.h, plant_ilqr.py is the definition): PlantSqpArgs'
-// place between two QPs of PlantQpArgs, its fields with its meanings, and `gains`, that block's gains [B][T][n + 1][m] - the
-// candidates are the QP's law run on the plant around the iterate (X_lin, U), not points of the line from U to U_qp.
-struct PlantIlqrArgs {
-  int B, T, kind, flags, iter, iters, steps;
-  double sat, du, tol;
-  M4Q_P(const double) dts;
-  M4Q_P(const cplx) x0;
-  M4Q_P(const double) U0; long u0_stride;
-  M4Q_P(const double) u_scale;
-  M4Q_P(const cplx) op0; long op0_stride;
-  M4Q_P(const cplx) ops; long ops_stride;
-  M4Q_P(const cplx) X_bm; long xbm_stride;
-  M4Q_P(const double) U_bm; long ubm_stride;
-  M4Q_P(const cplx) Q_ls; M4Q_P(const cplx) R_ls;
-  M4Q_P(const double) u_prev;
-  M4Q_P(const double) U_qp;                        // [B][T][m]: the QP's U_opt (what a pinned control of the exact mode goes to)
-  M4Q_P(const cplx) gains;                         // [B][T][n + 1][m]: the QP's rows
-  M4Q_P(double) U; M4Q_P(cplx) X_lin; M4Q_P(cplx) X;
-  M4Q_P(double) cost; M4Q_P(double) cost_hist; M4Q_P(double) alpha_hist;
-  M4Q_P(int) n_iter; M4Q_P(int) status;
 };
 
 // A stored feedback law closing the loop of a rollout (m4q_plant_feedback_batch, m4q_model_feedback_batch; m4q_feedback.h,
@@ -371,8 +351,7 @@ struct ShapeOps {
   int (*launch_refit_qr)(const RefitArgs&, hipStream_t);           // LDS of launch_fit
   int (*launch_plant_linearize)(const PlantLinArgs&, hipStream_t); // (the shapes of launch_plant_grad; no generator plant)
   int (*launch_plant_qp)(const PlantQpArgs&, hipStream_t);         // (square shapes that hold qp_kernel; no generator plant)
-  int (*launch_plant_sqp_step)(const PlantSqpArgs&, hipStream_t);  // (the shapes and plants of launch_plant_qp)
-  int (*launch_plant_ilqr_step)(const PlantIlqrArgs&, hipStream_t);    // (likewise)
+  int (*launch_plant_step)(const PlantStepArgs&, hipStream_t);     // (the shapes and plants of launch_plant_qp)
 };
 
 }  // namespace m4q

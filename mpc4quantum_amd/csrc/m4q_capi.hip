@@ -1548,13 +1548,9 @@ int m4q_plant_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
   return rc;
 }
 
-// m4q_plant_sqp_batch and m4q_plant_ilqr_batch are one call - refusals, staging, launches - around two step kernels: S is the
-// step's argument block (PlantSqpArgs, or PlantIlqrArgs, which also reads the QP's gains), `step` its launcher in ShapeOps
-extern "C++" {
-static void bind_gains(m4q::PlantSqpArgs&, const cplx*) {}
-static void bind_gains(m4q::PlantIlqrArgs& s, const cplx* gains) { s.gains = gains; }
-template <class S>
-static int plant_descent_batch(const char* who, const char* what, int (*m4q::ShapeOps::*step)(const S&, hipStream_t),
+// m4q_plant_sqp_batch and m4q_plant_ilqr_batch are one call - refusals, staging, launches - around one step launcher: closed
+// says which candidates the step's line search runs (PlantStepArgs)
+static int plant_descent_batch(const char* who, const char* what, int closed,
                                int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
                                const double* x0, const double* U0, int32_t u_per_instance, const double* u_scale,
                                const double* op0, const double* ops, int32_t plant_per_instance,
@@ -1598,8 +1594,8 @@ static int plant_descent_batch(const char* who, const char* what, int (*m4q::Sha
   const Extent xbm(B, bm_per_instance, (size_t)(T + 1) * n), ubm(B, bm_per_instance, (size_t)T * m);
   Stage st;
   // staged once: the plant, the targets, the weights, x0 and U0; the iterate and every workspace live on the device
-  S s{};
-  s.B = B; s.T = T; s.kind = plant_kind; s.flags = qp_flags; s.iters = iters; s.steps = steps; s.sat = sat; s.du = du; s.tol = tol;
+  m4q::PlantStepArgs s{};
+  s.B = B; s.T = T; s.kind = plant_kind; s.flags = qp_flags; s.iters = iters; s.steps = steps; s.closed = closed; s.sat = sat; s.du = du; s.tol = tol;
   s.dts = st.in<double>(dts, T);
   s.x0 = st.in<cplx>(x0, (size_t)B * n);
   s.U0 = st.in<double>(U0, eu.count); s.u0_stride = eu.stride;
@@ -1630,21 +1626,20 @@ static int plant_descent_batch(const char* who, const char* what, int (*m4q::Sha
   }
   a.X_opt = st.out<cplx>(nullptr, BT1 * n); a.U_opt = U_qp; a.cost = st.out<double>(nullptr, B);
   a.gains = st.out<cplx>(gains, BT * (n + 1) * m);          // (workspace when the caller wants no gains)
-  bind_gains(s, a.gains);                                   // (the closed-loop step runs the law the QP just wrote)
+  s.gains = a.gains;                                        // (the closed-loop step runs the law the QP just wrote)
   if (st.error()) return st.error();
   // one stream, no host synchronisation in between: the initial roll, then QP and step per iteration, then the gains' QP
   s.iter = -1;
-  int rc = (sh->*step)(s, nullptr);
+  int rc = sh->launch_plant_step(s, nullptr);
   for (int i = 0; i < iters && !rc; ++i) {
     rc = sh->launch_plant_qp(a, nullptr);
     if (rc) break;
     s.iter = i;
-    rc = (sh->*step)(s, nullptr);
+    rc = sh->launch_plant_step(s, nullptr);
   }
   if (!rc && gains) rc = sh->launch_plant_qp(a, nullptr);
   return st.finish(rc, what);
 }
-}  // extern "C++"
 
 int m4q_plant_sqp_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
                         const double* x0, const double* U0, int32_t u_per_instance, const double* u_scale,
@@ -1653,10 +1648,9 @@ int m4q_plant_sqp_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_k
                         const double* Q_ls, const double* R_ls, const double* u_prev, int32_t iters, int32_t steps, double tol,
                         double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
                         double* gains) {
-  return plant_descent_batch<m4q::PlantSqpArgs>("m4q_plant_sqp_batch", "plant sqp", &m4q::ShapeOps::launch_plant_sqp_step, B, dim_x, dim_u,
-                                                plant_kind, T, dts, x0, U0, u_per_instance, u_scale, op0, ops, plant_per_instance, qp_flags,
-                                                sat, du, X_bm, U_bm, bm_per_instance, Q_ls, R_ls, u_prev, iters, steps, tol, X, U, cost,
-                                                cost_hist, alpha_hist, n_iter, status, gains);
+  return plant_descent_batch("m4q_plant_sqp_batch", "plant sqp", /*closed=*/0, B, dim_x, dim_u, plant_kind, T, dts, x0, U0, u_per_instance,
+                             u_scale, op0, ops, plant_per_instance, qp_flags, sat, du, X_bm, U_bm, bm_per_instance, Q_ls, R_ls, u_prev, iters,
+                             steps, tol, X, U, cost, cost_hist, alpha_hist, n_iter, status, gains);
 }
 
 int m4q_plant_ilqr_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
@@ -1666,10 +1660,9 @@ int m4q_plant_ilqr_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_
                          const double* Q_ls, const double* R_ls, const double* u_prev, int32_t iters, int32_t steps, double tol,
                          double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
                          double* gains) {
-  return plant_descent_batch<m4q::PlantIlqrArgs>("m4q_plant_ilqr_batch", "plant ilqr", &m4q::ShapeOps::launch_plant_ilqr_step, B, dim_x, dim_u,
-                                                 plant_kind, T, dts, x0, U0, u_per_instance, u_scale, op0, ops, plant_per_instance, qp_flags,
-                                                 sat, du, X_bm, U_bm, bm_per_instance, Q_ls, R_ls, u_prev, iters, steps, tol, X, U, cost,
-                                                 cost_hist, alpha_hist, n_iter, status, gains);
+  return plant_descent_batch("m4q_plant_ilqr_batch", "plant ilqr", /*closed=*/1, B, dim_x, dim_u, plant_kind, T, dts, x0, U0, u_per_instance,
+                             u_scale, op0, ops, plant_per_instance, qp_flags, sat, du, X_bm, U_bm, bm_per_instance, Q_ls, R_ls, u_prev, iters,
+                             steps, tol, X, U, cost, cost_hist, alpha_hist, n_iter, status, gains);
 }
 
 int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* u,

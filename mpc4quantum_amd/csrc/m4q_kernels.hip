@@ -2178,10 +2178,9 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_qp_kernel(PlantQpArgs a) {
   }
 }
 
-// plant_sqp_step_kernel: the line search, the decision and the hand-over between two of these QPs (m4q_plant_sqp_batch)
-#include "m4q_plant_sqp.h"
-// plant_ilqr_step_kernel: the same place with a closed-loop forward pass - the QP's gains run on the plant (m4q_plant_ilqr_batch)
-#include "m4q_plant_ilqr.h"
+// plant_step_kernel: the line search, the decision and the hand-over between two of these QPs, over points of the line to the QP's
+// optimum (m4q_plant_sqp_batch) or in closed loop - the QP's gains run on the plant (m4q_plant_ilqr_batch)
+#include "m4q_plant_step.h"
 #endif  // M4Q_NO_AUX
 
 // ---------------------------------------------------------------------------------------------
@@ -2675,36 +2674,26 @@ static int launch_plant_qp(const PlantQpArgs& a, hipStream_t s) {
     return UNBUILT;
   }
 }
-// the step between two of them (m4q_plant_sqp.h): launch_aux's launch over quads of members, the rollouts' LDS
-static int launch_plant_sqp_step(const PlantSqpArgs& a, hipStream_t s) {
+// the step between two of them (m4q_plant_step.h): launch_aux's launch over quads of members, the rollouts' LDS
+template <bool CLOSED>
+static int launch_plant_step_of(const PlantStepArgs& a, hipStream_t s) {
   if constexpr (!SQUARE) {
     return UNBUILT;
   } else {
     constexpr size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
-    if (a.kind == PLANT_HAMILTONIAN) return launch_aux(plant_sqp_step_kernel<PLANT_HAMILTONIAN>, a, lds, s);
+    if (a.kind == PLANT_HAMILTONIAN) return launch_aux(plant_step_kernel<PLANT_HAMILTONIAN, CLOSED>, a, lds, s);
     if constexpr (QUARTIC) {
-      if (a.kind == PLANT_PROCESS) return launch_aux(plant_sqp_step_kernel<PLANT_PROCESS>, a, lds, s);
+      if (a.kind == PLANT_PROCESS) return launch_aux(plant_step_kernel<PLANT_PROCESS, CLOSED>, a, lds, s);
     }
     return UNBUILT;
   }
 }
-// ... and its closed-loop form (m4q_plant_ilqr.h): the same launch
-static int launch_plant_ilqr_step(const PlantIlqrArgs& a, hipStream_t s) {
-  if constexpr (!SQUARE) {
-    return UNBUILT;
-  } else {
-    constexpr size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
-    if (a.kind == PLANT_HAMILTONIAN) return launch_aux(plant_ilqr_step_kernel<PLANT_HAMILTONIAN>, a, lds, s);
-    if constexpr (QUARTIC) {
-      if (a.kind == PLANT_PROCESS) return launch_aux(plant_ilqr_step_kernel<PLANT_PROCESS>, a, lds, s);
-    }
-    return UNBUILT;
-  }
+static int launch_plant_step(const PlantStepArgs& a, hipStream_t s) {
+  return a.closed ? launch_plant_step_of<true>(a, s) : launch_plant_step_of<false>(a, s);
 }
 #else
 static int launch_plant_qp(const PlantQpArgs&, hipStream_t) { return UNBUILT; }
-static int launch_plant_sqp_step(const PlantSqpArgs&, hipStream_t) { return UNBUILT; }
-static int launch_plant_ilqr_step(const PlantIlqrArgs&, hipStream_t) { return UNBUILT; }
+static int launch_plant_step(const PlantStepArgs&, hipStream_t) { return UNBUILT; }
 #endif
 
 #if !defined(M4Q_NO_AUX) && M4Q_ORDER <= 2
@@ -2739,7 +2728,7 @@ static const ShapeOps* shape_ops() {
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
                                ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr,
                                launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr, launch_plant_linearize, launch_plant_qp,
-                               launch_plant_sqp_step, launch_plant_ilqr_step};
+                               launch_plant_step};
   return &ops;
 }
 

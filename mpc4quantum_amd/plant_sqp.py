@@ -20,6 +20,8 @@ u_scale * u:
 
 a_j is a power of two, so U + a_j D is one rounding (an fma on the device).  gains=True: one more linearisation and QP at the final
 (X[:T], U), whatever the status; its gains are returned."""
+from types import SimpleNamespace
+
 import numpy as np
 
 from . import _lib
@@ -63,11 +65,13 @@ def _clip(U, lo, hi):
     return np.minimum(np.maximum(U, lo), hi)
 
 
-def plant_sqp_reference(x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, iters=10, steps=6, tol=1e-9, du=None, u_prev=None,
-                        kind=_lib.PLANT_HAMILTONIAN, u_scale=None, exact=False, gains=False, trace=None):
-    """The definition of plant_sqp_batch (same arguments), on the host: the module's loop, member by member, on
-    plant_quad_program_reference's pieces and feedback._plant_step.  trace: a list that receives one dict per (member, iteration) -
-    "b", "i", "J" and "U" (the cost and the controls before), "U_qp", "Js" and "Us" (the candidates' costs and controls): what the decisions were taken on."""
+def _descent_reference(candidate, x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, kind, u_scale,
+                       exact, gains, trace):
+    """The module's loop, member by member, on plant_quad_program_reference's pieces and feedback._plant_step: the one definition
+    of plant_sqp_reference and plant_ilqr_reference - the first guess, the tie rule, the tol rule, the statuses, the histories and
+    the gains' QP.  candidate(mem, a, X, U, U_qp, rows) -> (X_j, U_j, J_j) is the candidate of step length a at the iterate (X, U),
+    given what the QP there returned; mem holds the member: T, n, m, exact, x0, Xb, Ub, lo, hi, step(x, u, t) (one plant step under
+    u_scale * u), cost(X, U) and roll(U) -> (X, J)."""
     (x0, U0, u_per, u_scale, op0, ops, per, dts, kind, X_bm, U_bm, bm_per, Q_ls, R_ls, band, u_prev, iters, steps,
      tol) = _sqp_common(x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, kind, u_scale)
     B, n = x0.shape
@@ -86,34 +90,39 @@ def plant_sqp_reference(x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat,
         if band:
             lo[0], hi[0] = np.maximum(lo[0], u_prev[b] - du), np.minimum(hi[0], u_prev[b] + du)
 
+        def step(x, u, t):
+            return _plant_step(kind, x, sc * u, H0, Hs, dts[t])
+
+        def cost(X, U):
+            with np.errstate(all="ignore"):
+                return _objective(X, U, Xb, Ub, Q_ls, R_ls)
+
         def roll(U):
             X = np.empty((T + 1, n), dtype=np.complex128)
             X[0] = x0[b]
             for t in range(T):
-                X[t + 1] = _plant_step(kind, X[t], sc * U[t], H0, Hs, dts[t])
-            with np.errstate(all="ignore"):
-                return X, _objective(X, U, Xb, Ub, Q_ls, R_ls)
+                X[t + 1] = step(X[t], U[t], t)
+            return X, cost(X, U)
 
         def qp(X, U):
             A, Bm, D = _reference_points(X[None, :T], U[None], 1, sc[None], H0[None], Hs[None], 1, dts, kind)
             return solve(x0[b], Xb, Ub, Q_ls, R_ls, A[0], Bm[0], D[0], lo, hi)
 
+        mem = SimpleNamespace(T=T, n=n, m=m, exact=exact, x0=x0[b], Xb=Xb, Ub=Ub, lo=lo, hi=hi, step=step, cost=cost, roll=roll)
         U = _clip(u0[b if u_per else 0], lo, hi)
         X, J = roll(U)
         hist = [J]
         status = STATUS_ITERS if np.isfinite(J) else STATUS_NOT_FINITE
         if status == STATUS_ITERS:
             for i in range(iters):
-                U_qp = qp(X, U)[1]
-                D = U_qp - U
+                _, U_qp, _, rows = qp(X, U)
                 best = None
                 rec = dict(b=b, i=i, J=J, U=U, U_qp=U_qp, Js=[], Us=[])
                 if trace is not None:
                     trace.append(rec)
                 for j in range(steps):
                     a = 0.5 ** j
-                    Uj = _clip(U + a * D, lo, hi)
-                    Xj, Jj = roll(Uj)
+                    Xj, Uj, Jj = candidate(mem, a, X, U, U_qp, rows)
                     rec["Js"].append(Jj)
                     rec["Us"].append(Uj)
                     if np.isfinite(Jj) and (best is None or Jj < best[0]):
@@ -136,6 +145,43 @@ def plant_sqp_reference(x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat,
     return out
 
 
+def _descent_batch(entry, x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, kind, u_scale, exact,
+                   gains):
+    """plant_sqp_batch and plant_ilqr_batch: one staging of one argument list around the C entry point named `entry`."""
+    (x0, U0, u_per, u_scale, op0, ops, per, dts, kind, X_bm, U_bm, bm_per, Q_ls, R_ls, band, u_prev, iters, steps,
+     tol) = _sqp_common(x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, kind, u_scale)
+    B, n = x0.shape
+    T, m = U0.shape[-2:]
+    flags = (_lib.QP_DU_BAND if band else 0) | (_lib.QP_EXACT_BOX if exact else 0)
+    out = {"X": np.empty((B, T + 1, n), dtype=np.complex128), "U": np.empty((B, T, m), dtype=np.float64),
+           "cost": np.empty(B, dtype=np.float64), "cost_hist": np.empty((B, iters + 1), dtype=np.float64),
+           "alpha_hist": np.empty((B, iters), dtype=np.float64), "n_iter": np.empty(B, dtype=np.int32),
+           "status": np.empty(B, dtype=np.int32), "gains": np.empty((B, T, n + 1, m), dtype=np.complex128) if gains else None}
+    ip = lambda a: a.ctypes.data_as(_lib._ip)
+    call = getattr(_lib.lib(), entry)
+    _lib.check(call(B, n, m, kind, T, _ptr(dts), _ptr(x0), _ptr(U0), u_per, _ptr(u_scale), _ptr(op0), _ptr(ops), per, int(flags),
+                    float(sat), float(du if band else 0.0), _ptr(X_bm), _ptr(U_bm), bm_per, _ptr(Q_ls), _ptr(R_ls), _ptr(u_prev), iters,
+                    steps, tol, _ptr(out["X"]), _ptr(out["U"]), _ptr(out["cost"]), _ptr(out["cost_hist"]), _ptr(out["alpha_hist"]),
+                    ip(out["n_iter"]), ip(out["status"]), _ptr(out["gains"])))
+    return out
+
+
+def _on_the_line(mem, a, X, U, U_qp, rows):
+    """The SQP's candidate: the point clip(U + a (U_qp - U)) of the line to the QP's optimum, rolled in open loop."""
+    Uj = _clip(U + a * (U_qp - U), mem.lo, mem.hi)
+    Xj, Jj = mem.roll(Uj)
+    return Xj, Uj, Jj
+
+
+def plant_sqp_reference(x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, iters=10, steps=6, tol=1e-9, du=None, u_prev=None,
+                        kind=_lib.PLANT_HAMILTONIAN, u_scale=None, exact=False, gains=False, trace=None):
+    """The definition of plant_sqp_batch (same arguments), on the host: the module's loop, member by member, on
+    plant_quad_program_reference's pieces and feedback._plant_step.  trace: a list that receives one dict per (member, iteration) -
+    "b", "i", "J" and "U" (the cost and the controls before), "U_qp", "Js" and "Us" (the candidates' costs and controls): what the decisions were taken on."""
+    return _descent_reference(_on_the_line, x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, kind,
+                              u_scale, exact, gains, trace)
+
+
 def plant_sqp_batch(x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, iters=10, steps=6, tol=1e-9, du=None, u_prev=None,
                     kind=_lib.PLANT_HAMILTONIAN, u_scale=None, exact=False, gains=False):
     """A Gauss-Newton SQP on the plant's own dynamics for B members in ONE device call (m4q_plant_sqp_batch): up to `iters` times
@@ -149,20 +195,5 @@ def plant_sqp_batch(x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, ite
     "cost_hist" [B, iters + 1], "alpha_hist" [B, iters], "n_iter" [B] and "status" [B] int32 (0 iterations used up, 1 converged,
     2 no candidate lowered the cost, 3 the first cost was not finite), "gains" [B, T, n + 1, m] (the QP's at the returned point) or
     None."""
-    (x0, U0, u_per, u_scale, op0, ops, per, dts, kind, X_bm, U_bm, bm_per, Q_ls, R_ls, band, u_prev, iters, steps,
-     tol) = _sqp_common(x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, kind, u_scale)
-    B, n = x0.shape
-    T, m = U0.shape[-2:]
-    flags = (_lib.QP_DU_BAND if band else 0) | (_lib.QP_EXACT_BOX if exact else 0)
-    out = {"X": np.empty((B, T + 1, n), dtype=np.complex128), "U": np.empty((B, T, m), dtype=np.float64),
-           "cost": np.empty(B, dtype=np.float64), "cost_hist": np.empty((B, iters + 1), dtype=np.float64),
-           "alpha_hist": np.empty((B, iters), dtype=np.float64), "n_iter": np.empty(B, dtype=np.int32),
-           "status": np.empty(B, dtype=np.int32), "gains": np.empty((B, T, n + 1, m), dtype=np.complex128) if gains else None}
-    ip = lambda a: a.ctypes.data_as(_lib._ip)
-    L = _lib.lib()
-    _lib.check(L.m4q_plant_sqp_batch(B, n, m, kind, T, _ptr(dts), _ptr(x0), _ptr(U0), u_per, _ptr(u_scale), _ptr(op0), _ptr(ops), per,
-                                     int(flags), float(sat), float(du if band else 0.0), _ptr(X_bm), _ptr(U_bm), bm_per, _ptr(Q_ls),
-                                     _ptr(R_ls), _ptr(u_prev), iters, steps, tol, _ptr(out["X"]), _ptr(out["U"]), _ptr(out["cost"]),
-                                     _ptr(out["cost_hist"]), _ptr(out["alpha_hist"]), ip(out["n_iter"]), ip(out["status"]),
-                                     _ptr(out["gains"])))
-    return out
+    return _descent_batch("m4q_plant_sqp_batch", x0, U0, op0, ops, dt_or_ts, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev,
+                          kind, u_scale, exact, gains)

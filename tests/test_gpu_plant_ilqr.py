@@ -1,4 +1,4 @@
-"""The iLQR on the plant itself in one device call (m4q_plant_ilqr_batch: plant_ilqr_step_kernel between the two kernels of
+"""The iLQR on the plant itself in one device call (m4q_plant_ilqr_batch: plant_step_kernel<PLANT, true> between the two kernels of
 launch_plant_qp) against the NumPy / SciPy definition of mpc4quantum_amd/plant_ilqr.py, which tests/test_plant_ilqr_host.py holds to
 itself and to its neighbours; bit for bit against chained calls (the in-place hand-over of the iterate), the rollout and the
 one-call QP; placement; against the stored law of plant_feedback_batch and against plant_sqp_batch where the two must agree; the

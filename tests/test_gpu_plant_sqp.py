@@ -1,4 +1,4 @@
-"""The SQP on the plant itself in one device call (m4q_plant_sqp_batch: plant_sqp_step_kernel between the two kernels of
+"""The SQP on the plant itself in one device call (m4q_plant_sqp_batch: plant_step_kernel<PLANT, false> between the two kernels of
 launch_plant_qp) against the NumPy / SciPy definition of mpc4quantum_amd/plant_sqp.py, which tests/test_plant_sqp_host.py holds to
 the gradient and to its own fixed points; bit for bit against chained calls, the rollout and the one-call QP; placement; the second
 trip of the grid; a converged start; refusals.  Cases, margins and the recorded amplification: tests/plant_sqp_cases.py.  Every

@@ -20,7 +20,7 @@ wall     the whole call as a caller sees it (host clock around calls that end in
          compared first (statuses, accepted step lengths, costs), then the ensemble means of the cost histories of the iLQR and
          of the SQP are printed side by side.
 kernels  one fused call, clipped, at the first count of --iters, for a run under rocprofv3 --kernel-trace --stats (a run of its
-         own): plant_factor_kernel, plant_qp_kernel and plant_ilqr_step_kernel per iteration."""
+         own): plant_factor_kernel, plant_qp_kernel and plant_step_kernel<PLANT, true> per iteration."""
 import argparse
 import os
 import sys

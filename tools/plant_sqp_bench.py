@@ -17,7 +17,7 @@ wall     the whole call as a caller sees it - staging in, the launches, the copy
          maximum.  The two are compared first: statuses, accepted step lengths, largest difference of the costs; then the ensemble
          means of the cost history and the split of the statuses are printed.
 kernels  one fused call, clipped, at the first count of --iters, for a run under rocprofv3 --kernel-trace --stats (a run of its
-         own): plant_factor_kernel, plant_qp_kernel and plant_sqp_step_kernel per iteration."""
+         own): plant_factor_kernel, plant_qp_kernel and plant_step_kernel<PLANT, false> per iteration."""
 import argparse
 import os
 import sys
