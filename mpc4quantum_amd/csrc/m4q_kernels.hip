@@ -183,7 +183,7 @@ constexpr size_t mpc_lds_layout_bytes() {
   constexpr int N = TL ? NX - 1 : NX;
   return sizeof(S) * (size_t)(model_lds_elems<N, SG>() + cost_elems<N>() + (cost_transposed<S, N, EXACT>() ? 2 * N * N : 0)) +
          sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS) + sizeof(double) * (size_t)WLS_DOUBLES + (size_t)stash_bytes<S, SG>() +
-         (TILE ? (size_t)TILE_LDS_BYTES : 0) + (exact_tile<S, TL, EXACT>() ? (size_t)(TILE_LDS_BYTES + TILE_PIN_LDS_BYTES) : 0);
+         (TILE ? (size_t)(TILE_LDS_BYTES + tile_opnd::bytes(NU, (N + 3) / 4)) : 0) + (exact_tile<S, TL, EXACT>() ? (size_t)(TILE_LDS_BYTES + TILE_PIN_LDS_BYTES) : 0);
 }
 
 __device__ __forceinline__ int row_bcast_int(int v) { return __shfl(v, 0, 16); }
@@ -339,6 +339,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
   volatile M4Q_LDS double* tgb = stash.xm + 64 * 2;
   volatile M4Q_LDS int* tiw = (volatile M4Q_LDS int*)(tgb + ROWS * TILE_GB_DOUBLES);
   volatile M4Q_LDS double* tpin = (volatile M4Q_LDS double*)(tiw + ROWS * TILE_IO_WORDS);      // (exact_tile kernels only)
+  volatile M4Q_LDS double* timg = (volatile M4Q_LDS double*)(tiw + ROWS * TILE_IO_WORDS);      // (TILE: the sweep's operand image, m4q_tile_opnd.h)
   int T0, flags;
   bool ls_diag, two_phase;
   int n_pieces;                // work items per instance: head [step_begin, 2), then [2, XCUTS[0]), ... , [.., step_end)
@@ -721,7 +722,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
           ts.R = reinterpret_cast<const double*>(cost.R);
           ts.gb = tgb + mb * TILE_GB_DOUBLES;
           M4Q_PHASE_MARK(3)
-          ts.backward((tfl & 1) != 0);
+          ts.backward((tfl & 1) != 0, timg);
           wave_sync();
           M4Q_PHASE_MARK(1)
         }
@@ -2309,6 +2310,9 @@ struct LaunchOp {
   template <class S, int PLANT, bool EXACT, bool TL, bool TILE, bool SG = false>
   int run() const {
     const size_t lds = mpc_lds_layout_bytes<S, TL, TILE, EXACT, SG>();
+    // (the tile kernels run two wavefronts per SIMD, eight workgroups per CU: an eighth of the CU's 160 KB each - with more, the launch
+    //  runs on fewer wavefronts than the grid has)
+    static_assert(!TILE || mpc_lds_layout_bytes<S, TL, TILE, EXACT, SG>() <= 20480, "tile kernel: eight workgroups per CU");
     int rc = prep_lds(mpc_kernel<S, PLANT, EXACT, TL, TILE, SG>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((mpc_kernel<S, PLANT, EXACT, TL, TILE, SG>), dim3(grid), dim3(64), lds, s, a);

@@ -12,11 +12,17 @@
 //     UG, UB  the controls / control targets of time t0 - q (the m-tuple, one 16-byte load each at m = 2)
 // 4 loads per 4 indices instead of 16, six doubles per lane per block, fetched a whole block (4-7 indices) ahead.  The products
 // N_s x_g of the four indices are ONE product per (s, I, K) - B_s[I] = sum_K mm(N_s^T[K][I], XT[K]) has column q = time t0 - q -
-// instead of one per index (8 -> 2 MFMAs per index), and an index takes its own column, and its own controls, with quad-permute
-// moves (v_mov_b32_dpp quad_perm:[j,j,j,j]: 32-bit VALU, not the fp64 pipe).
+// instead of one per index (8 -> 2 MFMAs per index), and an index takes its own column, and its own controls,
+//   * in the clipped sweep from an LDS image of the block's tiles (m4q_tile_opnd.h): the wavefront writes B_s[I], the affine column
+//     and the controls as they are, one ds_write_b64 per tile, and every index reads W = [B | c | 0], b, c and u_g with one
+//     ds_read_b64 per operand, the index an immediate offset.  The sweep is bound by VALU issue and the LDS is idle: the reads cost
+//     no issue slot there (config 3 27.75 -> 27.19 ms, bit-identical; profiles/r09_ab_experiments.txt);
+//   * in the pinned sweep with quad-permute moves (v_mov_b32_dpp quad_perm:[j,j,j,j]) and three q-selects per tile of W: 32-bit
+//     VALU, not the fp64 pipe (what the clipped sweep did before the image: 16 moves and 12 selects per index at n = 8, m = 2).
 // Arithmetic, lane map and gains layout as m4q_tile.h (read its header first).  Order-1 libraries.
 #pragma once
 #include "m4q_tile.h"
+#include "m4q_tile_opnd.h"
 
 namespace m4q {
 
@@ -105,7 +111,8 @@ struct TileBackwardB {
     return b;
   }
 
-  __device__ __forceinline__ void backward(bool store_ok) {
+  // img: LDS, the wavefront's operand image (m4q_tile_opnd.h; the clipped sweep only)
+  __device__ __forceinline__ void backward(bool store_ok, volatile __attribute__((address_space(3))) double* img = nullptr) {
     {
       // the lane's addresses as values of THIS sweep: as the kernel-long values they are, the register allocator spills them and
       // reloads them at every use inside the horizon loop
@@ -168,12 +175,30 @@ struct TileBackwardB {
       for (int l = 0; l < NU; ++l) Rm[s][l] = to_sgpr(R[s * NU + l]);
     const double satu = to_sgpr(sat);
     const int kr_src = 4 * (((int)threadIdx.x & ~3) | ((int)threadIdx.x >> 4));     // byte address of lane (r, member, q' = r)
+    // The clipped sweep spreads a block's operands through the LDS image of m4q_tile_opnd.h: iw, where this lane writes its double of a
+    // tile; ir, where it reads its column of W = [B | c | 0]; ib, where it reads what is replicated over q.  LDS operations of one
+    // wavefront execute in order and the accesses are volatile: a block's writes, then its reads, no barrier.  The zero tiles are
+    // written here, once per sweep.
+    namespace opnd = tile_opnd;
+    constexpr bool IMG = !PINNED;
+    volatile __attribute__((address_space(3))) double* iw = img;
+    volatile __attribute__((address_space(3))) double* ir = img;
+    volatile __attribute__((address_space(3))) double* ib = img;
+    if constexpr (IMG) {
+      iw += opnd::write_addr((int)threadIdx.x) / 8;
+      ir += opnd::w_addr(NU, (int)threadIdx.x) / 8;
+      ib += opnd::bcast_addr((int)threadIdx.x) / 8;
+      asm volatile("" : "+v"(iw), "+v"(ir), "+v"(ib));
+#pragma unroll
+      for (int K = 0; K < NT; ++K) iw[opnd::write_imm(opnd::tile_zero(NU, K)) / 8] = 0.0;
+    }
 
-    // one horizon index; ug / ub: its controls and control targets, b: rowrep(N_s x_g), all replicated over the member's lanes.
+    // one horizon index; ug / ub: its controls and control targets, b: rowrep(N_s x_g), all replicated over the member's lanes;
+    // Win (IMG): W = [B | c | 0], read from the image by the caller an index ahead.
     // LAST (a std::bool_constant): the index is t = 0 - the sweep ends with its gain stores: the cost-to-go of index 0 (S, P S, w,
     // R K, Kr, the new P and p: 28 of the index's 44 MFMAs in the MFMA form) is read by nothing, backward() returns no value
     auto step = [&](auto last, int t, const double (&ug)[NU], const double (&ub)[NU], const double (&b)[NU][NT],
-                    const double (&stv)[NU], const double (&cin)[NT]) __attribute__((always_inline)) {
+                    const double (&stv)[NU], const double (&cin)[NT], const double (&Win)[IMG ? NT : 1]) __attribute__((always_inline)) {
       constexpr bool LAST = decltype(last)::value;
       double At[NT][NT], c[NT], W[NT], Y[NT], H[NT];
 #pragma unroll
@@ -189,10 +214,14 @@ struct TileBackwardB {
       for (int K = 0; K < NT; ++K) {
         const double a = cin[K];                                                // (formed for the block's four indices at once: block())
         c[K] = a;
-        double w = isq[NU] ? a : 0.0;                                           // W = [B | c | 0]
+        if constexpr (IMG) {
+          W[K] = Win[K];
+        } else {
+          double w = isq[NU] ? a : 0.0;                                         // W = [B | c | 0]
 #pragma unroll
-        for (int s = 0; s < NU; ++s) w = isq[s] ? b[s][K] : w;
-        W[K] = w;
+          for (int s = 0; s < NU; ++s) w = isq[s] ? b[s][K] : w;
+          W[K] = w;
+        }
       }
 #pragma unroll
       for (int I = 0; I < NT; ++I) {
@@ -415,24 +444,60 @@ struct TileBackwardB {
         for (int s = 0; s < NU; ++s) a = fma(BT[s][K], cur.ub[s] - cur.ug[s], a);
         CT[K] = a;
       }
+      // IMG: the block's tiles go to the image as they are, one ds_write_b64 each, and every index reads its operands from there
+      // (ds_read_b64 with the index as an immediate) instead of selecting and moving them between lanes on the vector port: per
+      // index 16 v_mov_b32_dpp and 12 v_cndmask_b32 less at n = 8, m = 2, and BT, CT and the block's controls are dead from here.
+      // W, the first operand of an index, is read one index ahead; u_g, b and c at the start of their index.
+      double Wn[NT];
+      if constexpr (IMG) {
+#pragma unroll
+        for (int K = 0; K < NT; ++K) {
+#pragma unroll
+          for (int s = 0; s < NU; ++s) iw[opnd::write_imm(opnd::tile_b(NU, s, K)) / 8] = BT[s][K];
+          iw[opnd::write_imm(opnd::tile_c(NU, K)) / 8] = CT[K];
+        }
+#pragma unroll
+        for (int p = 0; p < NU; ++p) iw[opnd::write_imm(opnd::tile_u(NU, NT, p)) / 8] = cur.ug[p];
+#pragma unroll
+        for (int K = 0; K < NT; ++K) Wn[K] = ir[opnd::w_imm(NU, K, 0) / 8];
+      }
       static_for<0, 4>([&](auto jj) {
         constexpr int j = decltype(jj)::value;
         if (j < cnt) {
-          double ug[NU], ub[NU], b[NU][NT], stv[NU], cin[NT];
+          double ug[NU], ub[NU], b[NU][NT], stv[NU], cin[NT], Win[IMG ? NT : 1];
+          if constexpr (IMG) {
 #pragma unroll
-          for (int s = 0; s < NU; ++s) {
-            ug[s] = quad_bcast<j>(cur.ug[s]);
-            ub[s] = PINNED ? quad_bcast<j>(cur.ub[s]) : 0.0;
-            stv[s] = PINNED ? quad_bcast<j>(cur.st[s]) : 0.0;
+            for (int s = 0; s < NU; ++s) {
+              ug[s] = ib[opnd::bcast_imm(opnd::tile_u(NU, NT, s), j) / 8];
+              ub[s] = 0.0;
+              stv[s] = 0.0;
+            }
 #pragma unroll
-            for (int I = 0; I < NT; ++I) b[s][I] = quad_bcast<j>(BT[s][I]);
+            for (int s = 0; s < NU; ++s)
+#pragma unroll
+              for (int I = 0; I < NT; ++I) b[s][I] = ib[opnd::bcast_imm(opnd::tile_b(NU, s, I), j) / 8];
+#pragma unroll
+            for (int K = 0; K < NT; ++K) {
+              cin[K] = ib[opnd::bcast_imm(opnd::tile_c(NU, K), j) / 8];
+              Win[K] = Wn[K];
+              if constexpr (j < 3) Wn[K] = ir[opnd::w_imm(NU, K, j + 1) / 8];
+            }
+          } else {
+#pragma unroll
+            for (int s = 0; s < NU; ++s) {
+              ug[s] = quad_bcast<j>(cur.ug[s]);
+              ub[s] = PINNED ? quad_bcast<j>(cur.ub[s]) : 0.0;
+              stv[s] = PINNED ? quad_bcast<j>(cur.st[s]) : 0.0;
+#pragma unroll
+              for (int I = 0; I < NT; ++I) b[s][I] = quad_bcast<j>(BT[s][I]);
+            }
+#pragma unroll
+            for (int K = 0; K < NT; ++K) cin[K] = quad_bcast<j>(CT[K]);
           }
-#pragma unroll
-          for (int K = 0; K < NT; ++K) cin[K] = quad_bcast<j>(CT[K]);
-          if constexpr (!FIN) step(std::false_type{}, tb - j, ug, ub, b, stv, cin);
-          else if constexpr (j == 3) step(std::true_type{}, tb - j, ug, ub, b, stv, cin);          // (j < cnt: cnt == 4)
-          else if (j == cnt - 1) step(std::true_type{}, tb - j, ug, ub, b, stv, cin);               // (wave-uniform)
-          else step(std::false_type{}, tb - j, ug, ub, b, stv, cin);
+          if constexpr (!FIN) step(std::false_type{}, tb - j, ug, ub, b, stv, cin, Win);
+          else if constexpr (j == 3) step(std::true_type{}, tb - j, ug, ub, b, stv, cin, Win);          // (j < cnt: cnt == 4)
+          else if (j == cnt - 1) step(std::true_type{}, tb - j, ug, ub, b, stv, cin, Win);               // (wave-uniform)
+          else step(std::false_type{}, tb - j, ug, ub, b, stv, cin, Win);
         }
       });
     };
