@@ -359,6 +359,22 @@ struct IdxRowsum {            // acc[0] += lane_q(a[0]) * b[0]
   static constexpr int b(int) { return 0; }
   static constexpr int lane(int q) { return q; }
 };
+template <int L0>
+struct IdxDotLaneFrom {       // acc[0] += lane_{L0+q}(a[0]) * b[q]   (the vector sits in lanes L0 .. of the row: m4q_rollout_pair.h)
+  static constexpr int distinct = 1;
+  static constexpr int acc(int) { return 0; }
+  static constexpr int a(int) { return 0; }
+  static constexpr int b(int q) { return q; }
+  static constexpr int lane(int q) { return L0 + q; }
+};
+template <int L0>
+struct IdxRowsumFrom {        // acc[0] += lane_{L0+q}(a[0]) * b[0]
+  static constexpr int distinct = 1;
+  static constexpr int acc(int) { return 0; }
+  static constexpr int a(int) { return 0; }
+  static constexpr int b(int) { return 0; }
+  static constexpr int lane(int q) { return L0 + q; }
+};
 template <int K>
 struct IdxSameLane {          // acc[q] += lane_K(a[q]) * b[0]
   static constexpr int distinct = 1 << 20;
@@ -434,6 +450,23 @@ __device__ __forceinline__ double rowsum(double v) {
   double c1[1] = {0.0};
   const double a1[1] = {v}, b1[1] = {1.0};
   emit_terms<IdxRowsum, false, false, true, 0, N>(c1, a1, b1);
+  return c1[0];
+}
+// The same two sums over lanes L0 .. L0+N-1 of the row (same terms in the same order; result in every lane of the row).
+template <int L0, int N>
+__device__ __forceinline__ double dot_lane_index_from(double v, const double (&m)[N]) {
+  static_assert(L0 >= 0 && L0 + N <= 16, "source lanes inside the row");
+  double c1[1] = {0.0};
+  const double a1[1] = {v};
+  emit_terms<IdxDotLaneFrom<L0>, false, false, true, 0, N>(c1, a1, m);
+  return c1[0];
+}
+template <int L0, int N>
+__device__ __forceinline__ double rowsum_from(double v) {
+  static_assert(L0 >= 0 && L0 + N <= 16, "source lanes inside the row");
+  double c1[1] = {0.0};
+  const double a1[1] = {v}, b1[1] = {1.0};
+  emit_terms<IdxRowsumFrom<L0>, false, false, true, 0, N>(c1, a1, b1);
   return c1[0];
 }
 template <int N>

@@ -732,7 +732,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
         // form - tools/tile_rollout_r04.h - the same SIMD time at d = 3 and 14 % more of the launch at d = 2)
         // (idle lanes sit it out as in the DPP kernels: MASK_IDLE itself is off for TILE because the tile sweep needs all 64 lanes)
         constexpr bool MASK_FWD = NS < 16;
-        if (!MASK_FWD || lane_ok)         // (the tile path runs with a constant target only)
+        // (n = 8: two indices per trip on the two halves of the row, all 16 lanes in - rollout_forward_pair, m4q_mpc.h)
+        if constexpr (rollout_pair_form<S, NS, NU, false, true, Prov>())
+          chk = rollout_forward_pair<NS, NU>(prov, T, x_cur, win, flags, gains, sat, lo0, hi0, Xo, Uo, jj, running, uapp, !use_ls, Xg, Ug);
+        else if (!MASK_FWD || lane_ok)         // (the tile path runs with a constant target only)
           chk = rollout_forward<S, NS, NU, false, true>(prov, T, x_cur, win, cost, flags, gains, sat, lo0, hi0, Xo, Uo, j, st, uapp, !use_ls, &Xg, &Ug);
         if constexpr (MASK_FWD) {
           chk = bcast<0>(chk);
@@ -756,7 +759,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
         wave_sync();
         issue_prio<PRIO_ON && PRIO.rollout != PRIO.sweep, PRIO.rollout>();
         M4Q_PHASE_MARK(1)
-        if constexpr (HAS_TC) {
+        if constexpr (HAS_TC && rollout_pair_form<S, NS, NU, false, true, Prov>()) {
+          if (tc)           // (the pair form takes all 16 lanes of the row)
+            chk = rollout_forward_pair<NS, NU>(prov, T, x_cur, win, flags, gains, sat, lo0, hi0, Xo, Uo, jj, running, uapp, !use_ls, Xg, Ug);
+        } else if constexpr (HAS_TC) {
           if (tc && (!MASK_IDLE || lane_ok))
             chk = rollout_forward<S, NS, NU, false, true>(prov, T, x_cur, win, cost, flags, gains, sat, lo0, hi0, Xo, Uo, j, st, uapp,
                                                           !use_ls, &Xg, &Ug);

@@ -8,6 +8,7 @@
 #pragma once
 #include "m4q_args.h"
 #include "m4q_device.h"
+#include "m4q_rollout_pair.h"
 
 // Settled by A/B runs and no longer switches (the losing branches are gone from the source; their numbers are in
 // profiles/r02_ab_experiments.txt, r03_exact_qp_log.txt, r04_ab_experiments.txt):
@@ -1303,6 +1304,199 @@ __device__ __forceinline__ double rollout_forward(const Prov& prov, int T, S x0,
     }
   }
   return rowsum<NX>(cx) + cu;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The pair form of rollout_forward<S, NX, NU, false, true>: two horizon indices per trip on the two halves of the row.
+// Of the fp64 work of one index almost half - row j of A_t, nx[p] = N_p[j][:] x_g(t), Delta_t[j] - depends on the guess alone, not
+// on the state being rolled, and at NX = 8 it ran on 8 of a row's 16 lanes.  Here lane 8 g + j2 holds model row j2 and half g owns
+// the indices t with t % 2 == g (m4q_rollout_pair.h): one instruction forms those operands for both indices of a trip, and one
+// load or store serves both.  The state-dependent chain alternates between the halves: x_t sits in half 1 - t % 2, its sums read
+// that half's lanes (dot_lane_index_from / rowsum_from) and x_{t+1} is produced in half t % 2, where A_t's row is.  Every DPP
+// statement runs with both halves enabled (its source lanes must be live); the rest of an index - the clamp, x+, the finiteness
+// sums - runs under the owning half's mask, so no half ever accumulates or stores a value of the other's index.
+// Same products, same sums, same order as rollout_forward: xs, us and both guesses keep their bits (nx[p] by plain FMAs over the
+// node a lane loads whole: acc = fma(xg[k], row[k], acc) from zero, k = 0 .. 7, which is what the DPP dot computes).
+// Returns sum |x|^2 + sum u^2 summed over both halves - other bits than rollout_forward's, for the terms meet in another order,
+// but finite exactly when every state and control is, and only that is read (fail = !finite_d(chk)).
+// Entered with all 16 lanes of the row enabled; jj: the lane in its row; u_first and the return value are valid in lane 0.
+// ---------------------------------------------------------------------------------------------
+template <class S, int NX, int NU, bool WANT_COST, bool TCF, class Prov>
+constexpr bool rollout_pair_form() {
+  return sizeof(S) == sizeof(double) && std::is_same<Prov, FusedProv<S, NX, NU, Prov::ORDER_>>::value && !WANT_COST && TCF &&
+         NX == rollout_pair::HALF && batch_fits<NX, NU, Prov::ORDER_>();          // (the last: rollout_forward's HOIST at n = 8)
+}
+
+template <int NX, int NU, class Prov>
+__device__ __forceinline__ double rollout_forward_pair(const Prov& prov, int T, double x0, const Window& win, int flags, const GView& gains,
+                                                        double sat, const double (&lo0)[NU], const double (&hi0)[NU], const GView& Xo,
+                                                        const GView& Uo, int jj, bool store_ok, double (&u_first)[NU], bool shift_out,
+                                                        const GView& Xg, const GView& Ug) {
+  namespace rp = rollout_pair;
+  static_assert(NX == rp::HALF && NX % 2 == 0, "two halves of eight lanes");
+  constexpr int ORDER = Prov::ORDER_, NP = Prov::NP;
+  const bool ref = (flags & QP_REF_LQR) != 0;
+  const int g2 = rp::half_of_lane(jj), j2 = rp::coord_of_lane(jj);
+  const double xb0 = win.xbm.ld<double>(j2);
+  double x = __shfl(x0, j2, 16);                      // x_0 into the upper half (the lower keeps its copy: never read)
+  GView Xd = Xo, Ud = Uo;
+  Xd.off = shift_out ? Xg.off : Xo.off;
+  Ud.off = shift_out ? Ug.off : Uo.off;
+  if (store_ok && rp::stores_x0(g2, shift_out)) Xd.st<double>(j2, x);
+  // rows j2 of N_1 .. N_NP stay in registers; A's row is re-read from LDS into `arow` once per trip, as soon as the trip's second
+  // dot has read A_t's row out of it, and A_t's row is formed in place (A's row held as well - 16 more registers beside the node's
+  // 16 - spilled)
+  ModelRegs<double, NX, NU, ORDER> mregs;
+  mregs.load_rows(prov, j2);
+  double arow[NX];
+  auto load_arow = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < NX; ++k) arow[k] = prov.el(0, j2, k);
+  };
+  load_arow();
+  double cx = 0.0, cu = 0.0;     // this half's share of sum |x|^2 (per lane) and of sum u^2 (replicated over the half)
+  double u[NU];                  // the controls of the index this half rolled last
+#pragma unroll
+  for (int k = 0; k < NU; ++k) u[k] = 0.0;
+  // what a trip carries for its two indices: as many doubles as rollout_forward's operand set (the node is consumed on arrival;
+  // row j2 of B_t and Delta_t[j2] come out of nx and u_g at the top of the trip)
+  struct Ops {
+    double ug[NU];               // u_g of the half's own index
+    double nx[NP];               // N_p[j2][:] x_g of the half's own index
+    double ub[NU], kre[NU];
+    double Kx[NU];               // row j2 of the gain of the index whose state this half holds
+  };
+  auto fetch = [&](int p, Ops& o, double (&node)[NX]) __attribute__((always_inline)) {
+    const unsigned tl = (unsigned)rp::load_index(T, p, g2), tk = (unsigned)rp::gain_index(T, p, g2);
+    ldn<NU>(prov.Ug, tl * NU, o.ug);
+#pragma unroll
+    for (int i = 0; i < NX; i += 2) {
+      double w[2];
+      ldn<2>(prov.Xg, tl * NX + i, w);
+      node[i] = w[0]; node[i + 1] = w[1];
+    }
+    ldn<NU>(win.ubm, tl * NU, o.ub);
+    ldn<NU>(gains, tl * ((NX + 1) * NU) + NX * NU, o.kre);
+    ldn<NU>(gains, tk * ((NX + 1) * NU) + j2 * NU, o.Kx);
+  };
+  auto derive = [&](Ops& o, const double (&node)[NX]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      double acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < NX; ++k) acc = fma(node[k], mregs.row[1 + p][k], acc);
+      o.nx[p] = acc;
+    }
+    // (pinned here, ahead of the next trip's loads: left to the scheduler the sums sank below them and two nodes were live at once)
+#pragma unroll
+    for (int p = 0; p < NP; ++p) asm volatile("" : "+v"(o.nx[p]));
+  };
+  // row j2 of A_t (in place: arow holds A's row on entry), of B_t and Delta_t[j2] of the half's own index
+  auto form = [&](const Ops& cur, double (&Brow)[NU], double& dlt) __attribute__((always_inline)) {
+    Poly<NU, ORDER> po;
+    po.eval(cur.ug);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+#pragma unroll
+      for (int k = 0; k < NX; ++k) cmac_r(arow[k], mregs.row[1 + p][k], po.pu[p]);
+    }
+    typename Prov::Lin l;
+#pragma unroll
+    for (int k = 0; k < NU; ++k) l.u[k] = cur.ug[k];
+    l.xg = 0.0;
+    prov.finish_rows(l, po, cur.nx, Brow, dlt);
+  };
+  // index t = 2 p + H: x_t in half 1 - H, its operands and x_{t+1} in half H.  FIRST: the trip that holds t = 0
+  auto chain = [&](auto hh, auto first, const Ops& cur, const double (&Brow)[NU], double dlt) __attribute__((always_inline)) {
+    constexpr int H = decltype(hh)::value;
+    constexpr bool T0 = decltype(first)::value && H == 0;
+    constexpr int L0 = rp::first_source_lane(H);
+    const double ax = dot_lane_index_from<L0, NX>(x, arow);
+    const double dx = csub(x, xb0);
+    double rs[NU];
+#pragma unroll
+    for (int k = 0; k < NU; ++k) rs[k] = rowsum_from<L0, NX>(cmul(cur.Kx[k], dx));
+    if (g2 == H) {
+#pragma unroll
+      for (int k = 0; k < NU; ++k) {
+        double uk = rs[k] + cur.kre[k] + cur.ub[k];                      // lqr.py:75
+        double lo = -sat, hi = sat;
+        if constexpr (T0) {
+          lo = fmax(lo, lo0[k]);
+          hi = fmin(hi, hi0[k]);
+        }
+        uk = fmin(fmax(uk, lo), hi);                                     // lqr.py:76
+        u[k] = uk;
+        if constexpr (T0) u_first[k] = uk;
+      }
+      double xn = ref ? ax : cadd(ax, dlt);
+#pragma unroll
+      for (int k = 0; k < NU; ++k) cmac_r(xn, Brow[k], u[k]);
+      cx += norm2(xn);
+#pragma unroll
+      for (int k = 0; k < NU; ++k) cu = fma(u[k], u[k], cu);
+      x = xn;
+    }
+  };
+  // both halves store their index's x_{t+1} and u_t (t = 2 p + g2) in one instruction each
+  auto store = [&](auto first, int p, bool live) __attribute__((always_inline)) {
+    const int t = rp::own_index(p, g2);
+    if (live) {
+      Xd.st<double>((unsigned)rp::node_slot(t, shift_out) * NX + j2, x);
+      bool uok = true;
+      if constexpr (decltype(first)::value) uok = rp::ctrl_stored(t, shift_out);
+      if (uok) stn<NU>(Ud, (unsigned)rp::ctrl_slot(t, shift_out) * NU, u);
+    }
+  };
+  auto pair = [&](auto first, int p, const Ops& cur, Ops& nxt) __attribute__((always_inline)) {
+    M4Q_NO_HOIST();
+    double node[NX];
+    fetch(p + 1, nxt, node);
+    double Brow[NU], dlt;
+    form(cur, Brow, dlt);
+    chain(ic<0>{}, first, cur, Brow, dlt);
+    chain(ic<1>{}, first, cur, Brow, dlt);
+    M4Q_NO_HOIST();                  // (not above the dot that still reads A_t's row)
+    load_arow();
+    derive(nxt, node);
+    store(first, p, store_ok);
+  };
+  // an odd horizon's last index, alone in the lower half
+  auto half = [&](auto first, int p, const Ops& cur) __attribute__((always_inline)) {
+    M4Q_NO_HOIST();
+    double Brow[NU], dlt;
+    form(cur, Brow, dlt);
+    chain(ic<0>{}, first, cur, Brow, dlt);
+    store(first, p, store_ok && rp::index_live(T, rp::own_index(p, g2)));
+  };
+  Ops ops0, opsA, opsB;
+  {
+    double node[NX];
+    fetch(0, ops0, node);
+    derive(ops0, node);
+  }
+  const int nf = rp::full_pairs(T);
+  if (nf > 0) {
+    pair(std::true_type{}, 0, ops0, opsA);
+    int p = 1;
+    for (; p + 1 < nf; p += 2) {
+      pair(std::false_type{}, p, opsA, opsB);
+      pair(std::false_type{}, p + 1, opsB, opsA);
+    }
+    if (p < nf) {
+      pair(std::false_type{}, p, opsA, opsB);
+      opsA = opsB;
+    }
+    if (rp::odd_tail(T)) half(std::false_type{}, nf, opsA);
+  } else {
+    half(std::true_type{}, 0, ops0);
+  }
+  // a shifting row repeats its last column: the half that owns index T - 1 still holds x_T and u_{T-1}
+  if (store_ok && rp::repeats(T, T - 1, shift_out) && g2 == rp::owner_half(T - 1)) {
+    Xd.st<double>((unsigned)rp::repeat_node_slot(T) * NX + j2, x);
+    stn<NU>(Ud, (unsigned)rp::repeat_ctrl_slot(T) * NU, u);
+  }
+  return rowsum<16>(cx) + bcast<0>(cu) + bcast<rp::HALF>(cu);
 }
 
 // ---------------------------------------------------------------------------------------------
