@@ -96,6 +96,22 @@ def exact_paths(nx, order):
     return [COMPLEX, REAL, TRACELESS] + ([TILE] if has_tile(nx, order) else [])
 
 
+TC_MIN_N = 8                             # constexpr int TC_MIN_N = 8;
+
+
+def n_state(nx, path):
+    """NS, the dimension of a kernel's recursion: nx - 1 on the traceless coordinates (coords_of: paths 2, 3, 4), else nx."""
+    return nx - 1 if path in (TRACELESS, TILE, SG) else nx
+
+
+def has_tc(nx, path):
+    """constexpr bool HAS_TC = NS >= TC_MIN_N && sizeof(S) == sizeof(double);  (mpc_kernel, the clipped solve off the tiles): the
+    kernel holds a constant-target instantiation of the backward sweep and of the rollout (riccati_backward<.., false, true>,
+    rollout_forward<.., false, true>, rollout_forward_pair at NS = 8) beside the general one and picks by QP_TARG_CONST at run
+    time.  S is double on every path but the complex one."""
+    return path not in (COMPLEX, TILE) and n_state(nx, path) >= TC_MIN_N
+
+
 def pieces(step_begin, step_end, exact):
     """The work items [begin, end) mpc_kernel makes of one member's run [step_begin, step_end): two_phase (step_begin < 2 and
     step_end > 2) cuts a head [step_begin, 2) off the rest, and the exact kernel cuts the rest again at every XCUTS[i] below

@@ -57,22 +57,26 @@ def _oracle(cell, exact):
     return _ORACLE[key]
 
 
-def _open(cell, p, model_per_instance=None):
-    """A session of the cell's kernel on scenario p (model_per_instance: default, whether p holds one model per member)."""
+def _open(cell, p, model_per_instance=None, target_per_instance=False, plant_per_instance=None):
+    """A session of the cell's kernel on scenario p (model_per_instance: default, whether p holds one model per member;
+    plant_per_instance: default, the process cells - detuned members, one d x d Hamiltonian each; target_per_instance: X_targ and
+    U_targ of p carry a leading member axis)."""
     B, n, m = p["batch"], p["dim_x"], p["dim_u"]
-    per_plant = cell.plant == kv.PROCESS                 # detuned members: one d x d Hamiltonian each
-    op0, ops, _ = _plant_ops(p, kv.HAMILTONIAN if per_plant else cell.plant)
+    per_plant = cell.plant == kv.PROCESS if plant_per_instance is None else plant_per_instance
+    op0, ops, _ = _plant_ops(p, kv.HAMILTONIAN if cell.plant == kv.PROCESS else cell.plant)
     if model_per_instance is None:
         model_per_instance = p["models"].shape[0] > 1
     sess = m4q.EnsembleSession(B, n, m, p["order"], p["horizon"], p["n_steps"], p["dt"], p["sat"], p["du"],
                                plant_kind=kv.PLANT_CODE[cell.plant], model_per_instance=model_per_instance,
-                               plant_per_instance=per_plant, target_cols=p["n_steps"] + p["horizon"] + 1,
+                               plant_per_instance=per_plant, target_per_instance=target_per_instance,
+                               target_cols=p["n_steps"] + p["horizon"] + 1,
                                force_complex=cell.path == kv.COMPLEX, traceless=cell.path != kv.REAL, tile=cell.path == kv.TILE,
                                shared_generators=None if cell.path == kv.SG else False, exact_qp=cell.exact)
     try:
         if cell.path == kv.SG:
             sess.build_models(p["dt"], p["generators"], p["scales"])
-        if per_plant:
+        if per_plant and cell.plant != kv.NONE:
+            op0 = np.broadcast_to(op0, (B,) + op0.shape[1:])
             ops = np.broadcast_to(ops, (B,) + ops.shape[1:])
         sess.load_problem(None if cell.path == kv.SG else p["models"], p["x0"], p["X_targ"], p["U_targ"], p["Q"], p["R"], p["Qf"],
                           None if cell.plant == kv.NONE else op0, None if cell.plant == kv.NONE else ops)
@@ -82,19 +86,21 @@ def _open(cell, p, model_per_instance=None):
     return sess
 
 
-@pytest.mark.parametrize("cell", LOOP_CELLS, ids=kv.cell_id)
-def test_closed_loop_cell_teacher_forced(cell):
-    """One kernel instance: every MPC step started from the oracle's state (states, controls, SQP guesses; PLANT_NONE: the state
-    through put_state, as the host-driven loop hands it over).  Clipped solve: QP-solve counts identical, us[k] and xs[k+1] to
-    1e-10 relative, the SQP guesses left behind to 1e-7.  Exact solve: counts identical, us[k] within 1e-9 of the bound, xs[k+1]
-    within 1e-9, some control at the bound, and the controls differ from the clipped loop's.  Exit codes 0 throughout.  With no
-    plant the next state is the host's: us[k], the guesses and the counts are the kernel's outputs."""
-    p, xs_t, us_t, codes, solves, trace = _oracle(cell, cell.exact)
+def _teacher_forced(cell, run, path=None, **open_kw):
+    """One kernel instance on the oracle's run (p, xs_t, us_t, codes, solves, trace) of a scenario: every MPC step started from the
+    oracle's state (states, controls, SQP guesses; PLANT_NONE: the state through put_state, as the host-driven loop hands it over).
+    The session (opened with open_kw) reports `path` (default: the cell's) before the first step and after the last; exit codes 0
+    and identical QP-solve counts at every step.  Clipped solve: us[k] and xs[k+1] to 1e-10 relative, the SQP guesses left behind to
+    1e-7.  Exact solve: us[k] within 1e-9 of the bound, xs[k+1] within 1e-9.  Returns (the applied controls, the number of control
+    and guess entries seen at the bound, the worst error over its bound)."""
+    p, xs_t, us_t, codes, solves, trace = run
     assert np.all(codes == 0)
     B, ns, sat = p["batch"], p["n_steps"], p["sat"]
-    sess = _open(cell, p)
+    path = cell.path if path is None else path
+    worst = 0.0
+    sess = _open(cell, p, **open_kw)
     try:
-        assert sess.path_detail() == cell.path
+        assert sess.path_detail() == path
         at_bound = 0
         us_got = np.zeros_like(us_t)
         for k in range(ns):
@@ -118,6 +124,7 @@ def test_closed_loop_cell_teacher_forced(cell):
             if cell.exact:
                 eu = np.abs(got["us"][:, k] - us_t[:, k]).max() / sat
                 ex = np.abs(got["xs"][:, k + 1] - xs_t[:, k + 1]).max() if cell.plant != kv.NONE else 0.0
+                worst = max(worst, eu / 1e-9, ex / 1e-9)
                 assert eu <= 1e-9 and ex <= 1e-9, (k, eu, ex)
                 at_bound += int((np.abs(got["us"][:, k]) >= sat * (1 - 1e-9)).sum() + (np.abs(got["u_guess"]) >= sat * (1 - 1e-9)).sum())
             else:
@@ -125,12 +132,26 @@ def test_closed_loop_cell_teacher_forced(cell):
                         rel(got["xs"][:, k + 1], xs_t[:, k + 1]) if cell.plant != kv.NONE else 0.0,
                         rel(got["x_guess"], np.stack([trace[b][k + 1][0].T for b in range(B)])),
                         rel(got["u_guess"], np.stack([trace[b][k + 1][1].T for b in range(B)]))]
+                worst = max(worst, max(errs[:2]) / 1e-10, max(errs[2:]) / 1e-7)
                 assert max(errs[:2]) <= 1e-10 and max(errs[2:]) <= 1e-7, (k, errs)
                 at_bound += int((np.abs(got["u_guess"]) >= sat * (1 - 1e-9)).sum())
-        assert sess.path_detail() == cell.path                 # (the line-search weights are known after the first run)
+        assert sess.path_detail() == path                      # (the line-search weights are known after the first run)
     finally:
         sess.close()
     assert np.abs(us_got).max() <= sat * (1 + 1e-15)
+    return us_got, at_bound, worst
+
+
+@pytest.mark.parametrize("cell", LOOP_CELLS, ids=kv.cell_id)
+def test_closed_loop_cell_teacher_forced(cell):
+    """One kernel instance: every MPC step started from the oracle's state (states, controls, SQP guesses; PLANT_NONE: the state
+    through put_state, as the host-driven loop hands it over).  Clipped solve: QP-solve counts identical, us[k] and xs[k+1] to
+    1e-10 relative, the SQP guesses left behind to 1e-7.  Exact solve: counts identical, us[k] within 1e-9 of the bound, xs[k+1]
+    within 1e-9, some control at the bound, and the controls differ from the clipped loop's.  Exit codes 0 throughout.  With no
+    plant the next state is the host's: us[k], the guesses and the counts are the kernel's outputs."""
+    p = _oracle(cell, cell.exact)[0]
+    sat = p["sat"]
+    us_got, at_bound, _ = _teacher_forced(cell, _oracle(cell, cell.exact))
     assert at_bound > 0, "no control at the bound: the scenario does not exercise the box"
     if cell.exact:
         clip = _oracle(cell, False)[2]

@@ -81,6 +81,22 @@ def test_piece_rule_lines_read_as_mirrored():
         assert k.count(text) == 1, text
 
 
+def test_constant_target_rule_lines_read_as_mirrored():
+    """kernel_variants.TC_MIN_N / has_tc against the lines of mpc_kernel they mirror, the exact kernel's pin.tconst, and the two
+    host-side lines the moving-target cases of tests/operand_cases.py rest on: the tile path needs a constant target, and the flag
+    is the session's targ_const."""
+    k, capi = _src("m4q_kernels.hip"), _src("m4q_capi.hip")
+    assert k.count("constexpr int TC_MIN_N = %d;" % kv.TC_MIN_N) == 1
+    assert k.count("        constexpr bool HAS_TC = NS >= TC_MIN_N && sizeof(S) == sizeof(double);\n") == 1
+    assert k.count("        if constexpr (HAS_TC) tc = (flags & QP_TARG_CONST) != 0;\n") == 1
+    assert k.count("        pin.tconst = (flags & QP_TARG_CONST) != 0;\n") == 1
+    assert capi.count("    const bool supported[m4q::PATH_SG + 1] = {true, real, traceless, traceless && targ_const, traceless && sg_ok};") == 1
+    assert capi.count("  a.flags = p.qp_flags | (s->targ_const ? m4q::QP_TARG_CONST : 0) | ") == 1
+    cases = ((4, kv.REAL), (9, kv.REAL), (9, kv.TRACELESS), (9, kv.TILE), (16, kv.SG), (16, kv.COMPLEX), (8, kv.COMPLEX))
+    assert [kv.has_tc(nx, path) for nx, path in cases] == [False, True, True, False, True, False, False]
+    assert kv.n_state(9, kv.TRACELESS) == 8 and kv.n_state(9, kv.REAL) == 9 and kv.n_state(4, kv.TILE) == 3
+
+
 def test_pieces_mirror_the_cut_rule():
     assert kv.XCUTS == (4, 7, 12) and kv.LONG_STEPS > kv.XCUTS[-1] + 1
     assert kv.pieces(0, 14, True) == [(0, 2), (2, 4), (4, 7), (7, 12), (12, 14)]
