@@ -314,6 +314,44 @@ M4Q_API int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u
                                  int32_t q_mode, const double* weights, int32_t reduce, double* q, double* grad, double* grad_scale,
                                  double* q_mean);
 
+/* S control sequences, each SHARED by the ensemble, rolled against all B members in ONE launch: compare pulses or scan an amplitude
+ * over an ensemble; the line search of m4q_plant_robust_batch.  us [S][N][m] r, 1 <= S <= 8; the other arguments up to q_mode as
+ * m4q_plant_rollout_grad_batch with u_per_instance 0.  No state is stored.
+ * -> J [B][S] r or NULL: member b's objective under us[s], q_N (q_mode 1) or sum_{t=0..N} q_t with t ascending from 0.0 (q_mode 2);
+ *    J[.][s] has the bits of m4q_plant_rollout_batch's figure under us[s] (q_mode 2: of its N + 1 columns added in that order).
+ *    F [S] r or NULL: sum_b w_b J[b][s] in the gradient's fixed order, w = weights [B] r (finite, non-negative) or, NULL, 1/B.
+ * M4Q_E_BADARG: the gradient's refusals, S outside 1-8, q_mode outside 1-2, J and F both NULL.  M4Q_E_UNSUPPORTED: no compiled
+ * shape, n not a square, and M4Q_PLANT_GENERATOR (its kernels live in the other object; roll its discretised model).
+ * Arguments are checked before the device is asked for. */
+M4Q_API int m4q_plant_rollout_multi_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                                  const double* x0, int32_t S, const double* us, const double* u_scale, const double* op0,
+                                  const double* ops, int32_t plant_per_instance, const double* W, const double* target,
+                                  int32_t target_per_instance, int32_t q_mode, const double* weights, double* J, double* F);
+
+/* ONE control sequence optimised against the weighted mean of an ensemble (robust GRAPE) in one call: a projected L-BFGS on
+ * F(U) = sum_b w_b J_b(U), |U[t][k]| <= sat.  mpc4quantum_amd/plant_robust.py is the definition (its docstring states the loop step
+ * by step); csrc/m4q_robust_host.h repeats its direction in the same order of operations.
+ * The ensemble - plant, x0, u_scale, W, targets, weights, dts - is staged ONCE, with the gradient's state workspace [B][N+1][n] c.
+ * An iteration is one launch of the reduced gradient (m4q_plant_rollout_grad_batch with reduce) at the iterate and one launch of
+ * m4q_plant_rollout_multi_batch's kernel on the `steps` candidates clip(U + 2^-j p); the direction p and the decision are taken on
+ * the host in between: [N][m] + 1 doubles come down, [steps][N][m] go up, `steps` doubles come down.  The ensemble and its states
+ * never leave the device.  The gradient is not taken again when U did not move.
+ * U0 [N][m] r: the first guess (clipped into the box).  sat > 0 (INFINITY: no box); iters in 1..64; steps in 1..8; mem in 0..8
+ * pairs of quasi-Newton memory (0: projected gradient); step0 > 0 finite: the largest entry of the first trial step of a
+ * memoryless direction; tol, gtol >= 0 finite: stop when F - F_new <= tol |F| or max |projected gradient| <= gtol.
+ * -> U [N][m] r, cost [1], cost_hist [iters+1] (entry 0 the first F; unused entries repeat the last cost), alpha_hist [iters] (the
+ *    accepted 2^-j; 0: rejected or unused), pgrad_hist [iters] (max |projected gradient|; unused 0), n_iter [1] (iterations begun),
+ *    status [1]: 0 iterations used up, 1 converged, 2 no descent, 3 the first cost was not finite.
+ *    J [B] r or NULL: the members' objectives at U, by one more launch with S = 1 (whose F equals cost bit for bit).
+ * Refusals: those of m4q_plant_rollout_grad_batch with reduce, and the ranges above (M4Q_E_BADARG); M4Q_PLANT_GENERATOR is
+ * M4Q_E_UNSUPPORTED: optimise on the discretised model's gradient.  All checked before a device is asked for. */
+M4Q_API int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                                  const double* x0, const double* U0, const double* u_scale, const double* op0, const double* ops,
+                                  int32_t plant_per_instance, const double* W, const double* target, int32_t target_per_instance,
+                                  int32_t q_mode, const double* weights, double sat, int32_t iters, int32_t steps, int32_t mem,
+                                  double step0, double tol, double gtol, double* U, double* cost, double* cost_hist,
+                                  double* alpha_hist, double* pgrad_hist, int32_t* n_iter, int32_t* status, double* J);
+
 /* A stored feedback law run on B members over N steps in ONE launch: the tier between the open-loop rollouts above and the closed
  * loop that re-solves a QP at every step - time-varying gains around a nominal trajectory with saturation, a slew band and
  * measurement noise.  mpc4quantum_amd/feedback.py (FeedbackLaw, plant_feedback_reference, model_feedback_reference) is the

@@ -156,6 +156,26 @@ struct GradReduceArgs {
   M4Q_P(double) out_last; long last_stride;        // element nm of chunk c -> out_last[c last_stride]
 };
 
+// S control sequences shared by the ensemble, each rolled against all B members in one launch (m4q_plant_rollout_multi_batch and
+// the line search of m4q_plant_robust_batch; m4q_rollout_multi.h).  Member b under sequence s sees u_scale[b][k] us[s][t][k]; its
+// objective J[b][s] is q_N (q_mode 1) or sum_t q_t, t ascending from 0.0 (q_mode 2), q as RollArgs.  No state is stored.
+// F non-null: the launcher then runs grad_reduce_kernel twice - members in chunks of GRAD_CHUNK into partial [chunks][S], the
+// chunk partials into F [S] = sum_b weights[b] J[b][s] - with weights [B] (never null when F is set).
+constexpr int MULTI_MAX_S = 8;
+struct MultiArgs {
+  int B, N, kind, S, q_mode;
+  M4Q_P(const double) dts;                         // [N]
+  M4Q_P(const cplx) x0;                            // [B][n]
+  M4Q_P(const double) us;                          // [S][N][m]
+  M4Q_P(const double) u_scale;                     // [B][m] or null
+  M4Q_P(const cplx) op0; long op0_stride;          // plant operators, as PlantArgs
+  M4Q_P(const cplx) ops; long ops_stride;
+  M4Q_P(const cplx) W; M4Q_P(const cplx) target; long target_stride;
+  M4Q_P(double) J;                                 // [B][S]
+  M4Q_P(const double) weights;
+  M4Q_P(double) partial; M4Q_P(double) F;
+};
+
 // The plant's own linearisation along trajectories (m4q_plant_linearize_batch; m4q_plant_lin.h, plant_linearize.py is the
 // definition): the work unit is a (member, point) pair, B T of them.  Member b at point t: state X[b][t], controls U[b|.][t] as the
 // caller passed them (the member sees u_scale[b][k] u_k; u_scale may be null), step length dts[t].  Each output may be null.
@@ -352,6 +372,7 @@ struct ShapeOps {
   int (*launch_plant_linearize)(const PlantLinArgs&, hipStream_t); // (the shapes of launch_plant_grad; no generator plant)
   int (*launch_plant_qp)(const PlantQpArgs&, hipStream_t);         // (square shapes that hold qp_kernel; no generator plant)
   int (*launch_plant_step)(const PlantStepArgs&, hipStream_t);     // (the shapes and plants of launch_plant_qp)
+  int (*launch_plant_multi)(const MultiArgs&, hipStream_t);        // (the shapes and plants of launch_plant_grad)
 };
 
 }  // namespace m4q

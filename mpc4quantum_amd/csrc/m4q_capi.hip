@@ -20,6 +20,7 @@
 #include "../../include/m4q.h"
 #include "m4q_args.h"
 #include "m4q_lift.h"
+#include "m4q_robust_host.h"
 
 namespace m4q {
 struct cplx { double re, im; };
@@ -1683,6 +1684,208 @@ int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
   a.roll.models = st.in<cplx>(models, mdl.count); a.roll.model_stride = mdl.stride;
   if (st.error()) return st.error();
   return st.finish(sh->launch_model_grad(a, nullptr), "model rollout gradient");
+}
+
+namespace {
+// What m4q_plant_rollout_multi_batch and m4q_plant_robust_batch share: control sequences shared by the ensemble on one of the two
+// unitary plants.  The refusals are those of m4q_plant_rollout_grad_batch with reduce set, in its order, checked before a device
+// is asked for; *found receives the shape's kernels.
+int check_ensemble_args(const char* who, int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                        const double* x0, const double* u, const double* op0, const double* ops, const double* W, const double* target,
+                        int32_t q_mode, const double* weights, const m4q::ShapeOps** found) {
+  *found = find_shape_any_order(dim_x, dim_u, true);
+  if (!*found) return fail(M4Q_E_UNSUPPORTED, "%s: no kernel for dim_x=%d dim_u=%d", who, dim_x, dim_u);
+  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  if (B < 1 || N < 1) return fail(M4Q_E_BADARG, "%s: B and N must be at least 1 (got %d, %d)", who, B, N);
+  if (!x0 || !u || !W || !target) return fail(M4Q_E_BADARG, "%s: x0, the control sequences, W and target are required", who);
+  if (q_mode < 1 || q_mode > 2) return fail(M4Q_E_BADARG, "%s: q_mode is 1 (J = q_N) or 2 (J = sum_t q_t), got %d", who, q_mode);
+  if (weights)
+    for (int32_t b = 0; b < B; ++b)
+      if (!std::isfinite(weights[b]) || weights[b] < 0.0) return fail(M4Q_E_BADARG, "%s: weights[%d] = %g is not a finite non-negative number", who, b, weights[b]);
+  if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, op0 and ops are required", who);
+  if (int rc = check_device_plant_kind(plant_kind, dim_x, (std::string(who) + ": plant_kind %d is not a device plant").c_str())) {
+    if (plant_kind == M4Q_PLANT_PROCESS) return fail(rc, "%s: M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", who, dim_x);
+    return rc;
+  }
+  if (plant_kind == M4Q_PLANT_GENERATOR)      // (the gradient's advice: the optimiser needs that gradient, and the kernels live in the other object)
+    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no kernel here (its block matrix has (1 + m) n > 16 columns): "
+                "take the gradient of the discretised model with m4q_model_rollout_grad_batch", who);
+  return 0;
+}
+
+// stages the ensemble once: the plant, x0, u_scale, W, the targets, dts, the weights (1 / B when absent), and the buffers of S
+// sequences: us [S][N][m] (filled by the caller), J [B][S], the reduction's partials and F [S]
+m4q::MultiArgs stage_ensemble(Stage& st, int32_t B, size_t n, size_t m, int32_t plant_kind, int32_t N, const double* dts, const double* x0,
+                              const double* u_scale, const double* op0, const double* ops, int32_t plant_per_instance, const double* W,
+                              const double* target, int32_t target_per_instance, int32_t q_mode, const double* weights, int32_t S) {
+  const size_t k = plant_dim(plant_kind, (int)n);
+  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k), ef(B, target_per_instance, n);
+  m4q::MultiArgs a{};
+  a.B = B; a.N = N; a.kind = plant_kind; a.S = S; a.q_mode = q_mode;
+  a.dts = st.in<double>(dts, N);
+  a.x0 = st.in<cplx>(x0, (size_t)B * n);
+  if (u_scale) a.u_scale = st.in<double>(u_scale, (size_t)B * m);
+  a.op0 = st.in<cplx>(op0, e0.count); a.op0_stride = e0.stride;
+  a.ops = st.in<cplx>(ops, ek.count); a.ops_stride = ek.stride;
+  a.W = st.in<cplx>(W, n * n);
+  a.target = st.in<cplx>(target, ef.count); a.target_stride = ef.stride;
+  std::vector<double> w;
+  if (weights) w.assign(weights, weights + B);
+  else w.assign((size_t)B, 1.0 / B);
+  a.weights = st.in<double>(w.data(), (size_t)B);
+  a.us = st.in<double>(nullptr, (size_t)S * N * m);
+  a.J = st.out<double>(nullptr, (size_t)B * S);
+  a.partial = st.out<double>(nullptr, (((size_t)B + m4q::GRAD_CHUNK - 1) / m4q::GRAD_CHUNK) * S);
+  a.F = st.out<double>(nullptr, (size_t)S);
+  return a;
+}
+
+int copy_up(const void* dev, const void* host, size_t bytes) {
+  HIP_TRY(hipMemcpy(const_cast<void*>(dev), host, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+int copy_down(void* host, const void* dev, size_t bytes) {
+  HIP_TRY(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+}  // namespace
+
+int m4q_plant_rollout_multi_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                                  const double* x0, int32_t S, const double* us, const double* u_scale, const double* op0,
+                                  const double* ops, int32_t plant_per_instance, const double* W, const double* target,
+                                  int32_t target_per_instance, int32_t q_mode, const double* weights, double* J, double* F) {
+  const char* who = "m4q_plant_rollout_multi_batch";
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = check_ensemble_args(who, B, dim_x, dim_u, plant_kind, N, dts, x0, us, op0, ops, W, target, q_mode, weights, &sh)) return rc;
+  if (S < 1 || S > m4q::MULTI_MAX_S) return fail(M4Q_E_BADARG, "%s: S must be in 1..%d, got %d", who, m4q::MULTI_MAX_S, S);
+  if (!J && !F) return fail(M4Q_E_BADARG, "%s: nothing to return (J and F are both NULL)", who);
+  if (int rc = need_device()) return rc;
+  Stage st;
+  m4q::MultiArgs a = stage_ensemble(st, B, dim_x, dim_u, plant_kind, N, dts, x0, u_scale, op0, ops, plant_per_instance, W, target,
+                                    target_per_instance, q_mode, weights, S);
+  if (st.error()) return st.error();
+  const size_t nm = (size_t)N * dim_u;
+  if (int rc = copy_up(a.us, us, (size_t)S * nm * sizeof(double))) return rc;
+  if (!F) a.F = nullptr;                                     // (no reduction asked for)
+  if (int rc = st.finish(sh->launch_plant_multi(a, nullptr), "plant multi rollout")) return rc;
+  if (J)
+    if (int rc = copy_down(J, a.J, (size_t)B * S * sizeof(double))) return rc;
+  if (F)
+    if (int rc = copy_down(F, a.F, (size_t)S * sizeof(double))) return rc;
+  return 0;
+}
+
+int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts, const double* x0,
+                           const double* U0, const double* u_scale, const double* op0, const double* ops, int32_t plant_per_instance,
+                           const double* W, const double* target, int32_t target_per_instance, int32_t q_mode, const double* weights,
+                           double sat, int32_t iters, int32_t steps, int32_t mem, double step0, double tol, double gtol,
+                           double* U, double* cost, double* cost_hist, double* alpha_hist, double* pgrad_hist, int32_t* n_iter,
+                           int32_t* status, double* J) {
+  const char* who = "m4q_plant_robust_batch";
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = check_ensemble_args(who, B, dim_x, dim_u, plant_kind, N, dts, x0, U0, op0, ops, W, target, q_mode, weights, &sh)) return rc;
+  if (!U || !cost || !cost_hist || !alpha_hist || !pgrad_hist || !n_iter || !status)
+    return fail(M4Q_E_BADARG, "%s: U, cost, cost_hist, alpha_hist, pgrad_hist, n_iter and status are required", who);
+  if (!(sat > 0)) return fail(M4Q_E_BADARG, "%s: sat must be positive (INFINITY: no box)", who);
+  if (iters < 1 || iters > 64) return fail(M4Q_E_BADARG, "%s: iters must be in 1..64, got %d", who, iters);
+  if (steps < 1 || steps > m4q::MULTI_MAX_S) return fail(M4Q_E_BADARG, "%s: steps must be in 1..%d, got %d", who, m4q::MULTI_MAX_S, steps);
+  if (mem < 0 || mem > 8) return fail(M4Q_E_BADARG, "%s: mem must be in 0..8, got %d", who, mem);
+  if (!(step0 > 0) || !std::isfinite(step0)) return fail(M4Q_E_BADARG, "%s: step0 must be positive and finite", who);
+  if (!(tol >= 0) || !std::isfinite(tol) || !(gtol >= 0) || !std::isfinite(gtol))
+    return fail(M4Q_E_BADARG, "%s: tol and gtol must be finite and not negative", who);
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, nm = (size_t)N * m;
+  // staged once: the ensemble and every workspace; the iterate lives in a slot of the candidates' buffer
+  Stage st;
+  m4q::MultiArgs c = stage_ensemble(st, B, n, m, plant_kind, N, dts, x0, u_scale, op0, ops, plant_per_instance, W, target,
+                                    target_per_instance, q_mode, weights, steps);
+  m4q::GradArgs g{};
+  g.roll.B = B; g.roll.N = N; g.roll.kind = plant_kind; g.roll.xs_mode = 2; g.roll.q_mode = q_mode;
+  g.roll.dts = c.dts; g.roll.x0 = c.x0; g.roll.u_scale = c.u_scale; g.roll.u_stride = 0;
+  g.roll.op0 = c.op0; g.roll.op0_stride = c.op0_stride; g.roll.ops = c.ops; g.roll.ops_stride = c.ops_stride;
+  g.roll.W = c.W; g.roll.target = c.target; g.roll.target_stride = c.target_stride;
+  g.roll.xs = st.out<cplx>(nullptr, (size_t)B * ((size_t)N + 1) * n);
+  g.roll.q = st.out<double>(nullptr, (size_t)B * (q_mode == 2 ? (size_t)N + 1 : 1));
+  g.grad = st.out<double>(nullptr, (size_t)B * nm);
+  g.reduce = 1;
+  g.weights = c.weights;
+  g.partial = st.out<double>(nullptr, (((size_t)B + m4q::GRAD_CHUNK - 1) / m4q::GRAD_CHUNK) * (nm + 1));
+  double* mean = st.out<double>(nullptr, nm + 1);             // the reduced gradient [N][m], then F: one copy down per gradient
+  g.grad_mean = mean; g.q_mean = mean + nm;
+  if (st.error()) return st.error();
+
+  m4q::robust::State r;
+  r.mem = mem; r.sat = sat; r.step0 = step0;
+  r.U.resize(nm);
+  for (size_t e = 0; e < nm; ++e) r.U[e] = m4q::robust::clip(U0[e], sat);
+  r.g.assign(nm, 0.0);
+  std::vector<double> cands((size_t)steps * nm), down(nm + 1), Fs((size_t)steps);
+  int slot = 0;                                               // where on the device the iterate is (-1: nowhere)
+  if (int rc = copy_up(c.us, r.U.data(), nm * sizeof(double))) return rc;
+  for (int i = 0; i <= iters; ++i) cost_hist[i] = 0.0;
+  for (int i = 0; i < iters; ++i) alpha_hist[i] = pgrad_hist[i] = 0.0;
+  double Fcur = 0.0;
+  int st_code = 0, begun = 0;
+  bool moved = true;
+  for (int i = 0; i < iters; ++i) {
+    if (moved) {                                              // step 1: the reduced gradient at the iterate, where it lies
+      g.roll.u = c.us + (size_t)slot * nm;
+      if (int rc = sh->launch_plant_grad(g, nullptr)) return fail(rc, "%s: gradient launch failed", who);
+      if (int rc = copy_down(down.data(), mean, (nm + 1) * sizeof(double))) return rc;
+      r.g.assign(down.begin(), down.begin() + nm);
+      Fcur = down[nm];
+      moved = false;
+      if (i == 0) {
+        for (int e = 0; e <= iters; ++e) cost_hist[e] = Fcur;
+        if (!std::isfinite(Fcur)) { st_code = 3; break; }
+      }
+    }
+    begun = i + 1;
+    m4q::robust::project(r);                                  // steps 2 - 5 (m4q_robust_host.h)
+    pgrad_hist[i] = r.gmax;
+    if (r.gmax <= gtol) { st_code = 1; break; }
+    m4q::robust::absorb(r);
+    m4q::robust::direction(r);
+    for (int j = 0; j < steps; ++j) m4q::robust::candidate(r, j, cands.data() + (size_t)j * nm);
+    if (int rc = copy_up(c.us, cands.data(), cands.size() * sizeof(double))) return rc;
+    slot = -1;
+    if (int rc = sh->launch_plant_multi(c, nullptr)) return fail(rc, "%s: line search launch failed", who);
+    if (int rc = copy_down(Fs.data(), c.F, Fs.size() * sizeof(double))) return rc;
+    const int j = m4q::robust::pick(Fs.data(), steps);        // steps 6 - 8
+    if (j >= 0 && Fs[j] < Fcur) {
+      m4q::robust::accept(r, cands.data() + (size_t)j * nm);
+      slot = j;
+      moved = true;
+      alpha_hist[i] = std::ldexp(1.0, -j);
+      for (int e = i + 1; e <= iters; ++e) cost_hist[e] = Fs[j];
+      const double dec = Fcur - Fs[j], Fold = Fcur;
+      Fcur = Fs[j];
+      if (dec <= tol * std::fabs(Fold)) { st_code = 1; break; }
+    } else if (!r.pairs.empty()) {
+      r.pairs.clear();
+    } else {
+      st_code = 2;
+      break;
+    }
+  }
+  for (size_t e = 0; e < nm; ++e) U[e] = r.U[e];
+  cost[0] = Fcur; n_iter[0] = begun; status[0] = st_code;
+  if (J) {                                                    // the members' objectives at the returned U: one S = 1 launch
+    if (slot < 0) {
+      if (int rc = copy_up(c.us, r.U.data(), nm * sizeof(double))) return rc;
+      slot = 0;
+    }
+    m4q::MultiArgs one = c;
+    one.S = 1; one.us = c.us + (size_t)slot * nm;
+    if (int rc = sh->launch_plant_multi(one, nullptr)) return fail(rc, "%s: final launch failed", who);
+    double Fone = 0.0;
+    if (int rc = copy_down(J, one.J, (size_t)B * sizeof(double))) return rc;
+    if (int rc = copy_down(&Fone, one.F, sizeof(double))) return rc;
+    if (std::isfinite(Fcur) && Fone != Fcur)
+      return fail(-(int)hipErrorUnknown, "%s: the mean of the members' objectives at U, %.17g, is not the cost %.17g", who, Fone, Fcur);
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  return 0;
 }
 
 // what the fit against a prior model adds to the fit's arguments (m4q_dmdc_refit_batch, m4q_dmdc_refit_qr_batch)

@@ -2001,6 +2001,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NX == 9 ? 1 
   }
 }
 
+// plant_rollout_multi_kernel: S sequences shared by the ensemble against all members in one launch, the members' objectives alone
+// (m4q_plant_rollout_multi_batch; the line search of m4q_plant_robust_batch)
+#include "m4q_rollout_multi.h"
+
 // ---------------------------------------------------------------------------------------------
 // The plant's own discrete-time Jacobians along trajectories (m4q_plant_linearize_batch; plant_linearize.py:
 // plant_linearize_reference is the definition), Hamiltonian and process plants.  The work unit is a (member, point) pair: row g of
@@ -2647,7 +2651,41 @@ static int launch_model_grad(const GradArgs& a, hipStream_t s) { return launch_g
 #else
 static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 #endif
+// the S shared sequences of MultiArgs against every member (m4q_rollout_multi.h): launch_aux's launch over quads of members with the
+// rollouts' LDS, then - a.F set - the two passes of the ordered reduction over J [B][S] on the same stream.  grad_reduce's element
+// nm is row i's vals[i][nm] when q_cols is 0, so nm = S - 1 over rows of S covers the S columns.
+static int launch_multi_reduce(const MultiArgs& a, hipStream_t s) {
+  if (!a.F) return 0;
+  const int nchunks = (a.B + GRAD_CHUNK - 1) / GRAD_CHUNK;
+  GradReduceArgs p{};
+  p.count = a.B; p.chunk = GRAD_CHUNK; p.nm = a.S - 1; p.q_cols = 0;
+  p.vals = a.J; p.row_stride = a.S; p.w = a.weights;
+  p.out = a.partial; p.out_stride = a.S; p.out_last = a.partial + (a.S - 1); p.last_stride = a.S;
+  GradReduceArgs f{};
+  f.count = nchunks; f.chunk = nchunks; f.nm = a.S - 1; f.q_cols = 0;
+  f.vals = a.partial; f.row_stride = a.S;
+  f.out = a.F; f.out_last = a.F + (a.S - 1);
+  const long blocks = ((long)nchunks * a.S + 255) / 256;
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, p);
+  if (hipError_t e = hipGetLastError()) return -(int)e;
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3(1), dim3(256), 0, s, f);
+  return -(int)hipGetLastError();
+}
+static int launch_plant_multi(const MultiArgs& a, hipStream_t s) {
+  if constexpr (!SQUARE) {
+    return UNBUILT;
+  } else {
+    constexpr size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
+    int rc = UNBUILT;
+    if (a.kind == PLANT_HAMILTONIAN) rc = launch_aux(plant_rollout_multi_kernel<PLANT_HAMILTONIAN>, a, lds, s);
+    if constexpr (QUARTIC) {
+      if (a.kind == PLANT_PROCESS) rc = launch_aux(plant_rollout_multi_kernel<PLANT_PROCESS>, a, lds, s);
+    }
+    return rc ? rc : launch_multi_reduce(a, s);
+  }
+}
 #else
+static int launch_plant_multi(const MultiArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant(const PlantArgs&, hipStream_t) { return UNBUILT; }
 static int launch_noise(const NoiseArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant_rollout(const RollArgs&, hipStream_t) { return UNBUILT; }
@@ -2738,7 +2776,7 @@ static const ShapeOps* shape_ops() {
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
                                ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr,
                                launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr, launch_plant_linearize, launch_plant_qp,
-                               launch_plant_step};
+                               launch_plant_step, launch_plant_multi};
   return &ops;
 }
 

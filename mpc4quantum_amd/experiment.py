@@ -125,6 +125,15 @@ def _sqp_batch(exp, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps,
                            tol=tol, du=du, u_prev=u_prev, kind=exp.plant_kind, u_scale=u_scale, exact=exact, gains=gains)
 
 
+def _robust_batch(exp, x0, U0, ts_or_dt, W, target, sat, op0, u_scale, figure, weights, iters, steps, mem, step0, tol, gtol, members):
+    """plant_robust_batch of the two unitary device plants: operators as _linearize_batch."""
+    from .plant_robust import plant_robust_batch
+    own0, ops = exp.operators()
+    return plant_robust_batch(x0, U0, own0 if op0 is None else op0, ops, ts_or_dt, W, target, sat, kind=exp.plant_kind, u_scale=u_scale,
+                              figure=figure, weights=weights, iters=iters, steps=steps, mem=mem, step0=step0, tol=tol, gtol=gtol,
+                              members=members)
+
+
 def _ilqr_batch(exp, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0):
     """plant_ilqr_batch of the two unitary device plants: operators as _linearize_batch."""
     from .plant_ilqr import plant_ilqr_batch
@@ -267,6 +276,15 @@ class QExperiment(Experiment):
         the same arguments, the same dict, the same refusal of a generator plant."""
         return _ilqr_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0)
 
+    def robust_batch(self, x0, U0, ts_or_dt, W, target, sat, op0=None, u_scale=None, figure="last", weights=None, iters=10, steps=6,
+                     mem=5, step0=0.1, tol=1e-9, gtol=0.0, members=False):
+        """ONE control sequence U [N, m] optimised against the weighted mean of an ensemble of this plant - per-member op0 [B, k, k]
+        and u_scale [B, m] as simulate_batch - by a projected L-BFGS in one device call (plant_robust_batch): x0 [B, n], U0 [N, m],
+        ts_or_dt as linearize_batch, the rest and the returned dict as plant_robust_batch.  With collapse operators the plant is a
+        generator plant, which is refused."""
+        return _robust_batch(self, x0, U0, ts_or_dt, W, target, sat, op0, u_scale, figure, weights, iters, steps, mem, step0, tol, gtol,
+                             members)
+
 
 class LExperiment(QExperiment):
     """Open-system plant: x' = (L0 + sum_k u_k L_k) x with n x n generators on vec_r(rho)."""
@@ -291,6 +309,11 @@ class LExperiment(QExperiment):
         raise ValueError("LExperiment.quad_program_batch: the generator plant has no linearisation of its own on the device - "
                          "discretise the generators (discretize_homogeneous), linearise the model with WrapModel.linearize_batch and "
                          "solve with quad_program_batch")
+
+    def robust_batch(self, *args, **kwargs):
+        """Refused: the generator plant has no gradient kernel."""
+        raise ValueError("LExperiment.robust_batch: the generator plant has no control gradient on the device - discretise the "
+                         "generators (discretize_homogeneous) and optimise on the model's gradient (model_rollout_grad_batch)")
 
     def f(self, t, x, u):
         L = self.H0 + sum(h * uk for h, uk in zip(self.H1_list, np.reshape(u, -1)))
@@ -444,6 +467,13 @@ class QSynthesis(Experiment):
         """sqp_batch with the line search run in closed loop on the process plant (plant_ilqr_batch): arguments and the returned
         dict as QExperiment.ilqr_batch, x0 [B, d^4] process vectors."""
         return _ilqr_batch(self, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0)
+
+    def robust_batch(self, x0, U0, ts_or_dt, W, target, sat, op0=None, u_scale=None, figure="last", weights=None, iters=10, steps=6,
+                     mem=5, step0=0.1, tol=1e-9, gtol=0.0, members=False):
+        """ONE control sequence optimised against the weighted mean of an ensemble of process plants in one device call
+        (plant_robust_batch): arguments and the returned dict as QExperiment.robust_batch, x0 [B, d^4] process vectors."""
+        return _robust_batch(self, x0, U0, ts_or_dt, W, target, sat, op0, u_scale, figure, weights, iters, steps, mem, step0, tol, gtol,
+                             members)
 
 
 def split_blocks(bmatrix, nrows, ncols):
