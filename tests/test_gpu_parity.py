@@ -12,6 +12,7 @@ import mpc4quantum_amd as m4q
 from mpc4quantum_amd import _lib, configs
 from mpc4quantum_amd import lqr as m4q_lqr
 from oracle import m4q_oracle as orc
+from tests import strong_drive_cases as sd
 
 pytestmark = pytest.mark.gpu
 
@@ -440,8 +441,16 @@ def test_plant_hamiltonian_vs_expm(cfg):
         r = M @ M.conj().T
         rho.append((r / np.trace(r).real).reshape(-1))
     x = np.stack(rho)
-    for scale in (1.0, 40.0):      # the large one forces scaling-and-squaring (norm > theta_13)
+    # the large one forces scaling-and-squaring (norm > theta_13) for every member, with s differing within the five: per
+    # configuration the lowest of 40, 80, 160, .. that does (tests/strong_drive_cases.py: squarings mirrors expm_cols' rule)
+    large = {1: 1280.0, 3: 40.0, 4: 80.0}[cfg]
+    for scale in (1.0, large):
         u = scale * p["sat"] * rng.uniform(-1, 1, (5, m))
+        if scale == large:
+            s = [sd.squarings(sd.norm1(-1j * p["dt"] * (p["plant_op0"][0] + sum(u[b, k] * p["plant_ops"][0][k] for k in range(m)))))
+                 for b in range(5)]
+            print("config %d at %g x sat: s = %s" % (cfg, large, s))
+            assert min(s) >= 1 and len(set(s)) > 1
         out = m4q.plant_step_batch(x, u, p["plant_op0"], p["plant_ops"], p["dt"])
         for b in range(5):
             ref = orc.plant_step(x[b], u[b], p["plant_op0"][0], list(p["plant_ops"][0]), p["dt"])

@@ -15,6 +15,7 @@ import mpc4quantum_amd as m4q
 from mpc4quantum_amd import _lib
 from oracle import m4q_oracle as orc
 from tests import kernel_variants as kv
+from tests import strong_drive_cases as sd
 
 pytestmark = pytest.mark.gpu
 
@@ -315,10 +316,17 @@ def test_discretize_cell(cell):
         assert rel(out_s[b], orc.discretize_homogeneous([scales[b, k] * Ls[k] for k in range(m + 1)], dt, cell.order)) <= 1e-13
 
 
+# the large controls of test_plant_step_cell where 40 leaves a member at s = 0 or all five at one s: the lowest of 80, 160, .. at
+# which every member squares and s differs within the five (tests/strong_drive_cases.py: squarings mirrors expm_cols' rule)
+LARGE_CONTROLS = {(4, 1, kv.HAMILTONIAN): 80.0, (4, 1, kv.GENERATOR): 2560.0, (4, 2, kv.HAMILTONIAN): 80.0, (4, 2, kv.GENERATOR): 80.0,
+                  (16, 1, kv.GENERATOR): 80.0, (16, 2, kv.HAMILTONIAN): 80.0}
+
+
 @pytest.mark.parametrize("cell", _cells("plant"), ids=kv.cell_id)
 def test_plant_step_cell(cell):
     """m4q_plant_step_batch at (n, m) against orc.plant_step (Hamiltonian, 1e-12) / plant_step_generator (Lindbladian, 1e-11), B = 5
-    with per-member operators, and one case with large controls that forces scaling and squaring."""
+    with per-member operators, and one case with large controls that forces scaling and squaring: s >= 1 for every member and
+    differing within the five, asserted."""
     rng = np.random.default_rng(60 + cell.nx + 10 * cell.nu)
     n, m, d = cell.nx, cell.nu, kv.dd(cell.nx)
     Bn = 5
@@ -327,11 +335,19 @@ def test_plant_step_cell(cell):
         M = rng.standard_normal((d, d)) + 1j * rng.standard_normal((d, d))
         return 0.5 * (M + M.conj().T)
     x = _density_states(rng, d, Bn)
+    large = LARGE_CONTROLS.get((n, m, cell.mode), 40.0)
+
+    def squares(exponents):
+        s = [sd.squarings(sd.norm1(Z)) for Z in exponents]
+        print("%s at controls of %g: s = %s" % (kv.cell_id(cell), large, s))
+        assert min(s) >= 1 and len(set(s)) > 1
     if cell.mode == kv.HAMILTONIAN:
         H0 = np.stack([herm() for _ in range(Bn)])
         Hk = np.stack([[herm() for _ in range(m)] for _ in range(Bn)])
-        for dt, scale in ((0.25, 1.0), (0.25, 40.0)):
+        for dt, scale in ((0.25, 1.0), (0.25, large)):
             u = scale * rng.uniform(-1, 1, (Bn, m))
+            if scale == large:
+                squares(-1j * dt * (H0 + np.einsum('bk,bkij->bij', u, Hk)))
             out = m4q.plant_step_batch(x, u, H0, Hk, dt)
             for b in range(Bn):
                 assert rel(out[b], orc.plant_step(x[b], u[b], H0[b], list(Hk[b]), dt)) <= 1e-12
@@ -341,8 +357,10 @@ def test_plant_step_cell(cell):
     a = np.diag(np.sqrt(np.arange(1, d)), 1).astype(complex)
     L0 = np.stack([m4q.liouvillian(herm()) + 0.3 * kv.lindblad(a) for _ in range(Bn)])
     Lk = np.stack([[m4q.liouvillian(herm()) for _ in range(m)] for _ in range(Bn)])
-    for dt, scale in ((0.1, 1.0), (2.5, 1.0), (0.25, 40.0)):
+    for dt, scale in ((0.1, 1.0), (2.5, 1.0), (0.25, large)):
         u = scale * rng.uniform(-1, 1, (Bn, m))
+        if scale == large:
+            squares(np.swapaxes(dt * (L0 + np.einsum('bk,bkij->bij', u, Lk)), 1, 2))         # (a lane owns a row of L: expm of L^T)
         out = m4q.plant_step_batch(x, u, L0, Lk, dt, _lib.PLANT_GENERATOR)
         for b in range(Bn):
             assert rel(out[b], orc.plant_step_generator(x[b], u[b], L0[b], list(Lk[b]), dt)) <= 1e-11
