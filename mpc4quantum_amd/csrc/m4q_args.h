@@ -2,7 +2,10 @@
 // kernel translation units (m4q_kernels.hip) and the host side of the C ABI (m4q_capi.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "m4q_paths.h"      // enum Path, enum Coords
 
@@ -33,6 +36,15 @@ enum : int {
 
 constexpr Coords coords_of(Path p) { return p == PATH_COMPLEX ? COORDS_COMPLEX : p == PATH_REAL ? COORDS_HERM : COORDS_TRACELESS; }
 
+// The plant operators of a launch: op0 [B|1][k][k] and ops [B|1][m][k][k] complex, k the side the plant kind gives them (n for the
+// generator, d with d^2 = n for the Hamiltonian, d with d^4 = n for the process plant; d_p for an observed plant).  Per member or
+// shared: the strides are k k and m k k, or both 0 when shared.  Every block that steps a plant holds one as its member `plant`,
+// where the four fields stood before; the kernels read a.plant.op0 ... in place (a function around the reads changes their code).
+struct PlantOps {
+  M4Q_P(const cplx) op0; long op0_stride;
+  M4Q_P(const cplx) ops; long ops_stride;
+};
+
 // Arrays marked S are complex (cplx) on the general path and double on the real path (models that preserve
 // Hermiticity, expressed in the Hermitian operator basis of m4q_mpc.h); the host picks the kernel.
 struct MpcArgs {
@@ -46,8 +58,7 @@ struct MpcArgs {
   M4Q_P(const void) Q; M4Q_P(const void) Qf; M4Q_P(const void) R;            // S
   M4Q_P(const double) Cq; M4Q_P(const double) Cqf; M4Q_P(const double) Cr;   // line-search blocks (mpc.py:103-116)
   M4Q_P(const double) Wls;                        // [2n + 2n + 2m] diagonals of those blocks, or nullptr if one is not diagonal
-  M4Q_P(const cplx) op0; long op0_stride;         // plant operators
-  M4Q_P(const cplx) ops; long ops_stride;
+  PlantOps plant;                                 // (a PLANT_NONE session: both point at Q, strides 0 - never read)
   M4Q_P(cplx) xs; M4Q_P(double) us; M4Q_P(int) codes; M4Q_P(int) steps_done; M4Q_P(int) qp_solves;
   M4Q_P(cplx) Xg; M4Q_P(double) Ug;                     // per-instance SQP guess  [B][T+1][n] complex, [B][T][m] (resumable state)
   // per resident row (grid*4 of them): working guess followed by the QP solution (S [2][rows][T+1][n], [2][rows][T][m]), gains (S)
@@ -111,8 +122,7 @@ struct PlantArgs {
   int B, kind;
   double dt;
   M4Q_P(const cplx) x; M4Q_P(const double) u;
-  M4Q_P(const cplx) op0; long op0_stride;
-  M4Q_P(const cplx) ops; long ops_stride;
+  PlantOps plant;
   M4Q_P(cplx) x_next;
 };
 
@@ -126,8 +136,7 @@ struct RollArgs {
   M4Q_P(const cplx) x0;                            // [B][n]
   M4Q_P(const double) u; long u_stride;            // [B|1][N][m] (u_stride N m or 0)
   M4Q_P(const double) u_scale;                     // [B][m] or null
-  M4Q_P(const cplx) op0; long op0_stride;          // plant operators, as PlantArgs
-  M4Q_P(const cplx) ops; long ops_stride;
+  PlantOps plant;                                  // (plant rollout)
   M4Q_P(const cplx) models; long model_stride;     // [B|1][n][n(1+P)], as LinArgs (model rollout)
   M4Q_P(const cplx) W; M4Q_P(const cplx) target; long target_stride;
   M4Q_P(cplx) xs; M4Q_P(double) q;
@@ -168,8 +177,7 @@ struct MultiArgs {
   M4Q_P(const cplx) x0;                            // [B][n]
   M4Q_P(const double) us;                          // [S][N][m]
   M4Q_P(const double) u_scale;                     // [B][m] or null
-  M4Q_P(const cplx) op0; long op0_stride;          // plant operators, as PlantArgs
-  M4Q_P(const cplx) ops; long ops_stride;
+  PlantOps plant;
   M4Q_P(const cplx) W; M4Q_P(const cplx) target; long target_stride;
   M4Q_P(double) J;                                 // [B][S]
   M4Q_P(const double) weights;
@@ -179,29 +187,27 @@ struct MultiArgs {
 // The plant's own linearisation along trajectories (m4q_plant_linearize_batch; m4q_plant_lin.h, plant_linearize.py is the
 // definition): the work unit is a (member, point) pair, B T of them.  Member b at point t: state X[b][t], controls U[b|.][t] as the
 // caller passed them (the member sees u_scale[b][k] u_k; u_scale may be null), step length dts[t].  Each output may be null.
-struct PlantLinArgs {
-  int B, T, kind;
+// PlantTraj is that input side - the plant and the trajectories it is linearised along - which PlantQpArgs holds too.
+struct PlantTraj {
   M4Q_P(const double) dts;                         // [T]
   M4Q_P(const cplx) X;                             // [B][T][n]
   M4Q_P(const double) U; long u_stride;            // [B|1][T][m] (u_stride T m or 0)
   M4Q_P(const double) u_scale;                     // [B][m] or null
-  M4Q_P(const cplx) op0; long op0_stride;          // plant operators, as PlantArgs
-  M4Q_P(const cplx) ops; long ops_stride;
+  PlantOps plant;
+};
+struct PlantLinArgs {
+  int B, T, kind;
+  PlantTraj traj;
   M4Q_P(cplx) A_ls; M4Q_P(cplx) B_ls; M4Q_P(cplx) D_ls;      // [B][T][n][n], [B][T][n][m], [B][T][n], as LinArgs
 };
 
 // The QP of QpArgs on the linearisation PlantLinArgs describes, in two launches on one stream and no host in between
 // (m4q_plant_quad_program_batch; m4q_plant_qp.h): plant_factor_kernel writes U_t, B_t and Delta_t of every (member, point) pair
-// into the three workspaces, plant_qp_kernel sweeps each member over them.  x_init null: member b starts from X[b][0].
+// into the three workspaces, plant_qp_kernel sweeps each member over them.  x_init null: member b starts from traj.X[b][0].
 struct PlantQpArgs {
   int B, T, kind, flags;
   double sat, du;
-  M4Q_P(const double) dts;                         // the plant side, as PlantLinArgs
-  M4Q_P(const cplx) X;
-  M4Q_P(const double) U; long u_stride;
-  M4Q_P(const double) u_scale;
-  M4Q_P(const cplx) op0; long op0_stride;
-  M4Q_P(const cplx) ops; long ops_stride;
+  PlantTraj traj;                                  // the plant side: PlantLinArgs'
   M4Q_P(const cplx) x_init;                        // the QP side, as QpArgs ([B][n] or null)
   M4Q_P(const cplx) X_bm; long xbm_stride;
   M4Q_P(const double) U_bm; long ubm_stride;
@@ -222,12 +228,11 @@ struct PlantQpArgs {
 struct PlantStepArgs {
   int B, T, kind, flags, iter, iters, steps, closed;
   double sat, du, tol;
-  M4Q_P(const double) dts;                         // the plant side, as PlantLinArgs
+  M4Q_P(const double) dts;                         // the plant side, as PlantTraj but for the guess: the iterate is below
   M4Q_P(const cplx) x0;                            // [B][n]
   M4Q_P(const double) U0; long u0_stride;          // [B|1][T][m] (u0_stride T m or 0): read by the initial roll alone
   M4Q_P(const double) u_scale;
-  M4Q_P(const cplx) op0; long op0_stride;
-  M4Q_P(const cplx) ops; long ops_stride;
+  PlantOps plant;
   M4Q_P(const cplx) X_bm; long xbm_stride;         // the cost and the bounds, as PlantQpArgs
   M4Q_P(const double) U_bm; long ubm_stride;
   M4Q_P(const cplx) Q_ls; M4Q_P(const cplx) R_ls;
@@ -332,8 +337,7 @@ struct ObsPlantArgs {
   double dt;
   M4Q_P(const int) codes; M4Q_P(const int) steps_done;
   M4Q_P(const double) us;                          // [B][n_steps][m]
-  M4Q_P(const cplx) op0; long op0_stride;          // [B|1][d_p][d_p], as PlantArgs
-  M4Q_P(const cplx) ops; long ops_stride;          // [B|1][m][d_p][d_p]
+  PlantOps plant;                                  // (k = d_p)
   M4Q_P(cplx) zs;                                  // [B][n_steps + 1][n_p]
   M4Q_P(cplx) xs;                                  // [B][n_steps + 1][n]
 };
@@ -374,5 +378,24 @@ struct ShapeOps {
   int (*launch_plant_step)(const PlantStepArgs&, hipStream_t);     // (the shapes and plants of launch_plant_qp)
   int (*launch_plant_multi)(const MultiArgs&, hipStream_t);        // (the shapes and plants of launch_plant_grad)
 };
+
+// The blocks are the kernels' kernarg segments: a field that moves changes every kernel that reads the block.  Where the operator
+// block stands, what follows it and the size of each block that holds one, as they were when the four fields stood there bare.
+static_assert(std::is_standard_layout<PlantOps>::value && sizeof(PlantOps) == 32, "PlantOps: two pointers, two strides");
+static_assert(offsetof(PlantOps, op0_stride) == 8 && offsetof(PlantOps, ops) == 16 && offsetof(PlantOps, ops_stride) == 24, "PlantOps");
+static_assert(std::is_standard_layout<PlantTraj>::value && sizeof(PlantTraj) == 72 && offsetof(PlantTraj, plant) == 40, "PlantTraj");
+#define M4Q_PIN_PLANT(T, plant, plant_at, next, next_at, size)                                                         \
+  static_assert(std::is_standard_layout<T>::value && offsetof(T, plant) == plant_at && offsetof(T, next) == next_at && \
+                    sizeof(T) == size, #T ": the layout of the kernarg segment moved")
+M4Q_PIN_PLANT(MpcArgs, plant, 192, xs, 224, 432);
+M4Q_PIN_PLANT(PlantArgs, plant, 32, x_next, 64, 72);
+M4Q_PIN_PLANT(RollArgs, plant, 64, models, 96, 152);
+M4Q_PIN_PLANT(MultiArgs, plant, 56, W, 88, 144);
+M4Q_PIN_PLANT(PlantLinArgs, traj.plant, 56, A_ls, 88, 112);
+M4Q_PIN_PLANT(PlantQpArgs, traj.plant, 72, x_init, 104, 256);
+M4Q_PIN_PLANT(PlantStepArgs, plant, 96, X_bm, 128, 264);
+M4Q_PIN_PLANT(ObsPlantArgs, plant, 48, zs, 80, 96);
+#undef M4Q_PIN_PLANT
+static_assert(sizeof(GradArgs) == 208 && sizeof(FeedbackArgs) == 288, "the blocks that hold a RollArgs");
 
 }  // namespace m4q

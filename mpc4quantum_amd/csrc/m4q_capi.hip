@@ -165,6 +165,33 @@ int check_device_plant_kind(int32_t kind, int32_t dim_x, const char* not_a_plant
   return 0;
 }
 
+// What the one-shot entry points on a plant refuse alike, before a device is asked for, in two parts with the entry's own argument
+// checks in between.  named: the entry's name goes in front of the lookup's and of the process plant's refusal too (the entries
+// from m4q_plant_quad_program_batch on; the earlier ones print those two bare).
+//
+// plant_shape: the object that holds the plant kernels of (dim_x, dim_u), plant-only ones included, and dim_x a square - every
+// kernel behind these entries but plant_kernel's generator form has a density matrix or a process vector for a state.
+// needs_qp: a plant-only object will not do either, it has no QP kernel.
+int plant_shape(const char* who, bool named, int32_t dim_x, int32_t dim_u, bool needs_qp, const m4q::ShapeOps** found) {
+  *found = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
+  if (!*found) return fail(M4Q_E_UNSUPPORTED, "%s%sno kernel for dim_x=%d dim_u=%d", named ? who : "", named ? ": " : "", dim_x, dim_u);
+  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  if (needs_qp && (*found)->plant_only)
+    return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d dim_u=%d is a plant-only shape, it has no QP kernel", who, dim_x, dim_u);
+  return 0;
+}
+// check_plant_kind: a device plant (check_device_plant_kind), and not the generator plant where the entry's kernels have no form
+// for it - lacks names what is missing, advice what to call instead (lacks null: the generator plant is served)
+int check_plant_kind(const char* who, bool named, int32_t kind, int32_t dim_x, const char* lacks, const char* advice) {
+  if (int rc = check_device_plant_kind(kind, dim_x, (std::string(who) + ": plant_kind %d is not a device plant").c_str())) {
+    if (named && kind == M4Q_PLANT_PROCESS) return fail(rc, "%s: M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", who, dim_x);
+    return rc;
+  }
+  if (lacks && kind == M4Q_PLANT_GENERATOR)
+    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no %s (its block matrix has (1 + m) n > 16 columns): %s", who, lacks, advice);
+  return 0;
+}
+
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -232,6 +259,38 @@ class Stage {
     return 0;
   }
 };
+
+// The operator block (m4q::PlantOps) over arrays that are on the device already, [B|1][k][k] and [B|1][m][k][k]: the strides
+m4q::PlantOps plant_ops(const void* op0, const void* ops, size_t B, bool per_instance, size_t m, size_t k) {
+  m4q::PlantOps p{};
+  p.op0 = static_cast<const cplx*>(op0); p.op0_stride = Extent(B, per_instance, k * k).stride;
+  p.ops = static_cast<const cplx*>(ops); p.ops_stride = Extent(B, per_instance, m * k * k).stride;
+  return p;
+}
+// ... over the caller's arrays, staged: k from the plant kind, each size beside its stride
+m4q::PlantOps stage_plant(Stage& st, int32_t B, int32_t kind, int32_t dim_x, int32_t dim_u, const double* op0, const double* ops,
+                          int32_t plant_per_instance) {
+  const size_t m = dim_u, k = plant_dim(kind, dim_x);
+  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  m4q::PlantOps p{};
+  p.op0 = st.in<cplx>(op0, e0.count); p.op0_stride = e0.stride;
+  p.ops = st.in<cplx>(ops, ek.count); p.ops_stride = ek.stride;
+  return p;
+}
+// ... with the trajectories of B members over T points a linearisation runs along (m4q::PlantTraj)
+m4q::PlantTraj stage_traj(Stage& st, int32_t B, int32_t kind, int32_t dim_x, int32_t dim_u, int32_t T, const double* dts, const double* X,
+                          const double* U, int32_t u_per_instance, const double* u_scale, const double* op0, const double* ops,
+                          int32_t plant_per_instance) {
+  const size_t n = dim_x, m = dim_u;
+  const Extent eu(B, u_per_instance, (size_t)T * m);
+  m4q::PlantTraj t{};
+  t.dts = st.in<double>(dts, T);
+  t.X = st.in<cplx>(X, (size_t)B * T * n);
+  t.U = st.in<double>(U, eu.count); t.u_stride = eu.stride;
+  if (u_scale) t.u_scale = st.in<double>(u_scale, (size_t)B * m);
+  t.plant = stage_plant(st, B, kind, dim_x, dim_u, op0, ops, plant_per_instance);
+  return t;
+}
 
 // symmetrised real-ified cost block of iqp_line_search (mpc.py:92-93,103-104,112-116)
 void ls_block(const double* M, int k, std::vector<double>& out) {
@@ -680,9 +739,8 @@ int m4q_session_run(m4q_session* s, int32_t step_begin, int32_t step_end) {
   a.Q = s->input(M4Q_F_Q, coords); a.Qf = s->input(M4Q_F_QF, coords); a.R = s->input(M4Q_F_R, coords);
   a.Cq = (const double*)s->Cq.p; a.Cqf = (const double*)s->Cqf.p; a.Cr = (const double*)s->Cr.p;
   a.Wls = s->ls_diag ? (const double*)s->Wls.p : nullptr;
-  a.op0 = (const cplx*)s->f[M4Q_F_OP0].p; a.op0_stride = Extent(s->B, p.plant_per_instance, k * k).stride;
-  a.ops = (const cplx*)s->f[M4Q_F_OPS].p; a.ops_stride = Extent(s->B, p.plant_per_instance, m * k * k).stride;
-  if (p.plant_kind == M4Q_PLANT_NONE) { a.op0 = (const cplx*)s->f[M4Q_F_Q].p; a.ops = a.op0; a.op0_stride = a.ops_stride = 0; }
+  a.plant = plant_ops(s->f[M4Q_F_OP0].p, s->f[M4Q_F_OPS].p, s->B, p.plant_per_instance, m, k);
+  if (p.plant_kind == M4Q_PLANT_NONE) a.plant = plant_ops(s->f[M4Q_F_Q].p, s->f[M4Q_F_Q].p, s->B, false, m, k);
   a.xs = (cplx*)s->f[M4Q_F_XS].p; a.us = (double*)s->f[M4Q_F_US].p;
   a.codes = (int*)s->f[M4Q_F_CODES].p; a.steps_done = (int*)s->f[M4Q_F_STEPS_DONE].p; a.qp_solves = (int*)s->f[M4Q_F_QP_SOLVES].p;
   a.Xg = (cplx*)s->f[M4Q_F_X_GUESS].p; a.Ug = (double*)s->f[M4Q_F_U_GUESS].p;
@@ -817,8 +875,7 @@ int m4q_session_run_observed(m4q_session* s, int32_t step_begin, int32_t step_en
   a.B = s->B; a.kind = s->observe; a.n_steps = p.n_steps; a.dt = p.dt;
   a.codes = (const int*)s->f[M4Q_F_CODES].p; a.steps_done = (const int*)s->f[M4Q_F_STEPS_DONE].p;
   a.us = (const double*)s->f[M4Q_F_US].p;
-  a.op0 = (const cplx*)s->obs_op0.p; a.op0_stride = Extent(s->B, s->obs_per, dp * dp).stride;
-  a.ops = (const cplx*)s->obs_ops.p; a.ops_stride = Extent(s->B, s->obs_per, m * dp * dp).stride;
+  a.plant = plant_ops(s->obs_op0.p, s->obs_ops.p, s->B, s->obs_per, m, dp);
   a.zs = (cplx*)s->zs.p; a.xs = (cplx*)s->f[M4Q_F_XS].p;
   for (int k = step_begin; k < step_end; ++k) {
     if (int rc = m4q_session_run(s, k, k + 1)) return rc;
@@ -1171,14 +1228,12 @@ int m4q_plant_step_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_
   if (B <= 0 || !x || !u || !op0 || !ops || !x_next) return fail(M4Q_E_BADARG, "m4q_plant_step_batch: bad argument");
   if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_step_batch: bad argument")) return rc;
   if (int rc = need_device()) return rc;
-  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x);
-  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  const size_t n = dim_x, m = dim_u;
   Stage st;
   m4q::PlantArgs a{};
   a.B = B; a.kind = plant_kind; a.dt = dt;
   a.x = st.in<cplx>(x, (size_t)B * n); a.u = st.in<double>(u, (size_t)B * m);
-  a.op0 = st.in<cplx>(op0, e0.count); a.op0_stride = e0.stride;
-  a.ops = st.in<cplx>(ops, ek.count); a.ops_stride = ek.stride;
+  a.plant = stage_plant(st, B, plant_kind, dim_x, dim_u, op0, ops, plant_per_instance);
   a.x_next = st.out<cplx>(x_next, (size_t)B * n);
   if (st.error()) return st.error();
   return st.finish(sh->launch_plant(a, nullptr), "plant");
@@ -1222,21 +1277,18 @@ int m4q_plant_rollout_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t pla
                             const double* x0, const double* u, int32_t u_per_instance, const double* u_scale, const double* op0,
                             const double* ops, int32_t plant_per_instance, const double* W, const double* target,
                             int32_t target_per_instance, int32_t xs_mode, double* xs, int32_t q_mode, double* q) {
-  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
-  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d", dim_x, dim_u);
-  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "m4q_plant_rollout_batch: dim_x=%d is not a square, there is no device plant", dim_x);
-  if (int rc = check_roll_args("m4q_plant_rollout_batch", B, N, x0, u, W, target, xs_mode, xs, q_mode, q)) return rc;
-  if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "m4q_plant_rollout_batch: dts, op0 and ops are required");
-  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_rollout_batch: plant_kind %d is not a device plant")) return rc;
+  const char* who = "m4q_plant_rollout_batch";
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = plant_shape(who, /*named=*/false, dim_x, dim_u, /*needs_qp=*/false, &sh)) return rc;
+  if (int rc = check_roll_args(who, B, N, x0, u, W, target, xs_mode, xs, q_mode, q)) return rc;
+  if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, op0 and ops are required", who);
+  if (int rc = check_plant_kind(who, /*named=*/false, plant_kind, dim_x, nullptr, nullptr)) return rc;
   if (int rc = need_device()) return rc;
-  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x);
-  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
   Stage st;
-  m4q::RollArgs a = stage_roll(st, B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, xs_mode, xs, q_mode, q);
+  m4q::RollArgs a = stage_roll(st, B, dim_x, dim_u, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, xs_mode, xs, q_mode, q);
   a.kind = plant_kind;
   a.dts = st.in<double>(dts, N);
-  a.op0 = st.in<cplx>(op0, e0.count); a.op0_stride = e0.stride;
-  a.ops = st.in<cplx>(ops, ek.count); a.ops_stride = ek.stride;
+  a.plant = stage_plant(st, B, plant_kind, dim_x, dim_u, op0, ops, plant_per_instance);
   if (st.error()) return st.error();
   return st.finish(sh->launch_plant_rollout(a, nullptr), "plant rollout");
 }
@@ -1322,26 +1374,22 @@ int m4q_plant_feedback_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t pl
                              int32_t target_per_instance, int32_t xs_mode, double* xs, int32_t q_mode, double* q, double* us,
                              int32_t* clipped, int32_t* status) {
   const char* who = "m4q_plant_feedback_batch";
-  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
-  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d", dim_x, dim_u);
-  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = plant_shape(who, /*named=*/false, dim_x, dim_u, /*needs_qp=*/false, &sh)) return rc;
   const size_t sigma_count = B < 1 ? 0 : Extent(B, sigma_per_instance, 1).count;
   if (int rc = check_feedback_args(who, B, dim_x, N, x0, gains, x_ref, u_ref, sat, du_band, du, u_prev, noise_mode, sigma, sigma_count,
                                    plant_kind != M4Q_PLANT_PROCESS, W, target, xs_mode, xs, q_mode, q, us, clipped, status))
     return rc;
   if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, op0 and ops are required", who);
-  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_feedback_batch: plant_kind %d is not a device plant")) return rc;
+  if (int rc = check_plant_kind(who, /*named=*/false, plant_kind, dim_x, nullptr, nullptr)) return rc;
   if (int rc = need_device()) return rc;
-  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x);
-  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
   Stage st;
-  m4q::FeedbackArgs a = stage_feedback(st, B, n, m, N, x0, gains, x_ref, u_ref, law_per_instance, sat, du_band, du, u_prev,
+  m4q::FeedbackArgs a = stage_feedback(st, B, dim_x, dim_u, N, x0, gains, x_ref, u_ref, law_per_instance, sat, du_band, du, u_prev,
                                        u_prev_per_instance, u_scale, noise_mode, sigma, sigma_per_instance, seed, member_base, W, target,
                                        target_per_instance, xs_mode, xs, q_mode, q, us, clipped, status);
   a.roll.kind = plant_kind;
   a.roll.dts = st.in<double>(dts, N);
-  a.roll.op0 = st.in<cplx>(op0, e0.count); a.roll.op0_stride = e0.stride;
-  a.roll.ops = st.in<cplx>(ops, ek.count); a.roll.ops_stride = ek.stride;
+  a.roll.plant = stage_plant(st, B, plant_kind, dim_x, dim_u, op0, ops, plant_per_instance);
   if (st.error()) return st.error();
   return st.finish(sh->launch_plant_feedback(a, nullptr), "plant feedback");
 }
@@ -1417,25 +1465,20 @@ int m4q_plant_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
                                  int32_t target_per_instance, int32_t q_mode, const double* weights, int32_t reduce, double* q,
                                  double* grad, double* grad_scale, double* q_mean) {
   const char* who = "m4q_plant_rollout_grad_batch";
-  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
-  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d", dim_x, dim_u);
-  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = plant_shape(who, /*named=*/false, dim_x, dim_u, /*needs_qp=*/false, &sh)) return rc;
   if (int rc = check_grad_args(who, B, N, x0, u, u_per_instance, W, target, q_mode, weights, reduce, q, grad, q_mean)) return rc;
   if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, op0 and ops are required", who);
-  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_rollout_grad_batch: plant_kind %d is not a device plant")) return rc;
-  if (plant_kind == M4Q_PLANT_GENERATOR)
-    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no gradient kernel (its block matrix has (1 + m) n > 16 columns): "
-                "take the gradient of the discretised model with m4q_model_rollout_grad_batch", who);
+  if (int rc = check_plant_kind(who, /*named=*/false, plant_kind, dim_x, "gradient kernel",
+                                "take the gradient of the discretised model with m4q_model_rollout_grad_batch"))
+    return rc;
   if (int rc = need_device()) return rc;
-  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x);
-  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
   Stage st;
-  m4q::GradArgs a = stage_grad(st, B, n, m, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, q_mode, weights, reduce, q,
-                               grad, grad_scale, q_mean);
+  m4q::GradArgs a = stage_grad(st, B, dim_x, dim_u, N, x0, u, u_per_instance, u_scale, W, target, target_per_instance, q_mode, weights, reduce,
+                               q, grad, grad_scale, q_mean);
   a.roll.kind = plant_kind;
   a.roll.dts = st.in<double>(dts, N);
-  a.roll.op0 = st.in<cplx>(op0, e0.count); a.roll.op0_stride = e0.stride;
-  a.roll.ops = st.in<cplx>(ops, ek.count); a.roll.ops_stride = ek.stride;
+  a.roll.plant = stage_plant(st, B, plant_kind, dim_x, dim_u, op0, ops, plant_per_instance);
   if (st.error()) return st.error();
   return st.finish(sh->launch_plant_grad(a, nullptr), "plant rollout gradient");
 }
@@ -1445,29 +1488,21 @@ int m4q_plant_linearize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t p
                               const double* op0, const double* ops, int32_t plant_per_instance,
                               double* A_ls, double* B_ls, double* Delta_ls) {
   const char* who = "m4q_plant_linearize_batch";
-  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);
-  if (!sh) return fail(M4Q_E_UNSUPPORTED, "no kernel for dim_x=%d dim_u=%d", dim_x, dim_u);
-  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = plant_shape(who, /*named=*/false, dim_x, dim_u, /*needs_qp=*/false, &sh)) return rc;
   if (B < 1 || T < 1) return fail(M4Q_E_BADARG, "%s: B and T must be at least 1 (got %d, %d)", who, B, T);
   if ((int64_t)B * T > INT32_MAX) return fail(M4Q_E_BADARG, "%s: B T = %lld points do not fit one launch", who, (long long)B * T);
   if (!dts || !X || !U || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, X, U, op0 and ops are required", who);
   if (!A_ls && !B_ls && !Delta_ls) return fail(M4Q_E_BADARG, "%s: nothing to return (A_ls, B_ls and Delta_ls are all NULL)", who);
-  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_linearize_batch: plant_kind %d is not a device plant")) return rc;
-  if (plant_kind == M4Q_PLANT_GENERATOR)
-    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no linearisation kernel (its block matrix has (1 + m) n > 16 columns): "
-                "linearise its discretised model with m4q_discretize_batch and m4q_linearize_batch", who);
+  if (int rc = check_plant_kind(who, /*named=*/false, plant_kind, dim_x, "linearisation kernel",
+                                "linearise its discretised model with m4q_discretize_batch and m4q_linearize_batch"))
+    return rc;
   if (int rc = need_device()) return rc;
-  const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x), BT = (size_t)B * T;
-  const Extent eu(B, u_per_instance, (size_t)T * m), e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  const size_t n = dim_x, m = dim_u, BT = (size_t)B * T;
   Stage st;
   m4q::PlantLinArgs a{};
   a.B = B; a.T = T; a.kind = plant_kind;
-  a.dts = st.in<double>(dts, T);
-  a.X = st.in<cplx>(X, BT * n);
-  a.U = st.in<double>(U, eu.count); a.u_stride = eu.stride;
-  if (u_scale) a.u_scale = st.in<double>(u_scale, (size_t)B * m);
-  a.op0 = st.in<cplx>(op0, e0.count); a.op0_stride = e0.stride;
-  a.ops = st.in<cplx>(ops, ek.count); a.ops_stride = ek.stride;
+  a.traj = stage_traj(st, B, plant_kind, dim_x, dim_u, T, dts, X, U, u_per_instance, u_scale, op0, ops, plant_per_instance);
   if (A_ls) a.A_ls = st.out<cplx>(A_ls, BT * n * n);
   if (B_ls) a.B_ls = st.out<cplx>(B_ls, BT * n * m);
   if (Delta_ls) a.D_ls = st.out<cplx>(Delta_ls, BT * n);
@@ -1483,11 +1518,8 @@ int m4q_plant_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
                                  const double* u_prev, double* X_opt, double* U_opt, double* cost, double* gains) {
   const char* who = "m4q_plant_quad_program_batch";
   // (the lookup admits plant-only shapes so that theirs is a refusal of its own: such an object holds no QP kernel)
-  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, true);
-  if (!sh) return fail(M4Q_E_UNSUPPORTED, "%s: no kernel for dim_x=%d dim_u=%d", who, dim_x, dim_u);
-  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
-  if (sh->plant_only)
-    return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d dim_u=%d is a plant-only shape, it has no QP kernel", who, dim_x, dim_u);
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = plant_shape(who, /*named=*/true, dim_x, dim_u, /*needs_qp=*/true, &sh)) return rc;
   if (B < 1 || T < 1) return fail(M4Q_E_BADARG, "%s: B and T must be at least 1 (got %d, %d)", who, B, T);
   if ((int64_t)B * T > INT32_MAX) return fail(M4Q_E_BADARG, "%s: B T = %lld points do not fit one launch", who, (long long)B * T);
   if (!dts || !X || !U || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, X, U, op0 and ops are required", who);
@@ -1498,28 +1530,18 @@ int m4q_plant_quad_program_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
     const std::string why = m4q_last_error();
     return fail(M4Q_E_BADARG, "%s: %s", who, why.c_str());
   }
-  if (int rc = check_device_plant_kind(plant_kind, dim_x, "m4q_plant_quad_program_batch: plant_kind %d is not a device plant")) {
-    if (plant_kind == M4Q_PLANT_PROCESS) return fail(rc, "%s: M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", who, dim_x);
+  if (int rc = check_plant_kind(who, /*named=*/true, plant_kind, dim_x, "kernel here",
+                                "use m4q_discretize_batch + m4q_linearize_batch + m4q_quad_program_batch"))
     return rc;
-  }
-  if (plant_kind == M4Q_PLANT_GENERATOR)
-    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no kernel here (its block matrix has (1 + m) n > 16 columns): "
-                "use m4q_discretize_batch + m4q_linearize_batch + m4q_quad_program_batch", who);
   const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x), BT = (size_t)B * T, BT1 = (size_t)B * (T + 1);
   if ((qp_flags & M4Q_QP_EXACT_BOX) && (double)BT1 * n * 16 * 2 >= 4294967296.0)
     return fail(M4Q_E_BADARG, "%s: M4Q_QP_EXACT_BOX: batch too large for one call (trajectory workspace must stay below 4 GiB)", who);
   if (int rc = need_device()) return rc;
-  const Extent eu(B, u_per_instance, (size_t)T * m), e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
   const Extent xbm(B, bm_per_instance, (size_t)(T + 1) * n), ubm(B, bm_per_instance, (size_t)T * m);
   Stage st;
   m4q::PlantQpArgs a{};
   a.B = B; a.T = T; a.kind = plant_kind; a.flags = qp_flags; a.sat = sat; a.du = du;
-  a.dts = st.in<double>(dts, T);
-  a.X = st.in<cplx>(X, BT * n);
-  a.U = st.in<double>(U, eu.count); a.u_stride = eu.stride;
-  if (u_scale) a.u_scale = st.in<double>(u_scale, (size_t)B * m);
-  a.op0 = st.in<cplx>(op0, e0.count); a.op0_stride = e0.stride;
-  a.ops = st.in<cplx>(ops, ek.count); a.ops_stride = ek.stride;
+  a.traj = stage_traj(st, B, plant_kind, dim_x, dim_u, T, dts, X, U, u_per_instance, u_scale, op0, ops, plant_per_instance);
   if (x_init) a.x_init = st.in<cplx>(x_init, (size_t)B * n);
   a.X_bm = st.in<cplx>(X_bm, xbm.count); a.xbm_stride = xbm.stride;
   a.U_bm = st.in<double>(U_bm, ubm.count); a.ubm_stride = ubm.stride;
@@ -1560,11 +1582,8 @@ static int plant_descent_batch(const char* who, const char* what, int closed,
                                double* X, double* U, double* cost, double* cost_hist, double* alpha_hist, int32_t* n_iter, int32_t* status,
                                double* gains) {
   // the refusals of m4q_plant_quad_program_batch, whose launcher every iteration goes through, then the loop's own
-  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, true);
-  if (!sh) return fail(M4Q_E_UNSUPPORTED, "%s: no kernel for dim_x=%d dim_u=%d", who, dim_x, dim_u);
-  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
-  if (sh->plant_only)
-    return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d dim_u=%d is a plant-only shape, it has no QP kernel", who, dim_x, dim_u);
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = plant_shape(who, /*named=*/true, dim_x, dim_u, /*needs_qp=*/true, &sh)) return rc;
   if (B < 1 || T < 1) return fail(M4Q_E_BADARG, "%s: B and T must be at least 1 (got %d, %d)", who, B, T);
   if ((int64_t)B * T > INT32_MAX) return fail(M4Q_E_BADARG, "%s: B T = %lld points do not fit one launch", who, (long long)B * T);
   if (!x0 || !U0) return fail(M4Q_E_BADARG, "%s: x0 and U0, the initial states and the first guess, are required", who);
@@ -1580,18 +1599,12 @@ static int plant_descent_batch(const char* who, const char* what, int closed,
   if (iters < 1 || iters > 64) return fail(M4Q_E_BADARG, "%s: iters must be in 1..64, got %d", who, iters);
   if (steps < 1 || steps > 8) return fail(M4Q_E_BADARG, "%s: steps must be in 1..8, got %d", who, steps);
   if (!(tol >= 0) || !std::isfinite(tol)) return fail(M4Q_E_BADARG, "%s: tol must be finite and not negative", who);
-  if (int rc = check_device_plant_kind(plant_kind, dim_x, (std::string(who) + ": plant_kind %d is not a device plant").c_str())) {
-    if (plant_kind == M4Q_PLANT_PROCESS) return fail(rc, "%s: M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", who, dim_x);
-    return rc;
-  }
-  if (plant_kind == M4Q_PLANT_GENERATOR)
-    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no kernel here (its block matrix has (1 + m) n > 16 columns): "
-                "optimise on its discretised model", who);
+  if (int rc = check_plant_kind(who, /*named=*/true, plant_kind, dim_x, "kernel here", "optimise on its discretised model")) return rc;
   const size_t n = dim_x, m = dim_u, k = plant_dim(plant_kind, dim_x), BT = (size_t)B * T, BT1 = (size_t)B * (T + 1);
   if ((qp_flags & M4Q_QP_EXACT_BOX) && (double)BT1 * n * 16 * 2 >= 4294967296.0)
     return fail(M4Q_E_BADARG, "%s: M4Q_QP_EXACT_BOX: batch too large for one call (trajectory workspace must stay below 4 GiB)", who);
   if (int rc = need_device()) return rc;
-  const Extent eu(B, u_per_instance, (size_t)T * m), e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k);
+  const Extent eu(B, u_per_instance, (size_t)T * m);
   const Extent xbm(B, bm_per_instance, (size_t)(T + 1) * n), ubm(B, bm_per_instance, (size_t)T * m);
   Stage st;
   // staged once: the plant, the targets, the weights, x0 and U0; the iterate and every workspace live on the device
@@ -1601,8 +1614,7 @@ static int plant_descent_batch(const char* who, const char* what, int closed,
   s.x0 = st.in<cplx>(x0, (size_t)B * n);
   s.U0 = st.in<double>(U0, eu.count); s.u0_stride = eu.stride;
   if (u_scale) s.u_scale = st.in<double>(u_scale, (size_t)B * m);
-  s.op0 = st.in<cplx>(op0, e0.count); s.op0_stride = e0.stride;
-  s.ops = st.in<cplx>(ops, ek.count); s.ops_stride = ek.stride;
+  s.plant = stage_plant(st, B, plant_kind, dim_x, dim_u, op0, ops, plant_per_instance);
   s.X_bm = st.in<cplx>(X_bm, xbm.count); s.xbm_stride = xbm.stride;
   s.U_bm = st.in<double>(U_bm, ubm.count); s.ubm_stride = ubm.stride;
   s.Q_ls = st.in<cplx>(Q_ls, (size_t)(T + 1) * n * n); s.R_ls = st.in<cplx>(R_ls, (size_t)T * m * m);
@@ -1616,8 +1628,8 @@ static int plant_descent_batch(const char* who, const char* what, int closed,
   // the QP of every iteration: m4q_plant_quad_program_batch's block on the iterate
   m4q::PlantQpArgs a{};
   a.B = B; a.T = T; a.kind = plant_kind; a.flags = qp_flags; a.sat = sat; a.du = du;
-  a.dts = s.dts; a.X = s.X_lin; a.U = s.U; a.u_stride = (long)(T * m); a.u_scale = s.u_scale;
-  a.op0 = s.op0; a.op0_stride = s.op0_stride; a.ops = s.ops; a.ops_stride = s.ops_stride;
+  a.traj.dts = s.dts; a.traj.X = s.X_lin; a.traj.U = s.U; a.traj.u_stride = (long)(T * m); a.traj.u_scale = s.u_scale;
+  a.traj.plant = s.plant;
   a.x_init = s.x0; a.X_bm = s.X_bm; a.xbm_stride = s.xbm_stride; a.U_bm = s.U_bm; a.ubm_stride = s.ubm_stride;
   a.Q_ls = s.Q_ls; a.R_ls = s.R_ls; a.u_prev = s.u_prev;
   a.U_ws = st.out<cplx>(nullptr, BT * k * k); a.B_ws = st.out<cplx>(nullptr, BT * n * m); a.D_ws = st.out<cplx>(nullptr, BT * n);
@@ -1693,9 +1705,7 @@ namespace {
 int check_ensemble_args(const char* who, int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
                         const double* x0, const double* u, const double* op0, const double* ops, const double* W, const double* target,
                         int32_t q_mode, const double* weights, const m4q::ShapeOps** found) {
-  *found = find_shape_any_order(dim_x, dim_u, true);
-  if (!*found) return fail(M4Q_E_UNSUPPORTED, "%s: no kernel for dim_x=%d dim_u=%d", who, dim_x, dim_u);
-  if (dim_d(dim_x) == 0) return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d is not a square, there is no device plant", who, dim_x);
+  if (int rc = plant_shape(who, /*named=*/true, dim_x, dim_u, /*needs_qp=*/false, found)) return rc;
   if (B < 1 || N < 1) return fail(M4Q_E_BADARG, "%s: B and N must be at least 1 (got %d, %d)", who, B, N);
   if (!x0 || !u || !W || !target) return fail(M4Q_E_BADARG, "%s: x0, the control sequences, W and target are required", who);
   if (q_mode < 1 || q_mode > 2) return fail(M4Q_E_BADARG, "%s: q_mode is 1 (J = q_N) or 2 (J = sum_t q_t), got %d", who, q_mode);
@@ -1703,14 +1713,9 @@ int check_ensemble_args(const char* who, int32_t B, int32_t dim_x, int32_t dim_u
     for (int32_t b = 0; b < B; ++b)
       if (!std::isfinite(weights[b]) || weights[b] < 0.0) return fail(M4Q_E_BADARG, "%s: weights[%d] = %g is not a finite non-negative number", who, b, weights[b]);
   if (!dts || !op0 || !ops) return fail(M4Q_E_BADARG, "%s: dts, op0 and ops are required", who);
-  if (int rc = check_device_plant_kind(plant_kind, dim_x, (std::string(who) + ": plant_kind %d is not a device plant").c_str())) {
-    if (plant_kind == M4Q_PLANT_PROCESS) return fail(rc, "%s: M4Q_PLANT_PROCESS: dim_x=%d is not a fourth power", who, dim_x);
-    return rc;
-  }
-  if (plant_kind == M4Q_PLANT_GENERATOR)      // (the gradient's advice: the optimiser needs that gradient, and the kernels live in the other object)
-    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no kernel here (its block matrix has (1 + m) n > 16 columns): "
-                "take the gradient of the discretised model with m4q_model_rollout_grad_batch", who);
-  return 0;
+  // (the gradient's advice: the optimiser needs that gradient, and the kernels live in the other object)
+  return check_plant_kind(who, /*named=*/true, plant_kind, dim_x, "kernel here",
+                          "take the gradient of the discretised model with m4q_model_rollout_grad_batch");
 }
 
 // stages the ensemble once: the plant, x0, u_scale, W, the targets, dts, the weights (1 / B when absent), and the buffers of S
@@ -1718,15 +1723,13 @@ int check_ensemble_args(const char* who, int32_t B, int32_t dim_x, int32_t dim_u
 m4q::MultiArgs stage_ensemble(Stage& st, int32_t B, size_t n, size_t m, int32_t plant_kind, int32_t N, const double* dts, const double* x0,
                               const double* u_scale, const double* op0, const double* ops, int32_t plant_per_instance, const double* W,
                               const double* target, int32_t target_per_instance, int32_t q_mode, const double* weights, int32_t S) {
-  const size_t k = plant_dim(plant_kind, (int)n);
-  const Extent e0(B, plant_per_instance, k * k), ek(B, plant_per_instance, m * k * k), ef(B, target_per_instance, n);
+  const Extent ef(B, target_per_instance, n);
   m4q::MultiArgs a{};
   a.B = B; a.N = N; a.kind = plant_kind; a.S = S; a.q_mode = q_mode;
   a.dts = st.in<double>(dts, N);
   a.x0 = st.in<cplx>(x0, (size_t)B * n);
   if (u_scale) a.u_scale = st.in<double>(u_scale, (size_t)B * m);
-  a.op0 = st.in<cplx>(op0, e0.count); a.op0_stride = e0.stride;
-  a.ops = st.in<cplx>(ops, ek.count); a.ops_stride = ek.stride;
+  a.plant = stage_plant(st, B, plant_kind, (int32_t)n, (int32_t)m, op0, ops, plant_per_instance);
   a.W = st.in<cplx>(W, n * n);
   a.target = st.in<cplx>(target, ef.count); a.target_stride = ef.stride;
   std::vector<double> w;
@@ -1802,7 +1805,7 @@ int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plan
   m4q::GradArgs g{};
   g.roll.B = B; g.roll.N = N; g.roll.kind = plant_kind; g.roll.xs_mode = 2; g.roll.q_mode = q_mode;
   g.roll.dts = c.dts; g.roll.x0 = c.x0; g.roll.u_scale = c.u_scale; g.roll.u_stride = 0;
-  g.roll.op0 = c.op0; g.roll.op0_stride = c.op0_stride; g.roll.ops = c.ops; g.roll.ops_stride = c.ops_stride;
+  g.roll.plant = c.plant;
   g.roll.W = c.W; g.roll.target = c.target; g.roll.target_stride = c.target_stride;
   g.roll.xs = st.out<cplx>(nullptr, (size_t)B * ((size_t)N + 1) * n);
   g.roll.q = st.out<double>(nullptr, (size_t)B * (q_mode == 2 ? (size_t)N + 1 : 1));

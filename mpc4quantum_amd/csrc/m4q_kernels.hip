@@ -530,8 +530,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
         }
         xt_off = (unsigned)(b * a->xt_stride) * (unsigned)sizeof(S);
         ut_off = (unsigned)(b * a->ut_stride) * (unsigned)sizeof(double);
-        op0_off = (unsigned)(b * a->op0_stride) * (unsigned)sizeof(cplx);
-        ops_off = (unsigned)(b * a->ops_stride) * (unsigned)sizeof(cplx);
+        op0_off = (unsigned)(b * a->plant.op0_stride) * (unsigned)sizeof(cplx);
+        ops_off = (unsigned)(b * a->plant.ops_stride) * (unsigned)sizeof(cplx);
         step = row_begin;
         iter = 0;
         code = 0;
@@ -1078,7 +1078,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
         const bool measure = (step + 1) % mf == 0;
         cplx xn = czero();
         if (__any(ok && measure)) {
-          GView op0 = gview(a->op0, 0, 0), ops = gview(a->ops, 0, 0);
+          GView op0 = gview(a->plant.op0, 0, 0), ops = gview(a->plant.ops, 0, 0);
           op0.off = op0_off;
           ops.off = ops_off;
           const double dt = a->dt;
@@ -1834,8 +1834,8 @@ __global__ __launch_bounds__(64) void observed_plant_kernel(ObsPlantArgs a) {
     double u[NU];
 #pragma unroll
     for (int k = 0; k < NU; ++k) u[k] = gld(a.us, r.b * sU + (long)a.step * NU + k);
-    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const GView op0 = gview(a.plant.op0, r.q0 * a.plant.op0_stride, r.gl * (unsigned)a.plant.op0_stride);
+    const GView ops = gview(a.plant.ops, r.q0 * a.plant.ops_stride, r.gl * (unsigned)a.plant.ops_stride);
     const cplx zn = plant_hamiltonian<NPL, NU, DP>(z, u, op0, ops, a.dt, scratch, j, jj);
     const cplx x = observe_row<OBS>(zn, scratch, jj);
     if (live && jj < NPL) gst(a.zs, r.b * sZ + (long)(a.step + 1) * NPL + j, zn);
@@ -1862,8 +1862,8 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_kernel(PlantArgs a) {
     double u[NU];
 #pragma unroll
     for (int k = 0; k < NU; ++k) u[k] = gld(a.u, r.b * NU + k);
-    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const GView op0 = gview(a.plant.op0, r.q0 * a.plant.op0_stride, r.gl * (unsigned)a.plant.op0_stride);
+    const GView ops = gview(a.plant.ops, r.q0 * a.plant.ops_stride, r.gl * (unsigned)a.plant.ops_stride);
     cplx xn;
     M4Q_PLANT_STEP(PLANT, xn, x, u, op0, ops, a.dt, scratch, j, jj);
     if (r.valid && jj < NX) gst(a.x_next, r.b * NX + j, xn);
@@ -1882,8 +1882,8 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_rollout_kernel(RollArgs a) {
   const int nquads = quads_of(a.B);
   for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
     const QuadRow r(quad, g, a.B);
-    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const GView op0 = gview(a.plant.op0, r.q0 * a.plant.op0_stride, r.gl * (unsigned)a.plant.op0_stride);
+    const GView ops = gview(a.plant.ops, r.q0 * a.plant.ops_stride, r.gl * (unsigned)a.plant.ops_stride);
     const RollOut out(a, r.b, j, r.valid && L.lane_ok, r.valid && jj == 0);
     RollCtl ctl(a, r.b);
     double dtn = gld(a.dts, 0);
@@ -1918,8 +1918,8 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_feedback_kernel(FeedbackArgs
   const int nquads = quads_of(a.B);
   for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
     const QuadRow r(quad, g, a.B);
-    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const GView op0 = gview(a.plant.op0, r.q0 * a.plant.op0_stride, r.gl * (unsigned)a.plant.op0_stride);
+    const GView ops = gview(a.plant.ops, r.q0 * a.plant.ops_stride, r.gl * (unsigned)a.plant.ops_stride);
     const bool st0 = r.valid && jj == 0;
     const RollOut out(a, r.b, j, r.valid && L.lane_ok, st0);
     FeedbackRow<NX, NU> law(fa, r.b, j);
@@ -1970,8 +1970,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NX == 9 ? 1 
   const int nquads = quads_of(a.B);
   for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
     const QuadRow r(quad, g, a.B);
-    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const GView op0 = gview(a.plant.op0, r.q0 * a.plant.op0_stride, r.gl * (unsigned)a.plant.op0_stride);
+    const GView ops = gview(a.plant.ops, r.q0 * a.plant.ops_stride, r.gl * (unsigned)a.plant.ops_stride);
     const bool st0 = r.valid && jj == 0;
     const RollOut out(a, r.b, j, r.valid && L.lane_ok, st0);
     RollCtl ctl(a, r.b);
@@ -2033,17 +2033,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NX == 9 ? 1 
     const int b0 = (int)(r.q0 / a.T);                // the quad's first member (wave-uniform)
     const int b = (int)(r.b / a.T), t = (int)(r.b - (long)b * a.T);
     const unsigned bl = (unsigned)(b - b0);
-    const GView op0 = gview(a.op0, b0 * a.op0_stride, bl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, b0 * a.ops_stride, bl * (unsigned)a.ops_stride);
+    const GView op0 = gview(a.traj.plant.op0, b0 * a.traj.plant.op0_stride, bl * (unsigned)a.traj.plant.op0_stride);
+    const GView ops = gview(a.traj.plant.ops, b0 * a.traj.plant.ops_stride, bl * (unsigned)a.traj.plant.ops_stride);
     double u[NU], sc[NU];
 #pragma unroll
     for (int k = 0; k < NU; ++k) {
-      u[k] = gld(a.U, b * a.u_stride + (long)t * NU + k);
-      sc[k] = a.u_scale ? gld(a.u_scale, (long)b * NU + k) : 1.0;
+      u[k] = gld(a.traj.U, b * a.traj.u_stride + (long)t * NU + k);
+      sc[k] = a.traj.u_scale ? gld(a.traj.u_scale, (long)b * NU + k) : 1.0;
     }
-    const cplx x = gld(a.X, r.b * NX + j);
+    const cplx x = gld(a.traj.X, r.b * NX + j);
     cplx Bj[NU], dlt;
-    plant_lin_point<NX, NU, D, NC>(x, u, sc, op0, ops, gld(a.dts, t), scratch, j, jj, Bj, dlt);
+    plant_lin_point<NX, NU, D, NC>(x, u, sc, op0, ops, gld(a.traj.dts, t), scratch, j, jj, Bj, dlt);
     const bool st = r.valid && L.lane_ok;
     if (a.B_ls != nullptr && st) {
 #pragma unroll
@@ -2089,17 +2089,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NX == 9 ? 1 
     const int b0 = (int)(r.q0 / a.T);                // the quad's first member (wave-uniform)
     const int b = (int)(r.b / a.T), t = (int)(r.b - (long)b * a.T);
     const unsigned bl = (unsigned)(b - b0);
-    const GView op0 = gview(a.op0, b0 * a.op0_stride, bl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, b0 * a.ops_stride, bl * (unsigned)a.ops_stride);
+    const GView op0 = gview(a.traj.plant.op0, b0 * a.traj.plant.op0_stride, bl * (unsigned)a.traj.plant.op0_stride);
+    const GView ops = gview(a.traj.plant.ops, b0 * a.traj.plant.ops_stride, bl * (unsigned)a.traj.plant.ops_stride);
     double u[NU], sc[NU];
 #pragma unroll
     for (int k = 0; k < NU; ++k) {
-      u[k] = gld(a.U, b * a.u_stride + (long)t * NU + k);
-      sc[k] = a.u_scale ? gld(a.u_scale, (long)b * NU + k) : 1.0;
+      u[k] = gld(a.traj.U, b * a.traj.u_stride + (long)t * NU + k);
+      sc[k] = a.traj.u_scale ? gld(a.traj.u_scale, (long)b * NU + k) : 1.0;
     }
-    const cplx x = gld(a.X, r.b * NX + j);
+    const cplx x = gld(a.traj.X, r.b * NX + j);
     cplx Bj[NU], dlt;
-    plant_lin_point<NX, NU, D, NC>(x, u, sc, op0, ops, gld(a.dts, t), scratch, j, jj, Bj, dlt);
+    plant_lin_point<NX, NU, D, NC>(x, u, sc, op0, ops, gld(a.traj.dts, t), scratch, j, jj, Bj, dlt);
     if (r.valid && L.lane_ok) {
 #pragma unroll
       for (int k = 0; k < NU; ++k) gst(a.B_ws, (r.b * NX + j) * NU + k, Bj[k]);
@@ -2151,7 +2151,7 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_qp_kernel(PlantQpArgs a) {
       lo0[k] = band ? up - a.du : -a.sat;
       hi0[k] = band ? up + a.du : a.sat;
     }
-    const cplx x0 = a.x_init ? gld(a.x_init, r.b * NX + j) : gld(a.X, r.b * ((long)T * NX) + j);
+    const cplx x0 = a.x_init ? gld(a.x_init, r.b * NX + j) : gld(a.traj.X, r.b * ((long)T * NX) + j);
     const bool exact = (a.flags & QP_EXACT_BOX) != 0;
     // (the exact solver's ping-pong workspace, as qp_kernel)
     const GView Xa = gview(exact ? a.X_alt : a.X_opt, r.q0 * sX, r.gl * sX);
@@ -2415,30 +2415,34 @@ static int grid_for(int B) {
   return nquads < 4096 ? (nquads > 0 ? nquads : 1) : 4096;
 }
 
-// an auxiliary kernel over quads of members: grid_for(B) workgroups of one wavefront, `lds` bytes of dynamic LDS
+// The three ways an auxiliary kernel is launched, each with `lds` bytes of dynamic LDS and workgroups of one wavefront:
+// launch_rows: over quads of `count` rows of work - members, or (member, point) pairs - grid_for(count) workgroups
 template <class K, class A>
-static int launch_aux(K kern, const A& a, size_t lds, hipStream_t s) {
+static int launch_rows(K kern, const A& a, int count, size_t lds, hipStream_t s) {
   int rc = prep_lds(kern, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid_for(a.B)), dim3(64), lds, s, a);
+  hipLaunchKernelGGL(kern, dim3(grid_for(count)), dim3(64), lds, s, a);
+  return -(int)hipGetLastError();
+}
+// launch_aux: ... whose rows are the a.B members of the block
+template <class K, class A>
+static int launch_aux(K kern, const A& a, size_t lds, hipStream_t s) { return launch_rows(kern, a, a.B, lds, s); }
+// launch_members: one workgroup per member, 4096 at the most (the fits and the recursive update)
+template <class K, class A>
+[[maybe_unused]] static int launch_members(K kern, const A& a, int B, size_t lds, hipStream_t s) {
+  int rc = prep_lds(kern, lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(B < 4096 ? B : 4096), dim3(64), lds, s, a);
   return -(int)hipGetLastError();
 }
 [[maybe_unused]] constexpr int UNBUILT = -(int)hipErrorInvalidValue;      // what the launcher of a kernel this object does not hold returns
-// ... a feedback kernel, whose ensemble size is its rollout's
-template <class K>
-[[maybe_unused]] static int launch_feedback(K kern, const FeedbackArgs& a, size_t lds, hipStream_t s) {
-  int rc = prep_lds(kern, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid_for(a.roll.B)), dim3(64), lds, s, a);
-  return -(int)hipGetLastError();
-}
 
 #ifndef M4Q_NO_AUX
 constexpr size_t MODEL_LDS = sizeof(cplx) * (size_t)(ROWS * MODEL_ELEMS);
 static int launch_linearize(const LinArgs& a, hipStream_t s) { return launch_aux(linearize_kernel, a, MODEL_LDS, s); }
 static int launch_qp(const QpArgs& a, hipStream_t s) { return launch_aux(qp_kernel, a, 0, s); }
 static int launch_model_rollout(const RollArgs& a, hipStream_t s) { return launch_aux(model_rollout_kernel, a, MODEL_LDS, s); }
-static int launch_model_feedback(const FeedbackArgs& a, hipStream_t s) { return launch_feedback(model_feedback_kernel, a, MODEL_LDS, s); }
+static int launch_model_feedback(const FeedbackArgs& a, hipStream_t s) { return launch_rows(model_feedback_kernel, a, a.roll.B, MODEL_LDS, s); }
 // (a partial specialisation, so that the kernel is instantiated only for the shapes whose layout fits)
 template <bool FITS, int N_ = NX>
 struct FitLaunch {
@@ -2449,34 +2453,11 @@ struct FitLaunch {
 };
 template <int N_>
 struct FitLaunch<true, N_> {
-  static int run(const FitArgs& a, hipStream_t s) {
-    constexpr size_t lds = FitLayout<N_, NU, ORDER>::BYTES;
-    int rc = prep_lds(dmdc_fit_kernel<N_, NU, ORDER>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((dmdc_fit_kernel<N_, NU, ORDER>), dim3(a.B < 4096 ? a.B : 4096), dim3(64), lds, s, a);
-    return -(int)hipGetLastError();
-  }
-  static int run_qr(const FitArgs& a, hipStream_t s) {
-    constexpr size_t lds = FitLayout<N_, NU, ORDER>::BYTES;
-    int rc = prep_lds(dmdc_fit_qr_kernel<N_, NU, ORDER>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((dmdc_fit_qr_kernel<N_, NU, ORDER>), dim3(a.B < 4096 ? a.B : 4096), dim3(64), lds, s, a);
-    return -(int)hipGetLastError();
-  }
-  static int run_refit(const RefitArgs& a, hipStream_t s) {
-    constexpr size_t lds = FitLayout<N_, NU, ORDER>::BYTES;
-    int rc = prep_lds(dmdc_refit_kernel<N_, NU, ORDER>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((dmdc_refit_kernel<N_, NU, ORDER>), dim3(a.fit.B < 4096 ? a.fit.B : 4096), dim3(64), lds, s, a);
-    return -(int)hipGetLastError();
-  }
-  static int run_refit_qr(const RefitArgs& a, hipStream_t s) {
-    constexpr size_t lds = FitLayout<N_, NU, ORDER>::BYTES;
-    int rc = prep_lds(dmdc_refit_qr_kernel<N_, NU, ORDER>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((dmdc_refit_qr_kernel<N_, NU, ORDER>), dim3(a.fit.B < 4096 ? a.fit.B : 4096), dim3(64), lds, s, a);
-    return -(int)hipGetLastError();
-  }
+  static constexpr size_t LDS = FitLayout<N_, NU, ORDER>::BYTES;
+  static int run(const FitArgs& a, hipStream_t s) { return launch_members(dmdc_fit_kernel<N_, NU, ORDER>, a, a.B, LDS, s); }
+  static int run_qr(const FitArgs& a, hipStream_t s) { return launch_members(dmdc_fit_qr_kernel<N_, NU, ORDER>, a, a.B, LDS, s); }
+  static int run_refit(const RefitArgs& a, hipStream_t s) { return launch_members(dmdc_refit_kernel<N_, NU, ORDER>, a, a.fit.B, LDS, s); }
+  static int run_refit_qr(const RefitArgs& a, hipStream_t s) { return launch_members(dmdc_refit_qr_kernel<N_, NU, ORDER>, a, a.fit.B, LDS, s); }
 };
 constexpr bool FIT_FITS = FitLayout<NX, NU, ORDER>::FITS;
 constexpr int FIT_LDS = FIT_FITS ? (int)FitLayout<NX, NU, ORDER>::BYTES : 0;
@@ -2492,11 +2473,7 @@ template <int N_>
 struct OnlineLaunch<true, N_> {
   template <bool HERM>
   static int go(const OnlineArgs& a, hipStream_t s) {
-    constexpr size_t lds = OnlineLayout<N_, NU, ORDER>::BYTES;
-    int rc = prep_lds(online_dmdc_kernel<N_, NU, ORDER, HERM>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((online_dmdc_kernel<N_, NU, ORDER, HERM>), dim3(a.B < 4096 ? a.B : 4096), dim3(64), lds, s, a);
-    return -(int)hipGetLastError();
+    return launch_members(online_dmdc_kernel<N_, NU, ORDER, HERM>, a, a.B, OnlineLayout<N_, NU, ORDER>::BYTES, s);
   }
   static int run(const OnlineArgs& a, int hermitian, hipStream_t s) { return hermitian ? go<true>(a, s) : go<false>(a, s); }
 };
@@ -2540,39 +2517,37 @@ static int launch_model_feedback(const FeedbackArgs&, hipStream_t) { return UNBU
 #endif
 
 #ifndef M4Q_VARIANT_GEN
-// the kernel of a.kind among those of one family: kernel_of(ic<PLANT>) names them (plant_kernel, plant_rollout_kernel)
-template <class A, class F>
-static int launch_by_plant(const A& a, hipStream_t s, F kernel_of) {
+// The kernel of plant `kind` among those of one family, over quads of `count` rows: kernel_of(ic<PLANT>) names the family's kernel,
+// lds_elems(ic<PLANT>) the complex LDS elements it asks for per row.  GEN: the family has a kernel for the generator plant, which
+// then serves every kind that is neither of the other two; without one such a kind is UNBUILT, as the process plant is where n is
+// no fourth power and every plant where n is no square.  Only the kernels of the branches taken are instantiated.
+template <bool GEN, class A, class F, class L>
+static int launch_by_plant(const A& a, int kind, int count, hipStream_t s, F kernel_of, L lds_elems) {
   if constexpr (!SQUARE) {
     return UNBUILT;
   } else {
-    constexpr size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
-    if (a.kind == PLANT_HAMILTONIAN) return launch_aux(kernel_of(ic<PLANT_HAMILTONIAN>{}), a, lds, s);
-    if (a.kind == PLANT_PROCESS) {
-      if constexpr (QUARTIC) return launch_aux(kernel_of(ic<PLANT_PROCESS>{}), a, lds, s);
+    const auto go = [&](auto plant) { return launch_rows(kernel_of(plant), a, count, sizeof(cplx) * (size_t)(ROWS * lds_elems(plant)), s); };
+    if (kind == PLANT_HAMILTONIAN) return go(ic<PLANT_HAMILTONIAN>{});
+    if (kind == PLANT_PROCESS) {
+      if constexpr (QUARTIC) return go(ic<PLANT_PROCESS>{});
       else return UNBUILT;
     }
-    return launch_aux(kernel_of(ic<PLANT_GENERATOR>{}), a, lds, s);
+    if constexpr (GEN) return go(ic<PLANT_GENERATOR>{});
+    else return UNBUILT;
   }
 }
+// (LDS per row: the plant step's scratch; what the block exponential of the linearisation asks for; none)
+constexpr auto step_lds = [](auto) { return SCRATCH_ELEMS; };
+constexpr auto lin_lds = [](auto plant) { return plant_lin_lds_elems<decltype(plant)::value>(); };
+[[maybe_unused]] constexpr auto no_lds = [](auto) { return 0; };
 static int launch_plant(const PlantArgs& a, hipStream_t s) {
-  return launch_by_plant(a, s, [](auto plant) { return plant_kernel<decltype(plant)::value>; });
+  return launch_by_plant<true>(a, a.kind, a.B, s, [](auto plant) { return plant_kernel<decltype(plant)::value>; }, step_lds);
 }
 static int launch_plant_rollout(const RollArgs& a, hipStream_t s) {
-  return launch_by_plant(a, s, [](auto plant) { return plant_rollout_kernel<decltype(plant)::value>; });
+  return launch_by_plant<true>(a, a.kind, a.B, s, [](auto plant) { return plant_rollout_kernel<decltype(plant)::value>; }, step_lds);
 }
 static int launch_plant_feedback(const FeedbackArgs& a, hipStream_t s) {
-  if constexpr (!SQUARE) {
-    return UNBUILT;
-  } else {
-    constexpr size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
-    if (a.roll.kind == PLANT_HAMILTONIAN) return launch_feedback(plant_feedback_kernel<PLANT_HAMILTONIAN>, a, lds, s);
-    if (a.roll.kind == PLANT_PROCESS) {
-      if constexpr (QUARTIC) return launch_feedback(plant_feedback_kernel<PLANT_PROCESS>, a, lds, s);
-      else return UNBUILT;
-    }
-    return launch_feedback(plant_feedback_kernel<PLANT_GENERATOR>, a, lds, s);
-  }
+  return launch_by_plant<true>(a, a.roll.kind, a.roll.B, s, [](auto plant) { return plant_feedback_kernel<decltype(plant)::value>; }, step_lds);
 }
 
 static int launch_noise(const NoiseArgs& a, hipStream_t s) {
@@ -2603,56 +2578,26 @@ static int launch_grad_reduce(const GradArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((nm + 1 + 255) / 256)), dim3(256), 0, s, f);
   return -(int)hipGetLastError();
 }
-// a gradient kernel over quads of members (launch_aux's launch), then the reduction when the call asks for one
-template <class K>
-static int launch_grad(K kern, const GradArgs& a, size_t lds, hipStream_t s) {
-  int rc = prep_lds(kern, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid_for(a.roll.B)), dim3(64), lds, s, a);
-  if (hipError_t e = hipGetLastError()) return -(int)e;
-  return launch_grad_reduce(a, s);
-}
+// a gradient kernel over quads of members, then the reduction when the call asks for one
 static int launch_plant_grad(const GradArgs& a, hipStream_t s) {
-  if constexpr (!SQUARE) {
-    return UNBUILT;
-  } else {
-    if (a.roll.kind == PLANT_HAMILTONIAN)
-      return launch_grad(plant_rollout_grad_kernel<PLANT_HAMILTONIAN>, a, sizeof(cplx) * (size_t)(ROWS * grad_lds_elems<PLANT_HAMILTONIAN>()), s);
-    if constexpr (QUARTIC) {
-      if (a.roll.kind == PLANT_PROCESS)
-        return launch_grad(plant_rollout_grad_kernel<PLANT_PROCESS>, a, sizeof(cplx) * (size_t)(ROWS * grad_lds_elems<PLANT_PROCESS>()), s);
-    }
-    return UNBUILT;
-  }
+  const int rc = launch_by_plant<false>(a, a.roll.kind, a.roll.B, s, [](auto plant) { return plant_rollout_grad_kernel<decltype(plant)::value>; },
+                                        [](auto plant) { return grad_lds_elems<decltype(plant)::value>(); });
+  return rc ? rc : launch_grad_reduce(a, s);
 }
 // a linearisation kernel over quads of (member, point) pairs
-template <class K>
-static int launch_plant_lin(K kern, const PlantLinArgs& a, size_t lds, hipStream_t s) {
-  int rc = prep_lds(kern, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid_for(a.B * a.T)), dim3(64), lds, s, a);
-  return -(int)hipGetLastError();
-}
 static int launch_plant_linearize(const PlantLinArgs& a, hipStream_t s) {
-  if constexpr (!SQUARE) {
-    return UNBUILT;
-  } else {
-    if (a.kind == PLANT_HAMILTONIAN)
-      return launch_plant_lin(plant_linearize_kernel<PLANT_HAMILTONIAN>, a, sizeof(cplx) * (size_t)(ROWS * plant_lin_lds_elems<PLANT_HAMILTONIAN>()), s);
-    if constexpr (QUARTIC) {
-      if (a.kind == PLANT_PROCESS)
-        return launch_plant_lin(plant_linearize_kernel<PLANT_PROCESS>, a, sizeof(cplx) * (size_t)(ROWS * plant_lin_lds_elems<PLANT_PROCESS>()), s);
-    }
-    return UNBUILT;
-  }
+  return launch_by_plant<false>(a, a.kind, a.B * a.T, s, [](auto plant) { return plant_linearize_kernel<decltype(plant)::value>; }, lin_lds);
 }
 #ifndef M4Q_NO_AUX
-static int launch_model_grad(const GradArgs& a, hipStream_t s) { return launch_grad(model_rollout_grad_kernel, a, MODEL_LDS, s); }
+static int launch_model_grad(const GradArgs& a, hipStream_t s) {
+  const int rc = launch_rows(model_rollout_grad_kernel, a, a.roll.B, MODEL_LDS, s);
+  return rc ? rc : launch_grad_reduce(a, s);
+}
 #else
 static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 #endif
-// the S shared sequences of MultiArgs against every member (m4q_rollout_multi.h): launch_aux's launch over quads of members with the
-// rollouts' LDS, then - a.F set - the two passes of the ordered reduction over J [B][S] on the same stream.  grad_reduce's element
+// the S shared sequences of MultiArgs against every member (m4q_rollout_multi.h): over quads of members with the rollouts' LDS,
+// then - a.F set - the two passes of the ordered reduction over J [B][S] on the same stream.  grad_reduce's element
 // nm is row i's vals[i][nm] when q_cols is 0, so nm = S - 1 over rows of S covers the S columns.
 static int launch_multi_reduce(const MultiArgs& a, hipStream_t s) {
   if (!a.F) return 0;
@@ -2672,17 +2617,8 @@ static int launch_multi_reduce(const MultiArgs& a, hipStream_t s) {
   return -(int)hipGetLastError();
 }
 static int launch_plant_multi(const MultiArgs& a, hipStream_t s) {
-  if constexpr (!SQUARE) {
-    return UNBUILT;
-  } else {
-    constexpr size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
-    int rc = UNBUILT;
-    if (a.kind == PLANT_HAMILTONIAN) rc = launch_aux(plant_rollout_multi_kernel<PLANT_HAMILTONIAN>, a, lds, s);
-    if constexpr (QUARTIC) {
-      if (a.kind == PLANT_PROCESS) rc = launch_aux(plant_rollout_multi_kernel<PLANT_PROCESS>, a, lds, s);
-    }
-    return rc ? rc : launch_multi_reduce(a, s);
-  }
+  const int rc = launch_by_plant<false>(a, a.kind, a.B, s, [](auto plant) { return plant_rollout_multi_kernel<decltype(plant)::value>; }, step_lds);
+  return rc ? rc : launch_multi_reduce(a, s);
 }
 #else
 static int launch_plant_multi(const MultiArgs&, hipStream_t) { return UNBUILT; }
@@ -2697,44 +2633,15 @@ static int launch_plant_linearize(const PlantLinArgs&, hipStream_t) { return UNB
 
 #ifndef M4Q_NO_AUX
 // the two kernels of the QP on the plant's own linearisation, on one stream: the factors of every (member, point) pair, then the
-// sweep over quads of members (launch_aux's launch)
-template <class KF, class KQ>
-static int launch_plant_qp_pair(KF factor, KQ sweep, const PlantQpArgs& a, size_t lds, hipStream_t s) {
-  int rc = prep_lds(factor, lds);
-  if (rc) return rc;
-  const int units = a.B * a.T;
-  hipLaunchKernelGGL(factor, dim3(grid_for(units)), dim3(64), lds, s, a);
-  if (hipError_t e = hipGetLastError()) return -(int)e;
-  return launch_aux(sweep, a, 0, s);
-}
+// sweep over quads of members
 static int launch_plant_qp(const PlantQpArgs& a, hipStream_t s) {
-  if constexpr (!SQUARE) {
-    return UNBUILT;
-  } else {
-    if (a.kind == PLANT_HAMILTONIAN)
-      return launch_plant_qp_pair(plant_factor_kernel<PLANT_HAMILTONIAN>, plant_qp_kernel<PLANT_HAMILTONIAN>, a,
-                                  sizeof(cplx) * (size_t)(ROWS * plant_lin_lds_elems<PLANT_HAMILTONIAN>()), s);
-    if constexpr (QUARTIC) {
-      if (a.kind == PLANT_PROCESS)
-        return launch_plant_qp_pair(plant_factor_kernel<PLANT_PROCESS>, plant_qp_kernel<PLANT_PROCESS>, a,
-                                    sizeof(cplx) * (size_t)(ROWS * plant_lin_lds_elems<PLANT_PROCESS>()), s);
-    }
-    return UNBUILT;
-  }
+  const int rc = launch_by_plant<false>(a, a.kind, a.B * a.T, s, [](auto plant) { return plant_factor_kernel<decltype(plant)::value>; }, lin_lds);
+  return rc ? rc : launch_by_plant<false>(a, a.kind, a.B, s, [](auto plant) { return plant_qp_kernel<decltype(plant)::value>; }, no_lds);
 }
-// the step between two of them (m4q_plant_step.h): launch_aux's launch over quads of members, the rollouts' LDS
+// the step between two of them (m4q_plant_step.h): over quads of members, the rollouts' LDS
 template <bool CLOSED>
 static int launch_plant_step_of(const PlantStepArgs& a, hipStream_t s) {
-  if constexpr (!SQUARE) {
-    return UNBUILT;
-  } else {
-    constexpr size_t lds = sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS);
-    if (a.kind == PLANT_HAMILTONIAN) return launch_aux(plant_step_kernel<PLANT_HAMILTONIAN, CLOSED>, a, lds, s);
-    if constexpr (QUARTIC) {
-      if (a.kind == PLANT_PROCESS) return launch_aux(plant_step_kernel<PLANT_PROCESS, CLOSED>, a, lds, s);
-    }
-    return UNBUILT;
-  }
+  return launch_by_plant<false>(a, a.kind, a.B, s, [](auto plant) { return plant_step_kernel<decltype(plant)::value, CLOSED>; }, step_lds);
 }
 static int launch_plant_step(const PlantStepArgs& a, hipStream_t s) {
   return a.closed ? launch_plant_step_of<true>(a, s) : launch_plant_step_of<false>(a, s);

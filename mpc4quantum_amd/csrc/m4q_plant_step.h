@@ -18,7 +18,7 @@
 // registers and sums J = sum_t (x_t - xb_t)^H Q_t (x_t - xb_t) + (u_t - ub_t)^T R_t (u_t - ub_t) + the terminal term.  Passes
 // 0 .. steps-1 are the candidates clip(U + 2^-p D), D = U_opt - U (one fma: 2^-p D is exact), and store nothing; the last pass is
 // the winner again - THE SAME loop body, stores enabled, so its states and its J have the candidate's bits - and writes the controls,
-// the T linearisation points where plant_factor_kernel reads them ([B][T][n]: PlantQpArgs::X has no member stride) and the full
+// the T linearisation points where plant_factor_kernel reads them ([B][T][n]: PlantTraj::X has no member stride) and the full
 // trajectory [B][T + 1][n].  iter < 0 is the initial roll: no candidates, the last pass on clip(U0).
 // A member whose status is not SQP_RUNNING keeps everything it has; a quad of such members is skipped.
 //
@@ -67,8 +67,8 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_step_kernel(PlantStepArgs a)
     const QuadRow r(quad, g, a.B);
     const bool live = r.valid && (init || gld(a.status, r.b) == SQP_RUNNING);
     if (!__any(live)) continue;                      // (wave-uniform: every lane stays in step for the broadcasts below)
-    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const GView op0 = gview(a.plant.op0, r.q0 * a.plant.op0_stride, r.gl * (unsigned)a.plant.op0_stride);
+    const GView ops = gview(a.plant.ops, r.q0 * a.plant.ops_stride, r.gl * (unsigned)a.plant.ops_stride);
     const GView xbm = gview(a.X_bm, r.q0 * a.xbm_stride, r.gl * (unsigned)a.xbm_stride);
     const GView ubm = gview(a.U_bm, r.q0 * a.ubm_stride, r.gl * (unsigned)a.ubm_stride);
     const GView U0 = gview(a.U0, r.q0 * a.u0_stride, r.gl * (unsigned)a.u0_stride);

@@ -25,8 +25,8 @@ __global__ __launch_bounds__(64) M4Q_OCC void plant_rollout_multi_kernel(MultiAr
   const M4Q_GLOBAL cplx* Wr = a.W + j * NX;          // row j of W
   for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
     const QuadRow r(quad, g, a.B);
-    const GView op0 = gview(a.op0, r.q0 * a.op0_stride, r.gl * (unsigned)a.op0_stride);
-    const GView ops = gview(a.ops, r.q0 * a.ops_stride, r.gl * (unsigned)a.ops_stride);
+    const GView op0 = gview(a.plant.op0, r.q0 * a.plant.op0_stride, r.gl * (unsigned)a.plant.op0_stride);
+    const GView ops = gview(a.plant.ops, r.q0 * a.plant.ops_stride, r.gl * (unsigned)a.plant.ops_stride);
     const bool st0 = r.valid && jj == 0;
     double sc[NU];
 #pragma unroll

@@ -167,11 +167,11 @@ def test_aux_rule_lines_read_as_mirrored():
     assert k.count("#if defined(M4Q_PLANT_ONLY) || defined(M4Q_VARIANT_GEN)\n#define M4Q_NO_AUX 1\n") == 1
     assert b.count('(["-DM4Q_PLANT_ONLY"] if plant_only else [])') == 1
     assert b.count('return [(int(a), int(b), int(c), "plant-only" in rest)') == 1
-    assert k.count("#ifndef M4Q_NO_AUX\nstatic int launch_model_grad(const GradArgs& a, hipStream_t s) { return launch_grad("
-                   "model_rollout_grad_kernel, a, MODEL_LDS, s); }\n") == 1
+    assert k.count("#ifndef M4Q_NO_AUX\nstatic int launch_model_grad(const GradArgs& a, hipStream_t s) {\n  const int rc = launch_rows("
+                   "model_rollout_grad_kernel, a, a.roll.B, MODEL_LDS, s);\n") == 1
     for line in ("static int launch_model_rollout(const RollArgs& a, hipStream_t s) { return launch_aux(model_rollout_kernel, a, MODEL_LDS, s); }",
-                 "static int launch_model_feedback(const FeedbackArgs& a, hipStream_t s) { return launch_feedback(model_feedback_kernel, a, "
-                 "MODEL_LDS, s); }"):
+                 "static int launch_model_feedback(const FeedbackArgs& a, hipStream_t s) { return launch_rows(model_feedback_kernel, a, "
+                 "a.roll.B, MODEL_LDS, s); }"):
         assert k.count(line) == 1, line
     # FitLayout / OnlineLayout
     assert fit_h.count("constexpr size_t FIT_LDS_LIMIT = 160 * 1024;") == 1
@@ -198,46 +198,53 @@ def test_aux_rule_lines_read_as_mirrored():
         assert k.count(line) == 1, line
     assert capi.count("  if (sh->fit_lds_bytes == 0)\n    return fail(M4Q_E_UNSUPPORTED, ") == 1
     assert capi.count("  if (sh->online_lds_bytes == 0)\n    return fail(M4Q_E_UNSUPPORTED, ") == 1
-    # the plant dispatch: launch_by_plant (plant_kernel, plant_rollout_kernel) and launch_plant_feedback
+    # the plant dispatch, written once: launch_by_plant<GEN>, GEN for the families with a generator-plant kernel
     body = k[k.index("static int launch_by_plant("):k.index("static int launch_plant(const PlantArgs& a")]
     for line in ("  if constexpr (!SQUARE) {\n    return UNBUILT;\n",
-                 "    if (a.kind == PLANT_HAMILTONIAN) return launch_aux(kernel_of(ic<PLANT_HAMILTONIAN>{}), a, lds, s);\n",
-                 "    if (a.kind == PLANT_PROCESS) {\n      if constexpr (QUARTIC) return launch_aux(kernel_of(ic<PLANT_PROCESS>{}), a, lds, s);\n"
+                 "    const auto go = [&](auto plant) { return launch_rows(kernel_of(plant), a, count, sizeof(cplx) * (size_t)(ROWS * "
+                 "lds_elems(plant)), s); };\n",
+                 "    if (kind == PLANT_HAMILTONIAN) return go(ic<PLANT_HAMILTONIAN>{});\n",
+                 "    if (kind == PLANT_PROCESS) {\n      if constexpr (QUARTIC) return go(ic<PLANT_PROCESS>{});\n"
                  "      else return UNBUILT;\n    }\n",
-                 "    return launch_aux(kernel_of(ic<PLANT_GENERATOR>{}), a, lds, s);\n"):
+                 "    if constexpr (GEN) return go(ic<PLANT_GENERATOR>{});\n    else return UNBUILT;\n"):
         assert body.count(line) == 1, line
-    body = k[k.index("static int launch_plant_feedback(const FeedbackArgs& a"):k.index("static int launch_noise(")]
-    for line in ("  if constexpr (!SQUARE) {\n    return UNBUILT;\n",
-                 "    if (a.roll.kind == PLANT_HAMILTONIAN) return launch_feedback(plant_feedback_kernel<PLANT_HAMILTONIAN>, a, lds, s);\n",
-                 "    if (a.roll.kind == PLANT_PROCESS) {\n      if constexpr (QUARTIC) return launch_feedback(plant_feedback_kernel<PLANT_PROCESS>, "
-                 "a, lds, s);\n      else return UNBUILT;\n    }\n",
-                 "    return launch_feedback(plant_feedback_kernel<PLANT_GENERATOR>, a, lds, s);\n"):
-        assert body.count(line) == 1, line
+    # plant_kernel, plant_rollout_kernel and plant_feedback_kernel: all three plants
+    for line in ("  return launch_by_plant<true>(a, a.kind, a.B, s, [](auto plant) { return plant_kernel<decltype(plant)::value>; }, step_lds);\n",
+                 "  return launch_by_plant<true>(a, a.kind, a.B, s, [](auto plant) { return plant_rollout_kernel<decltype(plant)::value>; }, "
+                 "step_lds);\n",
+                 "  return launch_by_plant<true>(a, a.roll.kind, a.roll.B, s, [](auto plant) { return plant_feedback_kernel<decltype(plant)::"
+                 "value>; }, step_lds);\n"):
+        assert k.count(line) == 1, line
+    assert k.count("launch_by_plant<true>(") == 3
     # the gradient and the linearisation: Hamiltonian, process where QUARTIC, nothing else - and the entry points refuse the generator
     body = k[k.index("static int launch_plant_grad("):k.index("// a linearisation kernel over quads")]
-    assert body.count("    if (a.roll.kind == PLANT_HAMILTONIAN)\n      return launch_grad(plant_rollout_grad_kernel<PLANT_HAMILTONIAN>, ") == 1
-    assert body.count("    if constexpr (QUARTIC) {\n      if (a.roll.kind == PLANT_PROCESS)\n        return launch_grad("
-                      "plant_rollout_grad_kernel<PLANT_PROCESS>, ") == 1
-    assert body.count("    return UNBUILT;\n") == 2 and "PLANT_GENERATOR" not in body
+    assert body.count("  const int rc = launch_by_plant<false>(a, a.roll.kind, a.roll.B, s, [](auto plant) { return plant_rollout_grad_kernel<"
+                      "decltype(plant)::value>; },\n") == 1
+    assert body.count("launch_by_plant<") == 1 and "PLANT_GENERATOR" not in body
     body = k[k.index("static int launch_plant_linearize("):k.index("#ifndef M4Q_NO_AUX\nstatic int launch_model_grad(")]
-    assert body.count("    if (a.kind == PLANT_HAMILTONIAN)\n      return launch_plant_lin(plant_linearize_kernel<PLANT_HAMILTONIAN>, ") == 1
-    assert body.count("    if constexpr (QUARTIC) {\n      if (a.kind == PLANT_PROCESS)\n        return launch_plant_lin("
-                      "plant_linearize_kernel<PLANT_PROCESS>, ") == 1
-    assert body.count("    return UNBUILT;\n") == 2 and "PLANT_GENERATOR" not in body
-    assert capi.count('  if (plant_kind == M4Q_PLANT_GENERATOR)\n    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no gradient '
-                      'kernel ') == 1
-    assert capi.count('  if (plant_kind == M4Q_PLANT_GENERATOR)\n    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no '
-                      'linearisation kernel ') == 1
+    assert body.count("  return launch_by_plant<false>(a, a.kind, a.B * a.T, s, [](auto plant) { return plant_linearize_kernel<"
+                      "decltype(plant)::value>; }, lin_lds);\n") == 1
+    assert body.count("launch_by_plant<") == 1 and "PLANT_GENERATOR" not in body
+    assert capi.count('  if (lacks && kind == M4Q_PLANT_GENERATOR)\n    return fail(M4Q_E_UNSUPPORTED, "%s: the generator plant has no %s '
+                      '(its block matrix has (1 + m) n > 16 columns): %s", who, lacks, advice);\n') == 1
+    assert capi.count('  if (int rc = check_plant_kind(who, /*named=*/false, plant_kind, dim_x, "gradient kernel",\n') == 1
+    assert capi.count('  if (int rc = check_plant_kind(who, /*named=*/false, plant_kind, dim_x, "linearisation kernel",\n') == 1
+    assert capi.count("  if (int rc = check_plant_kind(who, /*named=*/false, plant_kind, dim_x, nullptr, nullptr)) return rc;\n") == 2
     # one object per (n, m) serves every plant family, plant-only shapes included; the model families need the shape's own object
-    assert capi.count("  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);") == 5
+    assert capi.count("  const m4q::ShapeOps* sh = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);") == 1      # m4q_plant_step_batch
+    assert capi.count("  *found = find_shape_any_order(dim_x, dim_u, /*plant_ok=*/true);") == 1                        # plant_shape
+    assert capi.count("  if (int rc = plant_shape(who, /*named=*/false, dim_x, dim_u, /*needs_qp=*/false, &sh)) return rc;") == 4
     assert capi.count("    if (s->nx == nx && s->nu == nu && s->order == order && (plant_ok || !s->plant_only)) return s;") == 1
     # the grid cap of every auxiliary launch
     assert k.count("constexpr int ROWS = 4;") == 1
     assert k.count("  const int nquads = (B + ROWS - 1) / ROWS;\n  return nquads < 4096 ? (nquads > 0 ? nquads : 1) : 4096;\n") == 1
-    assert k.count("dim3(a.B < 4096 ? a.B : 4096), dim3(64), lds, s, a);") == 3          # fit, fit_qr, online
-    assert k.count("dim3(a.fit.B < 4096 ? a.fit.B : 4096), dim3(64), lds, s, a);") == 2  # refit, refit_qr
-    assert k.count("dim3(grid_for(a.B)), dim3(64), lds, s, a);") == 1 and k.count("dim3(grid_for(a.roll.B)), dim3(64), lds, s, a);") == 2
-    assert k.count("dim3(grid_for(a.B * a.T)), dim3(64), lds, s, a);") == 1
+    assert k.count("  hipLaunchKernelGGL(kern, dim3(B < 4096 ? B : 4096), dim3(64), lds, s, a);") == 1   # launch_members
+    assert k.count(", a, a.B, LDS, s); }") == 2 and k.count(", a, a.B, OnlineLayout<N_, NU, ORDER>::BYTES, s);") == 1   # fit, fit_qr, online
+    assert k.count(", a, a.fit.B, LDS, s); }") == 2                                                       # refit, refit_qr
+    assert k.count("launch_members(") == 6
+    assert k.count("  hipLaunchKernelGGL(kern, dim3(grid_for(count)), dim3(64), lds, s, a);") == 1       # launch_rows
+    assert k.count("{ return launch_rows(kern, a, a.B, lds, s); }") == 1                                  # launch_aux
+    assert k.count("hipLaunchKernelGGL(") == 8     # mpc_kernel; launch_rows, launch_members; noise; the two reductions' two passes
     assert (kv.AUX_GRID, kv.ROWS, kv.QUAD_WRAP, kv.FIT_LDS_LIMIT) == (4096, 4, 16384, 160 * 1024)
 
 
