@@ -352,6 +352,29 @@ M4Q_API int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int3
                                   double step0, double tol, double gtol, double* U, double* cost, double* cost_hist,
                                   double* alpha_hist, double* pgrad_hist, int32_t* n_iter, int32_t* status, double* J);
 
+/* The model twins of the two calls above: the same multi rollout and the same optimiser on the members' MODELS
+ * (models [B|1][n][n(1+P)] c, the step of m4q_model_rollout_batch) - dissipative dynamics through their discretised generators
+ * (m4q_discretize_batch), identified models (m4q_dmdc_fit_batch), any shape with a model kernel.  mpc4quantum_amd/model_robust.py
+ * is the definition: plant_robust.py's loop on model_rollout_grad_reference(reduce) and model_rollout_multi_reference.
+ * m4q_model_rollout_multi_batch: J[.][s] has the bits of m4q_model_rollout_batch's figure under us[s] (q_mode 2: of its N + 1
+ * columns added with t ascending from 0.0); F as above.  The member's model is staged once per launch, not once per sequence.
+ * m4q_model_robust_batch: m4q_plant_robust_batch's loop, step for step, on m4q_model_rollout_grad_batch with reduce and the multi
+ * rollout's kernel; the ensemble - models, x0, u_scale, W, targets, weights - and every workspace are staged once.
+ * Refusals: those of m4q_model_rollout_grad_batch with reduce (M4Q_E_UNSUPPORTED: no model kernel for (dim_x, dim_u, order);
+ * M4Q_E_BADARG: B or N < 1, a missing x0, sequence, W, target or models, q_mode outside 1-2, a non-finite or negative weight), then
+ * the ranges of the plant twins (S, iters, steps, mem, sat, step0, tol, gtol, the required outputs; J and F both NULL).  All
+ * checked before a device is asked for, under the entry's name. */
+M4Q_API int m4q_model_rollout_multi_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, int32_t S,
+                                  const double* us, const double* u_scale, const double* models, int32_t model_per_instance,
+                                  const double* W, const double* target, int32_t target_per_instance, int32_t q_mode,
+                                  const double* weights, double* J, double* F);
+M4Q_API int m4q_model_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* U0,
+                                  const double* u_scale, const double* models, int32_t model_per_instance, const double* W,
+                                  const double* target, int32_t target_per_instance, int32_t q_mode, const double* weights,
+                                  double sat, int32_t iters, int32_t steps, int32_t mem, double step0, double tol, double gtol,
+                                  double* U, double* cost, double* cost_hist, double* alpha_hist, double* pgrad_hist, int32_t* n_iter,
+                                  int32_t* status, double* J);
+
 /* A stored feedback law run on B members over N steps in ONE launch: the tier between the open-loop rollouts above and the closed
  * loop that re-solves a QP at every step - time-varying gains around a nominal trajectory with saturation, a slew band and
  * measurement noise.  mpc4quantum_amd/feedback.py (FeedbackLaw, plant_feedback_reference, model_feedback_reference) is the

@@ -25,6 +25,8 @@ from .plant_sqp import plant_sqp_batch, plant_sqp_reference  # noqa: F401
 from .plant_ilqr import plant_ilqr_batch, plant_ilqr_reference  # noqa: F401
 from .plant_robust import (plant_robust_batch, plant_robust_reference, plant_rollout_multi_batch,  # noqa: F401
                            plant_rollout_multi_reference)
+from .model_robust import (model_robust_batch, model_robust_reference, model_rollout_multi_batch,  # noqa: F401
+                           model_rollout_multi_reference)
 from .rollout import model_rollout_batch, plant_rollout_batch  # noqa: F401
 from .session import EnsembleSession  # noqa: F401
 from .vectorize import discretize_homogeneous, discretize_homogeneous_batch, liouvillian, vectorize_me  # noqa: F401

@@ -88,6 +88,11 @@ PROTOTYPES = {
     "m4q_plant_robust_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _dp, _dp, _dp, _dp, _i32, _dp, _dp, _i32, _i32, _dp,
                                          C.c_double, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double,
                                          _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]),
+    "m4q_model_rollout_multi_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _i32, _i32, _dp,
+                                                _dp, _dp]),
+    "m4q_model_robust_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _dp, _dp, _i32, _dp, _dp, _i32, _i32, _dp,
+                                         C.c_double, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double,
+                                         _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]),
     "m4q_plant_feedback_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _dp, _dp, _dp, _i32, C.c_double, _i32, C.c_double, _dp,
                                            _i32, _dp, _dp, _dp, _i32, _i32, _dp, _i32, C.c_uint64, C.c_uint64, _dp, _dp, _i32, _i32, _dp,
                                            _i32, _dp, _dp, _ip, _ip]),

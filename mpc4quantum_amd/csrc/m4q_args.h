@@ -183,6 +183,20 @@ struct MultiArgs {
   M4Q_P(const double) weights;
   M4Q_P(double) partial; M4Q_P(double) F;
 };
+// ... through the members' models instead of their plants (m4q_model_rollout_multi_batch and the line search of
+// m4q_model_robust_batch; m4q_model_multi.h): MultiArgs with the models, as RollArgs', where dts and the plant stood - a model
+// advances by its own step.  A block of its own: MultiArgs is plant_rollout_multi_kernel's kernarg segment and stays as it is.
+struct ModelMultiArgs {
+  int B, N, S, q_mode;
+  M4Q_P(const cplx) x0;                            // [B][n]
+  M4Q_P(const double) us;                          // [S][N][m]
+  M4Q_P(const double) u_scale;                     // [B][m] or null
+  M4Q_P(const cplx) models; long model_stride;     // [B|1][n][n(1+P)] (model_stride n n (1 + P) or 0)
+  M4Q_P(const cplx) W; M4Q_P(const cplx) target; long target_stride;
+  M4Q_P(double) J;                                 // [B][S]
+  M4Q_P(const double) weights;
+  M4Q_P(double) partial; M4Q_P(double) F;
+};
 
 // The plant's own linearisation along trajectories (m4q_plant_linearize_batch; m4q_plant_lin.h, plant_linearize.py is the
 // definition): the work unit is a (member, point) pair, B T of them.  Member b at point t: state X[b][t], controls U[b|.][t] as the
@@ -377,6 +391,7 @@ struct ShapeOps {
   int (*launch_plant_qp)(const PlantQpArgs&, hipStream_t);         // (square shapes that hold qp_kernel; no generator plant)
   int (*launch_plant_step)(const PlantStepArgs&, hipStream_t);     // (the shapes and plants of launch_plant_qp)
   int (*launch_plant_multi)(const MultiArgs&, hipStream_t);        // (the shapes and plants of launch_plant_grad)
+  int (*launch_model_multi)(const ModelMultiArgs&, hipStream_t);   // (the shapes of launch_model_rollout)
 };
 
 // The blocks are the kernels' kernarg segments: a field that moves changes every kernel that reads the block.  Where the operator
@@ -397,5 +412,10 @@ M4Q_PIN_PLANT(PlantStepArgs, plant, 96, X_bm, 128, 264);
 M4Q_PIN_PLANT(ObsPlantArgs, plant, 48, zs, 80, 96);
 #undef M4Q_PIN_PLANT
 static_assert(sizeof(GradArgs) == 208 && sizeof(FeedbackArgs) == 288, "the blocks that hold a RollArgs");
+// ... and the model twin of MultiArgs: what the reduction behind both reads (B, S, J, weights, partial, F) has the same names
+static_assert(std::is_standard_layout<ModelMultiArgs>::value && sizeof(ModelMultiArgs) == 112, "ModelMultiArgs: four ints, twelve 8-byte fields");
+static_assert(offsetof(ModelMultiArgs, x0) == 16 && offsetof(ModelMultiArgs, models) == 40 && offsetof(ModelMultiArgs, model_stride) == 48 &&
+                  offsetof(ModelMultiArgs, W) == 56 && offsetof(ModelMultiArgs, J) == 80 && offsetof(ModelMultiArgs, F) == 104,
+              "ModelMultiArgs: the layout of the kernarg segment moved");
 
 }  // namespace m4q

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -1778,15 +1779,21 @@ int m4q_plant_rollout_multi_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32
   return 0;
 }
 
-int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts, const double* x0,
-                           const double* U0, const double* u_scale, const double* op0, const double* ops, int32_t plant_per_instance,
-                           const double* W, const double* target, int32_t target_per_instance, int32_t q_mode, const double* weights,
-                           double sat, int32_t iters, int32_t steps, int32_t mem, double step0, double tol, double gtol,
-                           double* U, double* cost, double* cost_hist, double* alpha_hist, double* pgrad_hist, int32_t* n_iter,
-                           int32_t* status, double* J) {
-  const char* who = "m4q_plant_robust_batch";
-  const m4q::ShapeOps* sh = nullptr;
-  if (int rc = check_ensemble_args(who, B, dim_x, dim_u, plant_kind, N, dts, x0, U0, op0, ops, W, target, q_mode, weights, &sh)) return rc;
+namespace {
+// What m4q_plant_robust_batch and m4q_model_robust_batch share behind their own ensemble checks: the refusals of the outputs and of
+// the loop's parameters ...
+// (the loop's parameters and its outputs, as both entries take them)
+struct RobustParams {
+  double sat; int32_t iters, steps, mem; double step0, tol, gtol;
+};
+struct RobustOut {
+  double* U; double* cost; double* cost_hist; double* alpha_hist; double* pgrad_hist; int32_t* n_iter; int32_t* status; double* J;
+};
+int check_robust_args(const char* who, const RobustParams& p, const RobustOut& o) {
+  const double sat = p.sat, step0 = p.step0, tol = p.tol, gtol = p.gtol;
+  const int32_t iters = p.iters, steps = p.steps, mem = p.mem;
+  const double *U = o.U, *cost = o.cost, *cost_hist = o.cost_hist, *alpha_hist = o.alpha_hist, *pgrad_hist = o.pgrad_hist;
+  const int32_t *n_iter = o.n_iter, *status = o.status;
   if (!U || !cost || !cost_hist || !alpha_hist || !pgrad_hist || !n_iter || !status)
     return fail(M4Q_E_BADARG, "%s: U, cost, cost_hist, alpha_hist, pgrad_hist, n_iter and status are required", who);
   if (!(sat > 0)) return fail(M4Q_E_BADARG, "%s: sat must be positive (INFINITY: no box)", who);
@@ -1796,27 +1803,23 @@ int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plan
   if (!(step0 > 0) || !std::isfinite(step0)) return fail(M4Q_E_BADARG, "%s: step0 must be positive and finite", who);
   if (!(tol >= 0) || !std::isfinite(tol) || !(gtol >= 0) || !std::isfinite(gtol))
     return fail(M4Q_E_BADARG, "%s: tol and gtol must be finite and not negative", who);
-  if (int rc = need_device()) return rc;
-  const size_t n = dim_x, m = dim_u, nm = (size_t)N * m;
-  // staged once: the ensemble and every workspace; the iterate lives in a slot of the candidates' buffer
-  Stage st;
-  m4q::MultiArgs c = stage_ensemble(st, B, n, m, plant_kind, N, dts, x0, u_scale, op0, ops, plant_per_instance, W, target,
-                                    target_per_instance, q_mode, weights, steps);
-  m4q::GradArgs g{};
-  g.roll.B = B; g.roll.N = N; g.roll.kind = plant_kind; g.roll.xs_mode = 2; g.roll.q_mode = q_mode;
-  g.roll.dts = c.dts; g.roll.x0 = c.x0; g.roll.u_scale = c.u_scale; g.roll.u_stride = 0;
-  g.roll.plant = c.plant;
-  g.roll.W = c.W; g.roll.target = c.target; g.roll.target_stride = c.target_stride;
-  g.roll.xs = st.out<cplx>(nullptr, (size_t)B * ((size_t)N + 1) * n);
-  g.roll.q = st.out<double>(nullptr, (size_t)B * (q_mode == 2 ? (size_t)N + 1 : 1));
-  g.grad = st.out<double>(nullptr, (size_t)B * nm);
-  g.reduce = 1;
-  g.weights = c.weights;
-  g.partial = st.out<double>(nullptr, (((size_t)B + m4q::GRAD_CHUNK - 1) / m4q::GRAD_CHUNK) * (nm + 1));
-  double* mean = st.out<double>(nullptr, nm + 1);             // the reduced gradient [N][m], then F: one copy down per gradient
-  g.grad_mean = mean; g.q_mean = mean + nm;
-  if (st.error()) return st.error();
+  return 0;
+}
 
+// ... and the loop itself (plant_robust.py: _loop is the definition; the direction is m4q_robust_host.h), written once on two
+// launches: launch_grad(u) runs the reduced gradient at the sequence u [N][m] on the device and leaves the reduced gradient and F in
+// d.mean [N m + 1]; launch_multi(us, S) rolls the S sequences at us and leaves J [B][S] in d.J and F [S] in d.F.  d.us is the
+// candidates' buffer [steps][N m]: the iterate lives in the accepted candidate's slot of it.
+struct RobustDev {
+  const double* us; const double* mean; const double* F; const double* J;
+};
+int robust_loop(const char* who, int32_t B, size_t nm, const double* U0, const RobustParams& p, const RobustDev& d,
+                const std::function<int(const double*)>& launch_grad, const std::function<int(const double*, int)>& launch_multi,
+                const RobustOut& o) {
+  const double sat = p.sat, step0 = p.step0, tol = p.tol, gtol = p.gtol;
+  const int iters = p.iters, steps = p.steps, mem = p.mem;
+  double *U = o.U, *cost = o.cost, *cost_hist = o.cost_hist, *alpha_hist = o.alpha_hist, *pgrad_hist = o.pgrad_hist, *J = o.J;
+  int32_t *n_iter = o.n_iter, *status = o.status;
   m4q::robust::State r;
   r.mem = mem; r.sat = sat; r.step0 = step0;
   r.U.resize(nm);
@@ -1824,7 +1827,7 @@ int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plan
   r.g.assign(nm, 0.0);
   std::vector<double> cands((size_t)steps * nm), down(nm + 1), Fs((size_t)steps);
   int slot = 0;                                               // where on the device the iterate is (-1: nowhere)
-  if (int rc = copy_up(c.us, r.U.data(), nm * sizeof(double))) return rc;
+  if (int rc = copy_up(d.us, r.U.data(), nm * sizeof(double))) return rc;
   for (int i = 0; i <= iters; ++i) cost_hist[i] = 0.0;
   for (int i = 0; i < iters; ++i) alpha_hist[i] = pgrad_hist[i] = 0.0;
   double Fcur = 0.0;
@@ -1832,9 +1835,8 @@ int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plan
   bool moved = true;
   for (int i = 0; i < iters; ++i) {
     if (moved) {                                              // step 1: the reduced gradient at the iterate, where it lies
-      g.roll.u = c.us + (size_t)slot * nm;
-      if (int rc = sh->launch_plant_grad(g, nullptr)) return fail(rc, "%s: gradient launch failed", who);
-      if (int rc = copy_down(down.data(), mean, (nm + 1) * sizeof(double))) return rc;
+      if (int rc = launch_grad(d.us + (size_t)slot * nm)) return fail(rc, "%s: gradient launch failed", who);
+      if (int rc = copy_down(down.data(), d.mean, (nm + 1) * sizeof(double))) return rc;
       r.g.assign(down.begin(), down.begin() + nm);
       Fcur = down[nm];
       moved = false;
@@ -1850,10 +1852,10 @@ int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plan
     m4q::robust::absorb(r);
     m4q::robust::direction(r);
     for (int j = 0; j < steps; ++j) m4q::robust::candidate(r, j, cands.data() + (size_t)j * nm);
-    if (int rc = copy_up(c.us, cands.data(), cands.size() * sizeof(double))) return rc;
+    if (int rc = copy_up(d.us, cands.data(), cands.size() * sizeof(double))) return rc;
     slot = -1;
-    if (int rc = sh->launch_plant_multi(c, nullptr)) return fail(rc, "%s: line search launch failed", who);
-    if (int rc = copy_down(Fs.data(), c.F, Fs.size() * sizeof(double))) return rc;
+    if (int rc = launch_multi(d.us, steps)) return fail(rc, "%s: line search launch failed", who);
+    if (int rc = copy_down(Fs.data(), d.F, Fs.size() * sizeof(double))) return rc;
     const int j = m4q::robust::pick(Fs.data(), steps);        // steps 6 - 8
     if (j >= 0 && Fs[j] < Fcur) {
       m4q::robust::accept(r, cands.data() + (size_t)j * nm);
@@ -1875,20 +1877,169 @@ int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plan
   cost[0] = Fcur; n_iter[0] = begun; status[0] = st_code;
   if (J) {                                                    // the members' objectives at the returned U: one S = 1 launch
     if (slot < 0) {
-      if (int rc = copy_up(c.us, r.U.data(), nm * sizeof(double))) return rc;
+      if (int rc = copy_up(d.us, r.U.data(), nm * sizeof(double))) return rc;
       slot = 0;
     }
-    m4q::MultiArgs one = c;
-    one.S = 1; one.us = c.us + (size_t)slot * nm;
-    if (int rc = sh->launch_plant_multi(one, nullptr)) return fail(rc, "%s: final launch failed", who);
+    if (int rc = launch_multi(d.us + (size_t)slot * nm, 1)) return fail(rc, "%s: final launch failed", who);
     double Fone = 0.0;
-    if (int rc = copy_down(J, one.J, (size_t)B * sizeof(double))) return rc;
-    if (int rc = copy_down(&Fone, one.F, sizeof(double))) return rc;
+    if (int rc = copy_down(J, d.J, (size_t)B * sizeof(double))) return rc;
+    if (int rc = copy_down(&Fone, d.F, sizeof(double))) return rc;
     if (std::isfinite(Fcur) && Fone != Fcur)
       return fail(-(int)hipErrorUnknown, "%s: the mean of the members' objectives at U, %.17g, is not the cost %.17g", who, Fone, Fcur);
   }
   HIP_TRY(hipDeviceSynchronize());
   return 0;
+}
+}  // namespace
+
+int m4q_plant_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts, const double* x0,
+                           const double* U0, const double* u_scale, const double* op0, const double* ops, int32_t plant_per_instance,
+                           const double* W, const double* target, int32_t target_per_instance, int32_t q_mode, const double* weights,
+                           double sat, int32_t iters, int32_t steps, int32_t mem, double step0, double tol, double gtol,
+                           double* U, double* cost, double* cost_hist, double* alpha_hist, double* pgrad_hist, int32_t* n_iter,
+                           int32_t* status, double* J) {
+  const char* who = "m4q_plant_robust_batch";
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = check_ensemble_args(who, B, dim_x, dim_u, plant_kind, N, dts, x0, U0, op0, ops, W, target, q_mode, weights, &sh)) return rc;
+  const RobustParams prm{sat, iters, steps, mem, step0, tol, gtol};
+  const RobustOut out{U, cost, cost_hist, alpha_hist, pgrad_hist, n_iter, status, J};
+  if (int rc = check_robust_args(who, prm, out)) return rc;
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, nm = (size_t)N * m;
+  // staged once: the ensemble and every workspace; the iterate lives in a slot of the candidates' buffer
+  Stage st;
+  m4q::MultiArgs c = stage_ensemble(st, B, n, m, plant_kind, N, dts, x0, u_scale, op0, ops, plant_per_instance, W, target,
+                                    target_per_instance, q_mode, weights, steps);
+  m4q::GradArgs g{};
+  g.roll.B = B; g.roll.N = N; g.roll.kind = plant_kind; g.roll.xs_mode = 2; g.roll.q_mode = q_mode;
+  g.roll.dts = c.dts; g.roll.x0 = c.x0; g.roll.u_scale = c.u_scale; g.roll.u_stride = 0;
+  g.roll.plant = c.plant;
+  g.roll.W = c.W; g.roll.target = c.target; g.roll.target_stride = c.target_stride;
+  g.roll.xs = st.out<cplx>(nullptr, (size_t)B * ((size_t)N + 1) * n);
+  g.roll.q = st.out<double>(nullptr, (size_t)B * (q_mode == 2 ? (size_t)N + 1 : 1));
+  g.grad = st.out<double>(nullptr, (size_t)B * nm);
+  g.reduce = 1;
+  g.weights = c.weights;
+  g.partial = st.out<double>(nullptr, (((size_t)B + m4q::GRAD_CHUNK - 1) / m4q::GRAD_CHUNK) * (nm + 1));
+  double* mean = st.out<double>(nullptr, nm + 1);             // the reduced gradient [N][m], then F: one copy down per gradient
+  g.grad_mean = mean; g.q_mean = mean + nm;
+  if (st.error()) return st.error();
+
+  const RobustDev d{c.us, mean, c.F, c.J};
+  return robust_loop(
+      who, B, nm, U0, prm, d,
+      [&](const double* u) { g.roll.u = u; return sh->launch_plant_grad(g, nullptr); },
+      [&](const double* us, int S) { m4q::MultiArgs one = c; one.S = S; one.us = us; return sh->launch_plant_multi(one, nullptr); },
+      out);
+}
+
+namespace {
+// What m4q_model_rollout_multi_batch and m4q_model_robust_batch share: control sequences shared by the ensemble on the members'
+// models.  The refusals are those of m4q_model_rollout_grad_batch with reduce set, in its order and under the entry's name, checked
+// before a device is asked for; *found receives the shape's kernels.
+int check_model_ensemble_args(const char* who, int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0,
+                              const double* u, const double* models, const double* W, const double* target, int32_t q_mode,
+                              const double* weights, const m4q::ShapeOps** found) {
+  *found = find_shape(dim_x, dim_u, order);
+  if (!*found) return fail(M4Q_E_UNSUPPORTED, "%s: no model kernel for dim_x=%d dim_u=%d order=%d", who, dim_x, dim_u, order);
+  if (B < 1 || N < 1) return fail(M4Q_E_BADARG, "%s: B and N must be at least 1 (got %d, %d)", who, B, N);
+  if (!x0 || !u || !W || !target) return fail(M4Q_E_BADARG, "%s: x0, the control sequences, W and target are required", who);
+  if (q_mode < 1 || q_mode > 2) return fail(M4Q_E_BADARG, "%s: q_mode is 1 (J = q_N) or 2 (J = sum_t q_t), got %d", who, q_mode);
+  if (weights)
+    for (int32_t b = 0; b < B; ++b)
+      if (!std::isfinite(weights[b]) || weights[b] < 0.0) return fail(M4Q_E_BADARG, "%s: weights[%d] = %g is not a finite non-negative number", who, b, weights[b]);
+  if (!models) return fail(M4Q_E_BADARG, "%s: models are required", who);
+  return 0;
+}
+
+// stage_ensemble for models: the models, x0, u_scale, W, the targets, the weights (1 / B when absent), and the buffers of S sequences
+m4q::ModelMultiArgs stage_model_ensemble(Stage& st, int32_t B, size_t n, size_t m, size_t P, int32_t N, const double* x0,
+                                         const double* u_scale, const double* models, int32_t model_per_instance, const double* W,
+                                         const double* target, int32_t target_per_instance, int32_t q_mode, const double* weights, int32_t S) {
+  const Extent ef(B, target_per_instance, n), mdl(B, model_per_instance, n * n * (1 + P));
+  m4q::ModelMultiArgs a{};
+  a.B = B; a.N = N; a.S = S; a.q_mode = q_mode;
+  a.x0 = st.in<cplx>(x0, (size_t)B * n);
+  if (u_scale) a.u_scale = st.in<double>(u_scale, (size_t)B * m);
+  a.models = st.in<cplx>(models, mdl.count); a.model_stride = mdl.stride;
+  a.W = st.in<cplx>(W, n * n);
+  a.target = st.in<cplx>(target, ef.count); a.target_stride = ef.stride;
+  std::vector<double> w;
+  if (weights) w.assign(weights, weights + B);
+  else w.assign((size_t)B, 1.0 / B);
+  a.weights = st.in<double>(w.data(), (size_t)B);
+  a.us = st.in<double>(nullptr, (size_t)S * N * m);
+  a.J = st.out<double>(nullptr, (size_t)B * S);
+  a.partial = st.out<double>(nullptr, (((size_t)B + m4q::GRAD_CHUNK - 1) / m4q::GRAD_CHUNK) * S);
+  a.F = st.out<double>(nullptr, (size_t)S);
+  return a;
+}
+}  // namespace
+
+int m4q_model_rollout_multi_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, int32_t S,
+                                  const double* us, const double* u_scale, const double* models, int32_t model_per_instance,
+                                  const double* W, const double* target, int32_t target_per_instance, int32_t q_mode,
+                                  const double* weights, double* J, double* F) {
+  const char* who = "m4q_model_rollout_multi_batch";
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = check_model_ensemble_args(who, B, dim_x, dim_u, order, N, x0, us, models, W, target, q_mode, weights, &sh)) return rc;
+  if (S < 1 || S > m4q::MULTI_MAX_S) return fail(M4Q_E_BADARG, "%s: S must be in 1..%d, got %d", who, m4q::MULTI_MAX_S, S);
+  if (!J && !F) return fail(M4Q_E_BADARG, "%s: nothing to return (J and F are both NULL)", who);
+  if (int rc = need_device()) return rc;
+  Stage st;
+  m4q::ModelMultiArgs a = stage_model_ensemble(st, B, dim_x, dim_u, sh->np, N, x0, u_scale, models, model_per_instance, W, target,
+                                               target_per_instance, q_mode, weights, S);
+  if (st.error()) return st.error();
+  const size_t nm = (size_t)N * dim_u;
+  if (int rc = copy_up(a.us, us, (size_t)S * nm * sizeof(double))) return rc;
+  if (!F) a.F = nullptr;                                     // (no reduction asked for)
+  if (int rc = st.finish(sh->launch_model_multi(a, nullptr), "model multi rollout")) return rc;
+  if (J)
+    if (int rc = copy_down(J, a.J, (size_t)B * S * sizeof(double))) return rc;
+  if (F)
+    if (int rc = copy_down(F, a.F, (size_t)S * sizeof(double))) return rc;
+  return 0;
+}
+
+int m4q_model_robust_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t order, int32_t N, const double* x0, const double* U0,
+                           const double* u_scale, const double* models, int32_t model_per_instance, const double* W,
+                           const double* target, int32_t target_per_instance, int32_t q_mode, const double* weights,
+                           double sat, int32_t iters, int32_t steps, int32_t mem, double step0, double tol, double gtol,
+                           double* U, double* cost, double* cost_hist, double* alpha_hist, double* pgrad_hist, int32_t* n_iter,
+                           int32_t* status, double* J) {
+  const char* who = "m4q_model_robust_batch";
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = check_model_ensemble_args(who, B, dim_x, dim_u, order, N, x0, U0, models, W, target, q_mode, weights, &sh)) return rc;
+  const RobustParams prm{sat, iters, steps, mem, step0, tol, gtol};
+  const RobustOut out{U, cost, cost_hist, alpha_hist, pgrad_hist, n_iter, status, J};
+  if (int rc = check_robust_args(who, prm, out)) return rc;
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u, nm = (size_t)N * m;
+  // staged once: the ensemble and every workspace; the iterate lives in a slot of the candidates' buffer
+  Stage st;
+  m4q::ModelMultiArgs c = stage_model_ensemble(st, B, n, m, sh->np, N, x0, u_scale, models, model_per_instance, W, target,
+                                               target_per_instance, q_mode, weights, steps);
+  m4q::GradArgs g{};
+  g.roll.B = B; g.roll.N = N; g.roll.xs_mode = 2; g.roll.q_mode = q_mode;
+  g.roll.x0 = c.x0; g.roll.u_scale = c.u_scale; g.roll.u_stride = 0;
+  g.roll.models = c.models; g.roll.model_stride = c.model_stride;
+  g.roll.W = c.W; g.roll.target = c.target; g.roll.target_stride = c.target_stride;
+  g.roll.xs = st.out<cplx>(nullptr, (size_t)B * ((size_t)N + 1) * n);
+  g.roll.q = st.out<double>(nullptr, (size_t)B * (q_mode == 2 ? (size_t)N + 1 : 1));
+  g.grad = st.out<double>(nullptr, (size_t)B * nm);
+  g.reduce = 1;
+  g.weights = c.weights;
+  g.partial = st.out<double>(nullptr, (((size_t)B + m4q::GRAD_CHUNK - 1) / m4q::GRAD_CHUNK) * (nm + 1));
+  double* mean = st.out<double>(nullptr, nm + 1);             // the reduced gradient [N][m], then F: one copy down per gradient
+  g.grad_mean = mean; g.q_mean = mean + nm;
+  if (st.error()) return st.error();
+
+  const RobustDev d{c.us, mean, c.F, c.J};
+  return robust_loop(
+      who, B, nm, U0, prm, d,
+      [&](const double* u) { g.roll.u = u; return sh->launch_model_grad(g, nullptr); },
+      [&](const double* us, int S) { m4q::ModelMultiArgs one = c; one.S = S; one.us = us; return sh->launch_model_multi(one, nullptr); },
+      out);
 }
 
 // what the fit against a prior model adds to the fit's arguments (m4q_dmdc_refit_batch, m4q_dmdc_refit_qr_batch)

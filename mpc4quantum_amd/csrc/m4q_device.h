@@ -20,7 +20,7 @@
 // Development-only instruments - a debug form of the row broadcast (ds_bpermute instead of DPP), an override of the DPP wait-state
 // pad, the per-phase clock - exist only in builds that say so: build.py passes -DM4Q_DEV for `--dev` alone and
 // tools/build_variant.sh (whose libraries never ship) always.  They measure and debug; they do not choose between variants.
-#if !defined(M4Q_DEV) && (defined(M4Q_BCAST_SHFL) || defined(M4Q_NOP) || defined(M4Q_DEV_PHASE_CLOCK))
+#if !defined(M4Q_DEV) && (defined(M4Q_BCAST_SHFL) || defined(M4Q_NOP) || defined(M4Q_DEV_PHASE_CLOCK) || defined(M4Q_DEV_MULTI_LDS))
 #error "development switch without -DM4Q_DEV: use build.py --dev or tools/build_variant.sh"
 #endif
 

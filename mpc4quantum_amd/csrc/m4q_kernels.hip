@@ -1610,6 +1610,10 @@ __global__ __launch_bounds__(64) M4Q_OCC void model_rollout_grad_kernel(GradArgs
   }
 }
 
+// model_rollout_multi_kernel: S sequences shared by the ensemble through all members' models in one launch, the members' objectives
+// alone (m4q_model_rollout_multi_batch; the line search of m4q_model_robust_batch)
+#include "m4q_model_multi.h"
+
 // ---------------------------------------------------------------------------------------------
 // DMDc identification of B members (m4q_dmdc_fit_batch; fit.py: dmdc_fit_reference is the definition): one wavefront per member,
 // grid-stride over members; the Gram data, the eigenvectors and the eigenvalues in dynamic LDS (FitLayout, m4q_fit.h).
@@ -2599,7 +2603,9 @@ static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 // the S shared sequences of MultiArgs against every member (m4q_rollout_multi.h): over quads of members with the rollouts' LDS,
 // then - a.F set - the two passes of the ordered reduction over J [B][S] on the same stream.  grad_reduce's element
 // nm is row i's vals[i][nm] when q_cols is 0, so nm = S - 1 over rows of S covers the S columns.
-static int launch_multi_reduce(const MultiArgs& a, hipStream_t s) {
+// (A: MultiArgs or ModelMultiArgs - the reduction reads what the two blocks name alike)
+template <class A>
+static int launch_multi_reduce(const A& a, hipStream_t s) {
   if (!a.F) return 0;
   const int nchunks = (a.B + GRAD_CHUNK - 1) / GRAD_CHUNK;
   GradReduceArgs p{};
@@ -2620,8 +2626,18 @@ static int launch_plant_multi(const MultiArgs& a, hipStream_t s) {
   const int rc = launch_by_plant<false>(a, a.kind, a.B, s, [](auto plant) { return plant_rollout_multi_kernel<decltype(plant)::value>; }, step_lds);
   return rc ? rc : launch_multi_reduce(a, s);
 }
+// ... through the members' models (m4q_model_multi.h): over quads of members with the model rollouts' LDS, then the same reduction
+#ifndef M4Q_NO_AUX
+static int launch_model_multi(const ModelMultiArgs& a, hipStream_t s) {
+  const int rc = launch_aux(model_rollout_multi_kernel, a, MODEL_LDS, s);
+  return rc ? rc : launch_multi_reduce(a, s);
+}
+#else
+static int launch_model_multi(const ModelMultiArgs&, hipStream_t) { return UNBUILT; }
+#endif
 #else
 static int launch_plant_multi(const MultiArgs&, hipStream_t) { return UNBUILT; }
+static int launch_model_multi(const ModelMultiArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant(const PlantArgs&, hipStream_t) { return UNBUILT; }
 static int launch_noise(const NoiseArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant_rollout(const RollArgs&, hipStream_t) { return UNBUILT; }
@@ -2683,7 +2699,7 @@ static const ShapeOps* shape_ops() {
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
                                ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr,
                                launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr, launch_plant_linearize, launch_plant_qp,
-                               launch_plant_step, launch_plant_multi};
+                               launch_plant_step, launch_plant_multi, launch_model_multi};
   return &ops;
 }
 

@@ -134,6 +134,52 @@ def _robust_batch(exp, x0, U0, ts_or_dt, W, target, sat, op0, u_scale, figure, w
                               members=members)
 
 
+def _robust_model_batch(exp, x0, U0, dt, order, W, target, sat, op0, u_scale, figure, weights, iters, steps, mem, step0, tol, gtol, members):
+    """model_robust_batch on the discretised generators of any plant kind: operators() in generator form (liouvillian(H) for a
+    Hamiltonian plant, the generators as they stand otherwise), the per-member op0 [B, k, k] in that same form in place of the
+    drift.  Everything is checked before the library is touched - the discretisation included."""
+    from .grad import _grad_common
+    from .model_robust import model_robust_batch
+    from .plant_robust import _robust_params, _shared_sequence
+    from .vectorize import discretize_homogeneous, discretize_homogeneous_batch, liouvillian
+    if np.ndim(dt) != 0:
+        raise ValueError("robust_model_batch takes a scalar dt, got an array of shape %s: a model advances by its own step, so a time "
+                         "grid has no meaning here (robust_batch takes one, on the plants that have a gradient)" % (np.shape(dt),))
+    dt = float(dt)
+    if not (dt > 0 and np.isfinite(dt)):
+        raise ValueError("dt must be positive and finite, got %r" % (dt,))
+    if isinstance(order, bool) or int(order) != order or not 1 <= int(order) <= 4:
+        raise ValueError("order must be an integer in 1..4, got %r" % (order,))
+    order = int(order)
+    _robust_params(sat, iters, steps, mem, step0, tol, gtol)
+    U0 = _shared_sequence(U0, "U0")
+    x0c = _grad_common(x0, U0, u_scale, W, target, figure, weights, True)[0]
+    B, n = x0c.shape
+    own0, ops = exp.operators()
+    m = len(ops)
+    if U0.shape[1] != m:
+        raise ValueError("U0 must be [N, m] = (.., %d) for this plant's %d control operators, got %s" % (m, m, U0.shape))
+    k = own0.shape[0]
+    generator = exp.plant_kind == _lib.PLANT_GENERATOR
+    if (k if generator else k * k) != n:
+        raise ValueError("x0 must be [B, n] with n = %d for this plant, got %s" % (k if generator else k * k, x0c.shape))
+    if op0 is not None:
+        op0 = np.asarray(op0, dtype=np.complex128)
+        if op0.shape != (B, k, k):
+            raise ValueError("op0 must be [B, k, k] = (%d, %d, %d), got %s" % (B, k, k, op0.shape))
+    drift = own0 if op0 is None else op0
+    gens = [drift if generator else liouvillian(drift)] + [g if generator else liouvillian(g) for g in ops]
+    if order <= 2:
+        models = discretize_homogeneous_batch(gens, dt, order)
+        models = models if op0 is not None else models[0]
+    else:                                                         # (no device discretisation beyond order 2: m4q_discretize_batch)
+        models = discretize_homogeneous([np.broadcast_to(g, (B, n, n)) for g in gens] if op0 is not None else gens, dt, order)
+    out = model_robust_batch(x0, U0, models, order, W, target, sat, u_scale=u_scale, figure=figure, weights=weights, iters=iters,
+                             steps=steps, mem=mem, step0=step0, tol=tol, gtol=gtol, members=members)
+    out["models"] = models
+    return out
+
+
 def _ilqr_batch(exp, x0, U0, ts_or_dt, X_bm, U_bm, Q_ls, R_ls, sat, iters, steps, tol, du, u_prev, u_scale, exact, gains, op0):
     """plant_ilqr_batch of the two unitary device plants: operators as _linearize_batch."""
     from .plant_ilqr import plant_ilqr_batch
@@ -284,6 +330,17 @@ class QExperiment(Experiment):
         generator plant, which is refused."""
         return _robust_batch(self, x0, U0, ts_or_dt, W, target, sat, op0, u_scale, figure, weights, iters, steps, mem, step0, tol, gtol,
                              members)
+
+    def robust_model_batch(self, x0, U0, dt, order, W, target, sat, op0=None, u_scale=None, figure="last", weights=None, iters=10,
+                           steps=6, mem=5, step0=0.1, tol=1e-9, gtol=0.0, members=False):
+        """robust_batch on the members' discretised MODELS (model_robust_batch): the optimiser every plant kind has, collapse
+        operators and LExperiment included.  The generators are those of operators() - for a Hamiltonian plant liouvillian(H),
+        with collapse operators or on an LExperiment the generators as they stand - with the per-member op0 [B, k, k] in the same
+        form in place of the drift; they are discretised to `order` over the scalar step dt (orders 1-2 on the device, 3-4 on the
+        host) into [B, n, n (1 + P)] models, and one U [N, m] is optimised against their weighted mean.  The rest and the returned
+        dict as model_robust_batch; the dict gains "models".  A time grid is refused: a model advances by its own step."""
+        return _robust_model_batch(self, x0, U0, dt, order, W, target, sat, op0, u_scale, figure, weights, iters, steps, mem, step0, tol,
+                                   gtol, members)
 
 
 class LExperiment(QExperiment):
