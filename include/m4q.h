@@ -314,6 +314,31 @@ M4Q_API int m4q_model_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u
                                  int32_t q_mode, const double* weights, int32_t reduce, double* q, double* grad, double* grad_scale,
                                  double* q_mean);
 
+/* Plant-parameter gradient of an open-loop plant rollout against a measured trajectory, for B members in ONE launch: what fitting
+ * detunings, anharmonicities, crosstalk strengths and drive gains to data needs.  mpc4quantum_amd/plant_param.py
+ * (plant_param_grad_reference) is the definition.
+ * The arguments up to plant_per_instance are m4q_plant_rollout_batch's.  dirs [B|1][p][d][d] c: Hermitian directions D_j; member b's
+ * drift is understood as op0_b + sum_j theta_j D_j, evaluated at the op0_b passed in.  data [B|1][N+1][n] c: the trajectory y the
+ * rollout is compared with; col_w [N+1] r (finite, non-negative) or NULL (ones): a column whose weight is 0 is skipped (sparse
+ * measurement), the costate still propagates through it.  W [n][n] c need not be Hermitian.
+ * -> J [B] r, required: J_b = sum_t col_w[t] Re((x_t - y_t)^H W (x_t - y_t)), t ascending from 0.0, each figure the one
+ *    m4q_plant_rollout_batch returns for that column;
+ *    grad_theta [B][p] r, required: dJ_b/dtheta_j;
+ *    grad_scale [B][m] r or NULL: dJ_b/du_scale[b][k] of the same objective.
+ * One matrix exponential of the (1 + p_tot) d block matrix per step gives the propagator and its Frechet derivatives in all
+ * p_tot = p + (grad_scale ? m : 0) directions; the block must fit the 16 lanes of a row: p_tot <= 16 / d - 1 (7 at d = 2, 4 at
+ * d = 3, 3 at d = 4).  The forward states stay in a device workspace [B][N+1][n] c, allocated by the call.
+ * M4Q_E_BADARG: B, N or p < 1, a missing x0, u, W, data, dts, op0, ops, dirs, J or grad_theta, a col_w entry that is not finite or
+ * negative, a plant_kind that is no device plant (M4Q_PLANT_NONE included), M4Q_PLANT_PROCESS with n not a fourth power.
+ * M4Q_E_UNSUPPORTED: no compiled shape, n not a square, a plant-only shape (the kernels are built with the auxiliary ones),
+ * M4Q_PLANT_GENERATOR, and more directions than the shape allows (the message names the limit).
+ * Arguments are checked before the device is asked for. */
+M4Q_API int m4q_plant_rollout_param_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                                       const double* x0, const double* u, int32_t u_per_instance, const double* u_scale,
+                                       const double* op0, const double* ops, int32_t plant_per_instance, int32_t p, const double* dirs,
+                                       int32_t dirs_per_instance, const double* W, const double* data, int32_t data_per_instance,
+                                       const double* col_w, double* J, double* grad_theta, double* grad_scale);
+
 /* S control sequences, each SHARED by the ensemble, rolled against all B members in ONE launch: compare pulses or scan an amplitude
  * over an ensemble; the line search of m4q_plant_robust_batch.  us [S][N][m] r, 1 <= S <= 8; the other arguments up to q_mode as
  * m4q_plant_rollout_grad_batch with u_per_instance 0.  No state is stored.

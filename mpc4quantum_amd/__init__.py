@@ -21,6 +21,8 @@ from .mpc import (StepClock, complex_to_real, complex_to_real_op, iqp_line_searc
 from .optimize import quad_program, quad_program_batch  # noqa: F401
 from .plant_linearize import plant_linearize_batch, plant_linearize_reference  # noqa: F401
 from .plant_linearize import plant_quad_program_batch, plant_quad_program_reference  # noqa: F401
+from .plant_param import (plant_calibrate_batch, plant_calibrate_reference, plant_param_grad_reference,  # noqa: F401
+                          plant_param_op0, plant_rollout_param_grad_batch)
 from .plant_sqp import plant_sqp_batch, plant_sqp_reference  # noqa: F401
 from .plant_ilqr import plant_ilqr_batch, plant_ilqr_reference  # noqa: F401
 from .plant_robust import (plant_robust_batch, plant_robust_reference, plant_rollout_multi_batch,  # noqa: F401

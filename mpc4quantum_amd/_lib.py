@@ -81,6 +81,8 @@ PROTOTYPES = {
                                           _i32, _dp]),
     "m4q_plant_rollout_grad_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _i32,
                                                _i32, _dp, _i32, _dp, _dp, _dp, _dp]),
+    "m4q_plant_rollout_param_grad_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _i32, _i32, _dp, _i32,
+                                                     _dp, _dp, _i32, _dp, _dp, _dp, _dp]),
     "m4q_model_rollout_grad_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _dp, _dp, _i32, _i32, _dp,
                                                _i32, _dp, _dp, _dp, _dp]),
     "m4q_plant_rollout_multi_batch": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _dp, _dp, _i32, _dp, _dp, _dp, _dp, _i32, _dp, _dp, _i32,

@@ -165,6 +165,21 @@ struct GradReduceArgs {
   M4Q_P(double) out_last; long last_stride;        // element nm of chunk c -> out_last[c last_stride]
 };
 
+// Plant-parameter gradient (m4q_plant_rollout_param_grad_batch; m4q_plant_param.h, plant_param.py is the definition).  The forward
+// pass is the rollout `roll` describes, with xs the workspace [B][N + 1][n] (roll.W is the objective's W; roll.target, roll.q and
+// the two modes are unused).  Objective: J_b = sum_t col_w[t] Re((x_t - y_t)^H W (x_t - y_t)), y = data, t ascending from 0.0; a
+// column whose weight is 0 is skipped.  The kernel is compiled for PT directions: the p matrices of dirs and - PT > p, then
+// PT = p + m - the m drive gains.  grad_theta [B][p] = dJ_b/dtheta_j, grad_scale [B][m] = dJ_b/du_scale[b][k] (PT > p).
+struct ParamGradArgs {
+  RollArgs roll;
+  int p;
+  M4Q_P(const cplx) dirs; long dirs_stride;        // [B|1][p][d][d] (dirs_stride p d d or 0)
+  M4Q_P(const cplx) data; long data_stride;        // [B|1][N + 1][n] (data_stride (N + 1) n or 0)
+  M4Q_P(const double) col_w;                       // [N + 1]
+  M4Q_P(double) J;                                 // [B]
+  M4Q_P(double) grad_theta; M4Q_P(double) grad_scale;
+};
+
 // S control sequences shared by the ensemble, each rolled against all B members in one launch (m4q_plant_rollout_multi_batch and
 // the line search of m4q_plant_robust_batch; m4q_rollout_multi.h).  Member b under sequence s sees u_scale[b][k] us[s][t][k]; its
 // objective J[b][s] is q_N (q_mode 1) or sum_t q_t, t ascending from 0.0 (q_mode 2), q as RollArgs.  No state is stored.
@@ -392,6 +407,8 @@ struct ShapeOps {
   int (*launch_plant_step)(const PlantStepArgs&, hipStream_t);     // (the shapes and plants of launch_plant_qp)
   int (*launch_plant_multi)(const MultiArgs&, hipStream_t);        // (the shapes and plants of launch_plant_grad)
   int (*launch_model_multi)(const ModelMultiArgs&, hipStream_t);   // (the shapes of launch_model_rollout)
+  // plant_param_grad_kernel<PLANT, p_tot>: square shapes with the auxiliary kernels; no generator plant; (1 + p_tot) d <= 16
+  int (*launch_plant_param_grad)(const ParamGradArgs&, int p_tot, hipStream_t);
 };
 
 // The blocks are the kernels' kernarg segments: a field that moves changes every kernel that reads the block.  Where the operator

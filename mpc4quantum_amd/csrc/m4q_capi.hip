@@ -1484,6 +1484,60 @@ int m4q_plant_rollout_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_
   return st.finish(sh->launch_plant_grad(a, nullptr), "plant rollout gradient");
 }
 
+int m4q_plant_rollout_param_grad_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t N, const double* dts,
+                                       const double* x0, const double* u, int32_t u_per_instance, const double* u_scale,
+                                       const double* op0, const double* ops, int32_t plant_per_instance, int32_t p, const double* dirs,
+                                       int32_t dirs_per_instance, const double* W, const double* data, int32_t data_per_instance,
+                                       const double* col_w, double* J, double* grad_theta, double* grad_scale) {
+  const char* who = "m4q_plant_rollout_param_grad_batch";
+  const m4q::ShapeOps* sh = nullptr;
+  if (int rc = plant_shape(who, /*named=*/true, dim_x, dim_u, /*needs_qp=*/false, &sh)) return rc;
+  if (sh->plant_only)
+    return fail(M4Q_E_UNSUPPORTED, "%s: dim_x=%d dim_u=%d is a plant-only shape, it has no parameter-gradient kernel", who, dim_x, dim_u);
+  sh = find_shape(dim_x, dim_u, 1);        // (the kernels do not depend on the library order: the order-1 object holds them)
+  if (!sh) return fail(M4Q_E_UNSUPPORTED, "%s: no order-1 object for dim_x=%d dim_u=%d, which would hold the parameter-gradient kernels", who, dim_x, dim_u);
+  if (B < 1 || N < 1) return fail(M4Q_E_BADARG, "%s: B and N must be at least 1 (got %d, %d)", who, B, N);
+  if (!x0 || !u || !W || !data) return fail(M4Q_E_BADARG, "%s: x0, u, W and data are required", who);
+  if (!dts || !op0 || !ops || !dirs) return fail(M4Q_E_BADARG, "%s: dts, op0, ops and dirs are required", who);
+  if (!J || !grad_theta) return fail(M4Q_E_BADARG, "%s: J and grad_theta are required", who);
+  if (int rc = check_plant_kind(who, /*named=*/true, plant_kind, dim_x, "parameter-gradient kernel",
+                                "fit the parameters through its discretised model (m4q_discretize_batch, m4q_model_rollout_grad_batch)"))
+    return rc;
+  const int d = (int)plant_dim(plant_kind, dim_x);
+  const int p_max = 16 / d - 1, p_tot = p + (grad_scale ? dim_u : 0);
+  if (p < 1) return fail(M4Q_E_BADARG, "%s: p must be at least 1 (got %d)", who, p);
+  if (p_tot > p_max)
+    return fail(M4Q_E_UNSUPPORTED, "%s: %d directions (p = %d%s) are too many: the block matrix of (1 + p_tot) d columns must fit the 16 lanes "
+                                   "of a row, at most %d directions for d = %d", who, p_tot, p, grad_scale ? " and the dim_u drive gains" : "",
+                p_max, d);
+  std::vector<double> cw((size_t)N + 1, 1.0);
+  if (col_w)
+    for (int32_t t = 0; t <= N; ++t) {
+      if (!std::isfinite(col_w[t]) || col_w[t] < 0.0)
+        return fail(M4Q_E_BADARG, "%s: col_w[%d] = %g is not a finite non-negative number", who, t, col_w[t]);
+      cw[t] = col_w[t];
+    }
+  if (int rc = need_device()) return rc;
+  const size_t n = dim_x, m = dim_u;
+  const Extent ed(B, dirs_per_instance, (size_t)p * d * d), ey(B, data_per_instance, ((size_t)N + 1) * n);
+  Stage st;
+  m4q::ParamGradArgs a{};
+  a.roll = stage_roll(st, B, n, m, N, x0, u, u_per_instance, u_scale, nullptr, nullptr, 0, /*xs_mode=*/2, /*xs=*/nullptr, /*q_mode=*/0, nullptr);
+  a.roll.kind = plant_kind;
+  a.roll.dts = st.in<double>(dts, N);
+  a.roll.plant = stage_plant(st, B, plant_kind, dim_x, dim_u, op0, ops, plant_per_instance);
+  a.roll.W = st.in<cplx>(W, n * n);
+  a.p = p;
+  a.dirs = st.in<cplx>(dirs, ed.count); a.dirs_stride = ed.stride;
+  a.data = st.in<cplx>(data, ey.count); a.data_stride = ey.stride;
+  a.col_w = st.in<double>(cw.data(), (size_t)N + 1);
+  a.J = st.out<double>(J, (size_t)B);
+  a.grad_theta = st.out<double>(grad_theta, (size_t)B * p);
+  if (grad_scale) a.grad_scale = st.out<double>(grad_scale, (size_t)B * m);
+  if (st.error()) return st.error();
+  return st.finish(sh->launch_plant_param_grad(a, p_tot, nullptr), "plant parameter gradient");
+}
+
 int m4q_plant_linearize_batch(int32_t B, int32_t dim_x, int32_t dim_u, int32_t plant_kind, int32_t T, const double* dts,
                               const double* X, const double* U, int32_t u_per_instance, const double* u_scale,
                               const double* op0, const double* ops, int32_t plant_per_instance,

@@ -11,6 +11,7 @@
 #include "m4q_fit_qr.h"
 #include "m4q_online.h"
 #include "m4q_grad.h"
+#include "m4q_plant_param.h"
 #include "m4q_plant_lin.h"
 #include "m4q_plant_qp.h"
 #include "m4q_noise.h"
@@ -2009,6 +2010,103 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NX == 9 ? 1 
 // (m4q_plant_rollout_multi_batch; the line search of m4q_plant_robust_batch)
 #include "m4q_rollout_multi.h"
 
+// (the kernels below do not depend on the library order: they are built once per (dim_x, dim_u), in the order-1 object, which is the
+// one m4q_plant_rollout_param_grad_batch asks)
+#if !defined(M4Q_NO_AUX) && M4Q_ORDER == 1
+// ---------------------------------------------------------------------------------------------
+// Plant-parameter gradient of an open-loop plant rollout against a measured trajectory (m4q_plant_rollout_param_grad_batch;
+// plant_param.py: plant_param_grad_reference is the definition), Hamiltonian and process plants, PT directions.  The forward pass is
+// plant_rollout_kernel's step, statement for statement, with every state kept in the workspace a.xs [B][N + 1][n] and the figure of
+// column t taken against column t of the member's data (quad_figure: the rollouts' own figure); the backward pass reads x_t back and
+// recomputes U and the PT derivatives dU_e (m4q_plant_param.h), adding each direction's terms with t descending.
+template <int PLANT, int PT>
+constexpr int param_lds_elems() {
+  constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;
+  constexpr int need = param_scratch_elems<NX, PT, D>();
+  return need > SCRATCH_ELEMS ? need : SCRATCH_ELEMS;          // (the forward step works in the same block)
+}
+// the block matrix has (1 + PT) d columns: past 6 of them the kernel is compiled for one wave per SIMD, as the control gradient's
+// 9 x 9 block is (two waves: expm_cols<8> of d = 2, PT = 3 spills 33 VGPRs, 136 B of scratch per lane; expm_cols<6> fits in 248)
+template <int PLANT, int PT>
+constexpr int param_waves() { return (1 + PT) * (PLANT == PLANT_PROCESS ? DQ : DD) > 6 ? 1 : WAVES; }
+template <int PLANT, int PT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(param_waves<PLANT, PT>(), 8))) void plant_param_grad_kernel(ParamGradArgs pa) {
+  static_assert(PLANT == PLANT_HAMILTONIAN || PLANT == PLANT_PROCESS, "the generator plant has no gradient kernel");
+  constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;
+  constexpr int NC = PLANT == PLANT_PROCESS ? D * D : 1;
+  const RollArgs& a = pa.roll;
+  cplx* lds = reinterpret_cast<cplx*>(m4q_lds_raw);
+  const LaneGeo L;
+  const int g = L.g, jj = L.jj, j = L.j;
+  cplx* scratch = lds + g * param_lds_elems<PLANT, PT>();
+  const int nquads = quads_of(a.B);
+  for (int quad = blockIdx.x; quad < nquads; quad += gridDim.x) {
+    const QuadRow r(quad, g, a.B);
+    const GView op0 = gview(a.plant.op0, r.q0 * a.plant.op0_stride, r.gl * (unsigned)a.plant.op0_stride);
+    const GView ops = gview(a.plant.ops, r.q0 * a.plant.ops_stride, r.gl * (unsigned)a.plant.ops_stride);
+    const GView dirs = gview(pa.dirs, r.q0 * pa.dirs_stride, r.gl * (unsigned)pa.dirs_stride);
+    const bool st = r.valid && L.lane_ok, st0 = r.valid && jj == 0;
+    const M4Q_GLOBAL cplx* Wr = a.W + j * NX;
+    const M4Q_GLOBAL cplx* yb = pa.data + r.b * pa.data_stride;
+    M4Q_GLOBAL cplx* xw = a.xs + r.b * (a.N + 1) * NX;
+    RollCtl ctl(a, r.b);
+    double dtn = gld(a.dts, 0);
+    cplx x = gld(a.x0, r.b * NX + j);
+    double J = 0.0;
+    for (int t = 0; t <= a.N; ++t) {
+      if (st) gst(xw, (long)t * NX + j, x);
+      const double cw = gld(pa.col_w, t);
+      if (cw != 0.0) {                               // (wave-uniform: every lane stays in for the broadcasts)
+        double prod = cw * quad_figure<NX>(csub(x, gld(yb, (long)t * NX + j)), Wr);
+        asm volatile("" : "+v"(prod));               // rounded before the add, as plant_param.py adds it
+        J = J + prod;
+      }
+      if (t == a.N) break;
+      double u[NU];
+      ctl.take(t, u);
+      const double dt = dtn;
+      dtn = gld(a.dts, t + 1 < a.N ? t + 1 : t);
+      M4Q_PLANT_STEP(PLANT, x, x, u, op0, ops, dt, scratch, j, jj);
+    }
+    if (st0) gst(pa.J, r.b, J);
+    wave_sync();                                   // the states of this member are in the workspace
+    cplx lam = czero();
+    {
+      const double cw = gld(pa.col_w, a.N);
+      if (cw != 0.0) lam = cscale(figure_grad<NX>(csub(x, gld(yb, (long)a.N * NX + j)), a.W, j), cw);
+    }
+    double acc[PT];
+#pragma unroll
+    for (int k = 0; k < PT; ++k) acc[k] = 0.0;
+    for (int t = a.N - 1; t >= 0; --t) {
+      double v[NU], ut[NU], ge[PT];
+#pragma unroll
+      for (int k = 0; k < NU; ++k) {
+        ut[k] = gld(ctl.u, (long)t * NU + k);
+        v[k] = ctl.sc[k] * ut[k];
+      }
+      const cplx xt = gld(xw, (long)t * NX + j);
+      lam = param_grad_step<NX, NU, PT, D, NC>(xt, lam, v, ut, pa.p, op0, ops, dirs, gld(a.dts, t), scratch, j, jj, ge);
+      const double cw = gld(pa.col_w, t);
+      if (cw != 0.0) {
+        const cplx gt = figure_grad<NX>(csub(xt, gld(yb, (long)t * NX + j)), a.W, j);
+        lam = cadd(lam, cscale(gt, cw));
+      }
+#pragma unroll
+      for (int k = 0; k < PT; ++k) acc[k] = acc[k] + ge[k];
+    }
+    if (st0) {
+#pragma unroll
+      for (int k = 0; k < PT; ++k) {
+        if (k < pa.p) gst(pa.grad_theta, r.b * pa.p + k, acc[k]);
+        else gst(pa.grad_scale, r.b * NU + (k - pa.p), acc[k]);
+      }
+    }
+    wave_sync();                                   // the row's reads of its LDS block and of the workspace are done
+  }
+}
+#endif  // !M4Q_NO_AUX && M4Q_ORDER == 1
+
 // ---------------------------------------------------------------------------------------------
 // The plant's own discrete-time Jacobians along trajectories (m4q_plant_linearize_batch; plant_linearize.py:
 // plant_linearize_reference is the definition), Hamiltonian and process plants.  The work unit is a (member, point) pair: row g of
@@ -2600,6 +2698,39 @@ static int launch_model_grad(const GradArgs& a, hipStream_t s) {
 #else
 static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 #endif
+#if !defined(M4Q_NO_AUX) && M4Q_ORDER == 1
+// the parameter-gradient kernel of plant PLANT compiled for p_tot directions, over quads of members: PT counts up from 1 to the
+// last count whose block matrix fits a row, (1 + PT) d <= 16; any other p_tot is UNBUILT
+template <int PLANT, int PT>
+static int launch_param_pt(const ParamGradArgs& a, int p_tot, hipStream_t s) {
+  constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;
+  if constexpr ((1 + PT) * D > 16) {
+    return UNBUILT;
+  } else {
+    if (p_tot == PT)
+      return launch_rows(plant_param_grad_kernel<PLANT, PT>, a, a.roll.B, sizeof(cplx) * (size_t)(ROWS * param_lds_elems<PLANT, PT>()), s);
+    return launch_param_pt<PLANT, PT + 1>(a, p_tot, s);
+  }
+}
+// (a template, as launch_by_plant: only the kernels of the branches taken are instantiated)
+template <class A>
+static int launch_param_by_plant(const A& a, int p_tot, hipStream_t s) {
+  if constexpr (!SQUARE) {
+    return UNBUILT;
+  } else {
+    const auto go = [&](auto plant) { return launch_param_pt<decltype(plant)::value, 1>(a, p_tot, s); };
+    if (a.roll.kind == PLANT_HAMILTONIAN) return go(ic<PLANT_HAMILTONIAN>{});
+    if (a.roll.kind == PLANT_PROCESS) {
+      if constexpr (QUARTIC) return go(ic<PLANT_PROCESS>{});
+      else return UNBUILT;
+    }
+    return UNBUILT;
+  }
+}
+static int launch_plant_param_grad(const ParamGradArgs& a, int p_tot, hipStream_t s) { return launch_param_by_plant(a, p_tot, s); }
+#else
+static int launch_plant_param_grad(const ParamGradArgs&, int, hipStream_t) { return UNBUILT; }
+#endif
 // the S shared sequences of MultiArgs against every member (m4q_rollout_multi.h): over quads of members with the rollouts' LDS,
 // then - a.F set - the two passes of the ordered reduction over J [B][S] on the same stream.  grad_reduce's element
 // nm is row i's vals[i][nm] when q_cols is 0, so nm = S - 1 over rows of S covers the S columns.
@@ -2645,6 +2776,7 @@ static int launch_plant_feedback(const FeedbackArgs&, hipStream_t) { return UNBU
 static int launch_plant_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 static int launch_model_grad(const GradArgs&, hipStream_t) { return UNBUILT; }
 static int launch_plant_linearize(const PlantLinArgs&, hipStream_t) { return UNBUILT; }
+static int launch_plant_param_grad(const ParamGradArgs&, int, hipStream_t) { return UNBUILT; }
 #endif
 
 #ifndef M4Q_NO_AUX
@@ -2699,7 +2831,7 @@ static const ShapeOps* shape_ops() {
                                launch_discretize, power_list, occupancy, launch_noise, launch_plant_rollout, launch_model_rollout, FIT_LDS, launch_fit,
                                ONLINE_LDS, launch_online, launch_plant_grad, launch_model_grad, OBS_KIND, launch_observe, launch_observed_plant, launch_fit_qr,
                                launch_plant_feedback, launch_model_feedback, launch_refit, launch_refit_qr, launch_plant_linearize, launch_plant_qp,
-                               launch_plant_step, launch_plant_multi, launch_model_multi};
+                               launch_plant_step, launch_plant_multi, launch_model_multi, launch_plant_param_grad};
   return &ops;
 }
 

@@ -102,6 +102,17 @@ def _gradient_batch(exp, x0s, ts, us, W, target, op0, u_scale, figure, weights, 
                                     figure=figure, weights=weights, reduce=reduce, scale_grad=scale_grad)
 
 
+def _calibrate_batch(exp, x0s, ts, us, dirs, W, data, op0, kwargs):
+    """calibrate_batch of the two unitary device plants: simulate_batch's arguments into plant_calibrate_batch."""
+    from .plant_param import plant_calibrate_batch
+    x0s = np.asarray(x0s, dtype=np.complex128)
+    if x0s.ndim == 1:
+        x0s = x0s[None]
+    own0, ops = exp.operators()
+    u = held_controls(us, ts, len(exp.H1_list), x0s.shape[0])
+    return plant_calibrate_batch(x0s, u, own0 if op0 is None else op0, ops, dirs, ts, W, data, kind=exp.plant_kind, **kwargs)
+
+
 def _linearize_batch(exp, X, U, ts_or_dt, u_scale, outputs, op0):
     """linearize_batch of the two unitary device plants: the plant's own operators() unless per-member op0 [B, k, k] is given."""
     from .plant_linearize import plant_linearize_batch
@@ -294,6 +305,17 @@ class QExperiment(Experiment):
         discretised model (model_rollout_grad_batch)."""
         return _gradient_batch(self, x0s, ts, us, W, target, op0, u_scale, figure, weights, reduce, scale_grad)
 
+    def calibrate_batch(self, x0s, ts, us, dirs, W, data, op0=None, **kwargs):
+        """Fits this plant's parameters member by member to measured trajectories (plant_calibrate_batch): x0s, ts, us, op0 as
+        simulate_batch - op0 the nominal drift, this plant's own unless given -, dirs [p, d, d] or [B|1, p, d, d] the Hermitian
+        directions of the drift, data [B|1, len(ts), n] what was measured, the keywords plant_calibrate_batch's (theta0, bounds,
+        fit_scale, u_scale, col_w, iters, mem, steps, tol, gtol, step0).  Returns its dict.  With collapse operators the plant is a
+        generator plant, which is refused as it is there."""
+        if self.plant_kind == _lib.PLANT_GENERATOR:
+            raise ValueError("QExperiment.calibrate_batch: with collapse operators the plant is a generator plant, which has no "
+                             "parameter gradient on the device - fit the parameters through its discretised model")
+        return _calibrate_batch(self, x0s, ts, us, dirs, W, data, op0, kwargs)
+
     def linearize_batch(self, X, U, ts_or_dt, u_scale=None, outputs=("A", "B", "Delta"), op0=None):
         """The exact Jacobians of this plant's held-control step along trajectories, for an ensemble in one launch
         (plant_linearize_batch): X [B, T, n] the points (ensemble axis first, then time), U [T, m] or [B, T, m] the controls held
@@ -355,6 +377,11 @@ class LExperiment(QExperiment):
         """Refused: the generator plant has no gradient kernel."""
         raise ValueError("LExperiment.gradient_batch: the generator plant has no control gradient on the device - discretise the "
                          "generators (discretize_homogeneous) and take the gradient of the model with model_rollout_grad_batch")
+
+    def calibrate_batch(self, *args, **kwargs):
+        """Refused: the generator plant has no parameter-gradient kernel."""
+        raise ValueError("LExperiment.calibrate_batch: the generator plant has no parameter gradient on the device - fit the "
+                         "parameters through the discretised model (discretize_homogeneous, model_rollout_grad_batch)")
 
     def linearize_batch(self, *args, **kwargs):
         """Refused: the generator plant has no linearisation kernel."""
@@ -501,6 +528,11 @@ class QSynthesis(Experiment):
         """The figure of simulate_batch's rollout and its gradient with respect to the held controls, for an ensemble in one launch
         (plant_rollout_grad_batch on the process plant): arguments and the returned dict as QExperiment.gradient_batch."""
         return _gradient_batch(self, x0s, ts, us, W, target, op0, u_scale, figure, weights, reduce, scale_grad)
+
+    def calibrate_batch(self, x0s, ts, us, dirs, W, data, op0=None, **kwargs):
+        """Fits the process plant's parameters member by member to measured process vectors (plant_calibrate_batch): arguments and
+        the returned dict as QExperiment.calibrate_batch, data [B|1, len(ts), d^4]."""
+        return _calibrate_batch(self, x0s, ts, us, dirs, W, data, op0, kwargs)
 
     def linearize_batch(self, X, U, ts_or_dt, u_scale=None, outputs=("A", "B", "Delta"), op0=None):
         """The exact Jacobians of the process plant's held-control step along trajectories, for an ensemble in one launch

@@ -1,0 +1,204 @@
+"""The plant-parameter gradient on the device (plant_param_grad_kernel) and the calibration that runs on it against the NumPy /
+SciPy definitions of mpc4quantum_amd/plant_param.py, which tests/test_plant_param_host.py holds to central differences.  Tolerance:
+the one tests/test_gpu_grad.py holds grad_scale to, 1e-10 max(1, max|ref|) - the same exponential and the same products.  Shapes
+are the smallest that can go wrong: B = 5 (a ragged quad) and B = 1, N in {1, 2, 7}, p = 1 and the largest count the shape allows;
+one case with 4,098 quads, past the grid the launch is capped at."""
+import numpy as np
+import pytest
+
+import mpc4quantum_amd as m4q
+from mpc4quantum_amd import _lib, plant_param
+from tests import grad_cases as gc
+from tests import kernel_variants as kv
+from tests import plant_param_cases as pc
+from tests.test_gpu_grad import TOL
+from tests.test_plant_param_host import _Call
+
+pytestmark = pytest.mark.gpu
+
+PLANTS = ("4-1", "9-2", "16-3", "16-1-process")          # (4, 1, 1), (9, 2, 1), (16, 3, 1) Hamiltonian; (16, 1, 1) process
+
+
+def _counts(name):
+    """(p, scale_grad): one direction; the largest count; the largest count that still leaves room for the drive gains."""
+    out = [(1, False), (pc.p_max(name), False)]
+    if pc.p_max(name, True) >= 1:
+        out.append((pc.p_max(name, True), True))
+    return out
+
+
+CASES = [(name, p, sg) for name in PLANTS for p, sg in _counts(name)]
+
+
+def _close(out, ref, what):
+    assert set(out) == set(ref)
+    for key in sorted(ref):
+        err = np.abs(out[key] - ref[key]).max() / max(1.0, np.abs(ref[key]).max())
+        print("%s %s: max|ref| = %.3e, max|d| / max(1, max|ref|) = %.2e" % (what, key, np.abs(ref[key]).max(), err))
+        assert out[key].shape == ref[key].shape and np.isfinite(out[key]).all()
+        assert err <= TOL
+
+
+@pytest.mark.parametrize("N", [1, 2, 7])
+@pytest.mark.parametrize("variant,B", [("shared", 5), ("per", 5), ("shared", 1), ("per", 1)], ids=lambda v: str(v))
+@pytest.mark.parametrize("name,p,sg", CASES, ids=lambda v: str(v))
+def test_device_against_the_definition(name, p, sg, variant, B, N):
+    c, args, kw = pc.inputs(name, variant, B, N, p, 9600 + 31 * PLANTS.index(name) + 7 * p + 101 * B + N)
+    ref = m4q.plant_param_grad_reference(*args, scale_grad=sg, **kw)
+    out = m4q.plant_rollout_param_grad_batch(*args, scale_grad=sg, **kw)
+    _close(out, ref, "%s p=%d%s %s B=%d N=%d" % (name, p, "+gains" if sg else "", variant, B, N))
+    assert np.abs(ref["grad_theta"]).max() > 1e-3
+    if sg:                                              # without the gains the parameter gradient is the same to the bound
+        plain = m4q.plant_rollout_param_grad_batch(*args, **kw)
+        assert set(plain) == {"J", "grad_theta"} and np.array_equal(plain["J"], out["J"])
+        assert np.abs(plain["grad_theta"] - out["grad_theta"]).max() <= TOL * max(1.0, np.abs(ref["grad_theta"]).max())
+
+
+# ---------------------------------------------------------------- properties that need no tolerance
+def _figures(c, args, kw, data):
+    """q [B, N + 1]: column t of plant_rollout_batch's figure against column t of the shared data."""
+    x0, u, op0, ops, _, ts, W, _ = args
+    N = data.shape[0] - 1
+    return np.stack([m4q.plant_rollout_batch(x0, u, op0, ops, ts, c.kind, u_scale=kw["u_scale"], W=W, target=data[t], keep="none",
+                                             figure="all")["q"][:, t] for t in range(N + 1)], axis=1)
+
+
+@pytest.mark.parametrize("name", PLANTS)
+def test_objective_is_the_ordered_sum_of_the_rollouts_figures(name):
+    c, args, kw = pc.inputs(name, "shared", 5, 7, 1, 9700 + PLANTS.index(name))
+    data = args[7]
+    q = _figures(c, args, kw, data)
+    ones = m4q.plant_rollout_param_grad_batch(*args, kind=c.kind, u_scale=kw["u_scale"])       # col_w: ones
+    J = np.zeros(5)
+    for t in range(8):
+        J = J + q[:, t]
+    assert np.array_equal(ones["J"], J) and np.all(np.abs(J) > 1e-3)         # (W is indefinite: J may have either sign)
+    # weights, zeros among them: a column of weight 0 contributes nothing - whatever data holds there
+    cw = kw["col_w"]
+    assert cw[0] == 0.0 and cw[3] == 0.0 and cw[6] == 0.0 and np.all(cw[[1, 2, 4, 5, 7]] > 0)
+    J = np.zeros(5)
+    for t in range(8):
+        if cw[t] != 0.0:
+            J = J + cw[t] * q[:, t]
+    got = m4q.plant_rollout_param_grad_batch(*args, **kw)
+    assert np.array_equal(got["J"], J)
+    blind = np.array(data)
+    blind[cw == 0.0] = np.nan
+    again = m4q.plant_rollout_param_grad_batch(*args[:7], blind, **kw)
+    assert all(np.array_equal(got[k], again[k]) for k in got) and np.isfinite(got["grad_theta"]).all()
+
+
+@pytest.mark.parametrize("variant", ["shared", "per"])
+@pytest.mark.parametrize("name,p,sg", [("4-1", 6, True), ("9-2", 4, False), ("16-3", 3, False), ("16-1-process", 6, True)], ids=lambda v: str(v))
+def test_results_do_not_depend_on_the_batch_split(name, p, sg, variant):
+    c, args, kw = pc.inputs(name, variant, 5, 7, p, 9750 + PLANTS.index(name))
+    full = m4q.plant_rollout_param_grad_batch(*args, scale_grad=sg, **kw)
+
+    def part(idx):
+        def cut(a, lead):
+            return a[idx] if (a is not None and np.ndim(a) == lead and np.shape(a)[0] == 5) else a
+        x0, u, op0, ops, dirs, ts, W, data = args
+        return m4q.plant_rollout_param_grad_batch(x0[idx], cut(u, 3), cut(op0, 3), cut(ops, 4), cut(dirs, 4), ts, W, cut(data, 3),
+                                                  kind=c.kind, u_scale=cut(kw["u_scale"], 2), col_w=kw["col_w"], scale_grad=sg)
+    two, three = part(slice(0, 2)), part(slice(2, 5))
+    for key in full:
+        assert np.array_equal(full[key], np.concatenate([two[key], three[key]])), key
+    assert len({full["grad_theta"][b].tobytes() for b in range(5)}) == 5                      # (the members do differ)
+
+
+def test_member_does_not_depend_on_its_place():
+    """Five distinct members tiled to 16,389 - 4,098 quads, one more than the grid, the last one ragged."""
+    B = kv.QUAD_WRAP + 5
+    assert B % kv.ROWS and B > kv.QUAD_WRAP
+    c, args, kw = pc.inputs("4-1", "per", 5, 2, 2, 9790)
+    x0, u, op0, ops, dirs, ts, W, data = args
+    five = m4q.plant_rollout_param_grad_batch(*args, scale_grad=True, **kw)
+    idx = np.arange(B) % 5
+    full = m4q.plant_rollout_param_grad_batch(x0[idx], u[idx], op0[idx], ops[idx], dirs[idx], ts, W, data[idx], scale_grad=True, **kw)
+    for key in five:
+        assert np.isfinite(full[key]).all()
+        assert np.array_equal(full[key], five[key][idx]), key
+
+
+def test_data_of_the_rollout_itself_has_no_misfit():
+    """The forward pass is the rollout's own: against plant_rollout_batch's states of the same plants J and its gradient are 0."""
+    for name in PLANTS:
+        c, args, kw = pc.inputs(name, "per", 5, 7, 1, 9800 + PLANTS.index(name))
+        x0, u, op0, ops, dirs, ts, W, _ = args
+        xs = m4q.plant_rollout_batch(x0, u, op0, ops, ts, c.kind, keep="all")["xs"]
+        sg = pc.p_max(name, True) >= 1
+        out = m4q.plant_rollout_param_grad_batch(x0, u, op0, ops, dirs, ts, W, xs, kind=c.kind, scale_grad=sg)
+        assert not out["J"].any() and not out["grad_theta"].any() and not (sg and out["grad_scale"].any())
+
+
+# ---------------------------------------------------------------- the calibration
+def test_calibration_follows_the_definition_step_for_step():
+    """plant_calibrate_batch against the same loop driven by the definition, on the host test's case set: every member's status,
+    n_iter and accepted steps are the same, theta within the bound times the iterations the member ran."""
+    cal = pc.calibration_case()
+    args = cal.args(cal.data_reference())
+    ref = m4q.plant_calibrate_reference(*args, **cal.kwargs())
+    out = m4q.plant_calibrate_batch(*args, **{k: v for k, v in cal.kwargs().items()})
+    print("status", out["status"], "n_iter", out["n_iter"], "max|dtheta|", np.abs(out["theta"] - ref["theta"]).max(axis=1))
+    assert np.array_equal(ref["status"], np.ones(cal.B))
+    for key in ("status", "n_iter", "alpha_hist"):
+        assert np.array_equal(out[key], ref[key]), key
+    assert out["evaluations"] == ref["evaluations"]
+    scale = max(1.0, np.abs(ref["theta"]).max())
+    assert np.all(np.abs(out["theta"] - ref["theta"]).max(axis=1) <= TOL * scale * np.maximum(ref["n_iter"], 1))
+    assert np.all(np.diff(out["cost_hist"], axis=1) <= 0) and np.abs(out["theta"] - cal.theta_true).max() <= 1e-6
+    assert np.array_equal(out["op0"], m4q.plant_param_op0(cal.c.op0, cal.dirs, out["theta"]))
+
+
+def test_calibration_on_the_devices_own_data_and_through_the_experiment():
+    """Data from plant_rollout_batch on the true plants: the member that starts at its truth has J = 0 on the device and stops at
+    iteration 0; QExperiment.calibrate_batch passes its own operators."""
+    cal = pc.calibration_case()
+    c = cal.c
+    data = m4q.plant_rollout_batch(cal.x0, cal.u, cal.op0_true(), c.ops, c.dt, c.kind, keep="all")["xs"]
+    out = m4q.plant_calibrate_batch(*cal.args(data), **cal.kwargs())
+    assert np.array_equal(out["status"], np.ones(cal.B)) and out["n_iter"][0] == 0 and out["cost"][0] == 0.0
+    assert np.abs(out["theta"] - cal.theta_true).max() <= 1e-6
+    exp = m4q.QExperiment(c.op0, list(c.ops))
+    ts = c.dt * np.arange(cal.N + 1)
+    us = np.concatenate([cal.u.T, np.zeros((c.m, 1))], axis=1)               # as simulate() takes them; the last column is unused
+    kw = {k: v for k, v in cal.kwargs().items() if k != "kind"}
+    got = exp.calibrate_batch(cal.x0, ts, us, cal.dirs, cal.W, data, **kw)
+    want = m4q.plant_calibrate_batch(cal.x0, cal.u, c.op0, c.ops, cal.dirs, ts, cal.W, data, **cal.kwargs())
+    assert all(np.array_equal(got[k], want[k]) for k in ("theta", "cost_hist", "n_iter", "status", "op0"))
+
+
+def test_process_plant_calibrates_through_qsynthesis():
+    c = gc.plant_case("16-1-process")
+    B, N = 3, 8
+    rng = np.random.default_rng(9900)
+    dirs = pc.physical_directions(2)[:1]
+    theta = rng.uniform(-0.05, 0.05, (B, 1))
+    sc = 1 + rng.uniform(-0.1, 0.1, (B, 1))
+    x0 = c.states(rng, B)
+    u = rng.uniform(-c.sat, c.sat, (N, 1))
+    data = m4q.plant_rollout_batch(x0, u, m4q.plant_param_op0(c.op0, dirs, theta), c.ops, c.dt, c.kind, u_scale=sc, keep="all")["xs"]
+    exp = m4q.QSynthesis(c.op0, list(c.ops))
+    us = np.concatenate([u.T, np.zeros((1, 1))], axis=1)
+    out = exp.calibrate_batch(x0, c.dt * np.arange(N + 1), us, dirs, np.eye(16), data, fit_scale=True, iters=60, steps=8, tol=0.0, gtol=1e-8,
+                              step0=0.05)
+    print("status", out["status"], "n_iter", out["n_iter"], "cost", out["cost"])
+    assert np.array_equal(out["status"], np.ones(B))
+    assert np.abs(out["theta"] - theta).max() <= 1e-5 and np.abs(out["u_scale"] - sc).max() <= 1e-5
+
+
+# ---------------------------------------------------------------- refusals
+def test_refusals_return_the_documented_codes():
+    who = b"m4q_plant_rollout_param_grad_batch"
+    err = _lib.lib().m4q_last_error
+    assert _Call(n=9, d=9, p=1, kind=_lib.PLANT_GENERATOR)() == _lib.E_UNSUPPORTED and who in err() and b"generator" in err()
+    assert _Call(n=16, m=2, d=4)() == _lib.E_UNSUPPORTED and who in err() and b"plant-only" in err()
+    assert _Call(kind=_lib.PLANT_NONE)() == _lib.E_BADARG and who in err()
+    assert _Call(p=5)() == _lib.E_UNSUPPORTED and who in err() and b"at most 4 directions for d = 3" in err()
+    assert _Call()() == 0 and _Call(n=16, m=1, d=2, p=6, kind=_lib.PLANT_PROCESS)(gs=np.zeros((2, 1))) == 0
+    c = gc.plant_case("9-2")
+    x0 = c.states(np.random.default_rng(9950), 2)
+    with pytest.raises(ValueError, match="at most 4 directions"):
+        m4q.plant_rollout_param_grad_batch(x0, np.zeros((3, 2)), c.op0, c.ops, pc.directions(np.random.default_rng(1), 3, 3), c.dt, np.eye(9),
+                                           np.zeros((4, 9)), scale_grad=True)
+    assert plant_param.max_directions(3) == 4
