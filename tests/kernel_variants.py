@@ -9,6 +9,8 @@ closed_loop_cells() is what tests/test_gpu_variant_matrix.py runs one teacher-fo
 single-kernel entry points (linearize, quad_program, discretize, plant_step) per shape; aux_cells() lists every instance of the
 auxiliary kernel families (rollouts, gradients, feedback laws, plant linearisation, the four fits, the online update) from mirrors
 of M4Q_NO_AUX, FitLayout / OnlineLayout and the plant dispatch: what tests/test_gpu_aux_matrix.py runs one case of each.
+param_cells() lists every plant_param_grad_kernel<PLANT, PT> (tests/test_plant_param_host.py pins its rule lines,
+tests/test_gpu_plant_param.py runs every one).
 scenario() gives seeded, well-conditioned host inputs for every closed-loop shape in the configs.build dict layout.  pieces() mirrors how one launch cuts a member's run into
 work items (tests/test_gpu_launch_schedule.py); _planned() / _check_planned() plan exits on a member's own stored states and check
 them (tests/test_gpu_exit_condition.py, tests/test_gpu_launch_schedule.py)."""
@@ -266,6 +268,31 @@ def aux_cells():
             cells += [AuxCell(f, nx, nu, 0, kind) for f in ("plant_rollout", "plant_feedback")]
             cells += [AuxCell(f, nx, nu, 0, REFUSED if kind == GENERATOR else kind) for f in ("plant_grad", "plant_linearize")]
     return cells
+
+
+def param_dim(nx, kind):
+    """constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;  (launch_param_pt, plant_param_grad_kernel)"""
+    return fourth_root(nx) if kind == PROCESS else dd(nx)
+
+
+def param_cells():
+    """[(nx, nu, kind, PT)]: every plant_param_grad_kernel<PLANT, PT> the library holds.  The kernel lives in the order-1 object of
+    every square shape that is not plant-only (#if !defined(M4Q_NO_AUX) && M4Q_ORDER == 1), for the Hamiltonian plant and, where
+    QUARTIC, the process plant (launch_param_by_plant), and launch_param_pt counts PT up from 1 while (1 + PT) * D <= 16."""
+    nm = sorted({(nx, nu) for nx, nu, o, po in shapes() if square(nx) and not po and o == 1})
+    cells = []
+    for kind in (HAMILTONIAN, PROCESS):
+        for nx, nu in nm:
+            if kind == PROCESS and not quartic(nx):
+                continue
+            cells += [(nx, nu, kind, pt) for pt in range(1, 16 // param_dim(nx, kind))]
+    return cells
+
+
+def param_waves(nx, kind, pt):
+    """constexpr int param_waves() { return (1 + PT) * (PLANT == PLANT_PROCESS ? DQ : DD) > 6 ? 1 : WAVES; }
+    constexpr int WAVES = NX <= 9 ? 2 : 1;"""
+    return 1 if (1 + pt) * param_dim(nx, kind) > 6 else (2 if nx <= 9 else 1)
 
 
 # ---------------------------------------------------------------- scenarios

@@ -6,6 +6,7 @@ import mpc4quantum_amd as m4q
 from mpc4quantum_amd import _lib
 from mpc4quantum_amd.plant_param import max_directions
 from tests import grad_cases as gc
+from tests import kernel_variants as kv
 
 
 def _herm(rng, d):
@@ -61,6 +62,61 @@ def inputs(name, variant, B, N, p, seed):
 def p_max(name, scale_grad=False):
     c = gc.plant_case(name)
     return max_directions(c.d) - (c.m if scale_grad else 0)
+
+
+def live_directions(rng, d, p, B=None):
+    """directions(), with every direction that is the zero matrix (the anharmonicity of a two-level system: n (n - 1) / 2 = 0 at
+    d = 2) replaced by one more random Hermitian draw: no column of the gradient is 0 by construction."""
+    dirs = np.array(directions(rng, d, p, B))
+    for j in range(p):
+        if not dirs[..., j, :, :].any():
+            dirs[..., j, :, :] = _herm(rng, d)
+    return dirs
+
+
+# ---------------------------------------------------------------- the direction-count matrix
+# every (cell, PT) of kernel_variants.param_cells() at both splits of PT and in both layouts: B = 5 (a ragged quad), N = 2 (one step
+# with a next step to prefetch, one without)
+MATRIX_B, MATRIX_N = 5, 2
+# A case whose reference fails the preconditions of tests/test_plant_param_host.py (a column of the gradient that is all but 0, two
+# columns all but equal) draws again: {case id: draws skipped}.  None does.
+MATRIX_RESEED = {}
+
+
+def cell_name(nx, nu, kind):
+    return "%d-%d%s" % (nx, nu, "-process" if kind == kv.PROCESS else "")
+
+
+def matrix_cases():
+    """[(name, PT, p, scale_grad, variant)]: (p = PT, no gains) and, where PT - m >= 1, (p = PT - m, the m gains)."""
+    out = []
+    for nx, nu, kind, pt in kv.param_cells():
+        for p, sg in [(pt, False)] + ([(pt - nu, True)] if pt - nu >= 1 else []):
+            out += [(cell_name(nx, nu, kind), pt, p, sg, variant) for variant in ("shared", "per")]
+    return out
+
+
+def matrix_id(case):
+    name, pt, p, sg, variant = case
+    return "%s-PT%d-p%d%s-%s" % (name, pt, p, "+gains" if sg else "", variant)
+
+
+def matrix_inputs(case):
+    """(case, args, kwargs) as inputs() gives them, the directions live_directions()' (drawn after everything else)."""
+    name, pt, p, sg, variant = case
+    names = sorted({c[0] for c in matrix_cases()})
+    seed = 12000 + 100 * names.index(name) + 10 * pt + 2 * int(sg) + (variant == "per") + 100000 * MATRIX_RESEED.get(matrix_id(case), 0)
+    c, args, kw = inputs(name, variant, MATRIX_B, MATRIX_N, p, seed)
+    rng = np.random.default_rng(seed + 50000)
+    dirs = live_directions(rng, c.d, p, MATRIX_B if variant == "per" else None)
+    return c, args[:4] + (dirs,) + args[5:], kw
+
+
+def columns(ref):
+    """(smallest column maximum, smallest distance of two columns over max|ref|) of [grad_theta, grad_scale] [B, p_tot]."""
+    G = np.concatenate([ref["grad_theta"]] + ([ref["grad_scale"]] if "grad_scale" in ref else []), axis=1)
+    far = [np.abs(G[:, i] - G[:, j]).max() for i in range(G.shape[1]) for j in range(i)]
+    return np.abs(G).max(axis=0).min(), (min(far) / np.abs(G).max() if far else np.inf)
 
 
 # ---------------------------------------------------------------- the calibration's case set

@@ -14,7 +14,11 @@ Layouts, as every plant file's:
 A quad of five: member QUIET sees controls inside the configuration's bound (s = 0 at every step), the others see FRACTIONS of
 LEVEL[cell] x sat, shaped along the horizon by ENVELOPE so that a driven member's s changes from step to step.  B = 1: the one
 member is driven at the full level.  The truth of every case is tests/golden/strong_drive_truth.npz
-(tests/golden/make_golden_strong_drive.py: mpmath at 40 digits)."""
+(tests/golden/make_golden_strong_drive.py: mpmath at 40 digits).
+
+The parameter gradient (plant_param_grad_kernel) runs on the same cases: ParamCase adds the directions, the data and the column
+weights of one direction set to a Case, and param_block() is the (1 + p_tot) d matrix of param_block_expm (csrc/m4q_plant_param.h).
+Its truth is tests/golden/strong_drive_param_truth.npz (tests/golden/make_golden_strong_drive_param.py)."""
 import math
 import os
 
@@ -24,6 +28,7 @@ from mpc4quantum_amd import _lib
 from mpc4quantum_amd.vectorize import liouvillian
 from tests import grad_cases as gc
 from tests import kernel_variants as kv
+from tests import plant_param_cases as pc
 
 THETA13 = 5.371920351148152              # const double theta13 = 5.371920351148152;
 S_CAP = 60                               # if (s > 60) s = 60;
@@ -236,3 +241,126 @@ def linearisation(cs, tr, X):
                                           + np.einsum('ac,cgx,eg->aex', U, R, dU[k].conj())).reshape(-1)
                 Delta[b, t] -= Bm[b, t, :, k] * u[t, k]
     return A, Bm, Delta
+
+
+# ---------------------------------------------------------------- the parameter gradient on the same cases
+PARAM_CELLS = ("4-1", "4-2", "9-2", "16-1", "16-3", "16-1-process", "16-3-process")       # (the C entry refuses (16, 2): plant-only)
+# A (case, set) whose preconditions (tests/test_strong_drive_host.py) fail on the first draw takes the next: {pair id: draws skipped}.
+# 4-1-shared-B5-N1 at p = 7: the first draw's random directions lift the quiet member's block to s = 1 without any gains.
+# 16-3-process-per-B1-N1 at p = 7: the one member's gradient in the first draw's direction 1 is 6.0e-4, under the 1e-3 every
+# column has to exceed.
+PARAM_RESEED = {"4-1-shared-B5-N1/p7": 1, "16-3-process-per-B1-N1/p7": 1}
+
+
+def param_sets(cell):
+    """[(p, scale_grad)] of a cell: the largest count without the gains and, where one direction or more is left, with them."""
+    return [(pc.p_max(cell), False)] + ([(pc.p_max(cell, True), True)] if pc.p_max(cell, True) >= 1 else [])
+
+
+def all_param_pairs(cells=PARAM_CELLS):
+    return [(cell, variant, B, N, p, sg) for cell, variant, B, N in all_cases(cells) for p, sg in param_sets(cell)]
+
+
+def pair_id(cell, variant, B, N, p, sg):
+    return "%s/p%d%s" % (case_id(cell, variant, B, N), p, "+gains" if sg else "")
+
+
+class ParamCase:
+    """One direction set on one Case cs (whose controls, operators, grid and members it keeps): p directions dirs [p, d, d] (shared
+    layout) or [B, p, d, d] (per), with scale_grad the m drive gains after them; data: a trajectory that is no rollout, [N + 1, n]
+    or [B, N + 1, n]; col_w: zeros at columns 0, 3, 6 (shared), None (per) - as plant_param_cases.inputs."""
+
+    def __init__(self, cs, p, sg):
+        self.cs, self.p, self.sg = cs, p, sg
+        self.id = pair_id(cs.cell, cs.variant, cs.B, cs.N, p, sg)
+        self.p_tot = p + (cs.m if sg else 0)
+        seed = 8800 + 97 * CELLS.index(cs.cell) + 11 * cs.B + cs.N + (500 if cs.per else 0) + 7 * p
+        rng = np.random.default_rng(seed + 100000 * PARAM_RESEED.get(self.id, 0))
+        self.dirs = pc.live_directions(rng, cs.d, p, cs.B if cs.per else None)
+        self.data = pc.data_for(rng, cs.c, cs.B, cs.N, cs.per)
+        self.col_w = None
+        if not cs.per:
+            self.col_w = rng.uniform(0.5, 1.5, cs.N + 1)
+            self.col_w[::3] = 0.0
+            if cs.N == 1:
+                self.col_w[1] = 1.0
+            self.col_w.setflags(write=False)
+        self.dirs.setflags(write=False)
+        self.data.setflags(write=False)
+
+    def weights(self):
+        return np.ones(self.cs.N + 1) if self.col_w is None else self.col_w
+
+    def member_dirs(self, b):
+        return self.dirs[b] if self.dirs.ndim == 4 else self.dirs
+
+    def member_data(self, b):
+        return self.data[b] if self.data.ndim == 3 else self.data
+
+    def directions(self, b, t):
+        """[E_1 .. E_p_tot] of member b's step t: -i dt D_j, then (gains) -i dt u[t][k] H_k with the UNSCALED control."""
+        cs = self.cs
+        f = -1j * cs.dts[t]
+        Es = [f * D for D in self.member_dirs(b)]
+        if self.sg:
+            _, ops = cs.member_ops(b)
+            Es += [f * cs.useq(b)[t, k] * ops[k] for k in range(cs.m)]
+        return Es
+
+    def param_block(self, b, t):
+        """The (1 + p_tot) d matrix of param_block_expm: X on the diagonal blocks, [X, E_1 .. E_p_tot] as the first block row."""
+        X, _ = self.cs.generator(b, t)
+        d, n = X.shape[0], 1 + self.p_tot
+        Z = np.zeros((n * d, n * d), dtype=complex)
+        for k in range(n):
+            Z[k * d:(k + 1) * d, k * d:(k + 1) * d] = X
+        for k, E in enumerate(self.directions(b, t)):
+            Z[:d, (1 + k) * d:(2 + k) * d] = E
+        return Z
+
+    def norms(self):
+        """{"forward": [B, N], "param_block": [B, N]}: the 1-norms the forward and the backward pass of the kernel take s from."""
+        cs = self.cs
+        return {"forward": cs.norms()["forward"],
+                "param_block": np.array([[norm1(self.param_block(b, t)) for t in range(cs.N)] for b in range(cs.B)])}
+
+    def s(self):
+        return {key: np.vectorize(squarings)(val) for key, val in self.norms().items()}
+
+    def args(self):
+        """(args, kwargs) of plant_param_grad_reference / plant_rollout_param_grad_batch."""
+        cs = self.cs
+        return ((cs.x0, cs.us, cs.op0, cs.ops, self.dirs, cs.ts, cs.W, self.data),
+                dict(kind=cs.kind, u_scale=cs.u_scale, col_w=self.col_w, scale_grad=self.sg))
+
+    def alone(self, b):
+        """The same for member b by itself, as a B = 1 call takes it."""
+        cs = self.cs
+        x0, us, op0, ops, sc, _ = cs.alone(b)
+        return ((x0, us, op0, ops, self.member_dirs(b), cs.ts, cs.W, self.member_data(b)),
+                dict(kind=cs.kind, u_scale=sc, col_w=self.col_w, scale_grad=self.sg))
+
+
+_PAIRS = {}
+
+
+def param_case(cell, variant, B, N, p, sg):
+    key = (cell, variant, B, N, p, sg)
+    if key not in _PAIRS:
+        _PAIRS[key] = ParamCase(case(cell, variant, B, N), p, sg)
+    return _PAIRS[key]
+
+
+PARAM_TRUTH_FILE = os.path.join(os.path.dirname(TRUTH_FILE), "strong_drive_param_truth.npz")
+_PARAM_TRUTH = []
+
+
+def param_truth(pr):
+    """The stored truth of a (case, set): "J" [B], "grad_theta" [B, p] and, with the gains, "grad_scale" [B, m]."""
+    if not _PARAM_TRUTH:
+        with np.load(PARAM_TRUTH_FILE) as z:
+            _PARAM_TRUTH.append({k: z[k] for k in z.files})
+        for a in _PARAM_TRUTH[0].values():
+            a.setflags(write=False)
+    pre = pr.id + "/"
+    return {k[len(pre):]: a for k, a in _PARAM_TRUTH[0].items() if k.startswith(pre)}

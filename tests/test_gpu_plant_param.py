@@ -2,7 +2,12 @@
 SciPy definitions of mpc4quantum_amd/plant_param.py, which tests/test_plant_param_host.py holds to central differences.  Tolerance:
 the one tests/test_gpu_grad.py holds grad_scale to, 1e-10 max(1, max|ref|) - the same exponential and the same products.  Shapes
 are the smallest that can go wrong: B = 5 (a ragged quad) and B = 1, N in {1, 2, 7}, p = 1 and the largest count the shape allows;
-one case with 4,098 quads, past the grid the launch is capped at."""
+one case with 4,098 quads, past the grid the launch is capped at.
+The direction-count matrix launches every plant_param_grad_kernel<PLANT, PT> the library holds - the 38 (cell, PT) of
+kernel_variants.param_cells(), the middle counts included, where param_block_expm's clamps and selects, the occupancy switch of
+param_waves and the grad_theta / grad_scale store routing are not at an end of their range - at both splits of PT (p = PT without
+the gains; p = PT - m with them) and in both layouts, B = 5, N = 2.  tests/test_plant_param_host.py holds the preconditions that
+make a misrouted direction visible there (no column trivial, no two columns alike)."""
 import numpy as np
 import pytest
 
@@ -49,6 +54,23 @@ def test_device_against_the_definition(name, p, sg, variant, B, N):
     _close(out, ref, "%s p=%d%s %s B=%d N=%d" % (name, p, "+gains" if sg else "", variant, B, N))
     assert np.abs(ref["grad_theta"]).max() > 1e-3
     if sg:                                              # without the gains the parameter gradient is the same to the bound
+        plain = m4q.plant_rollout_param_grad_batch(*args, **kw)
+        assert set(plain) == {"J", "grad_theta"} and np.array_equal(plain["J"], out["J"])
+        assert np.abs(plain["grad_theta"] - out["grad_theta"]).max() <= TOL * max(1.0, np.abs(ref["grad_theta"]).max())
+
+
+# ---------------------------------------------------------------- every compiled direction count
+MATRIX = pc.matrix_cases()
+
+
+@pytest.mark.parametrize("case", MATRIX, ids=[pc.matrix_id(c) for c in MATRIX])
+def test_every_direction_count_against_the_definition(case):
+    name, pt, p, sg, variant = case
+    c, args, kw = pc.matrix_inputs(case)
+    ref = m4q.plant_param_grad_reference(*args, scale_grad=sg, **kw)
+    out = m4q.plant_rollout_param_grad_batch(*args, scale_grad=sg, **kw)
+    _close(out, ref, pc.matrix_id(case))
+    if sg:                                              # without the gains (kernel PT - m): the same J, the same parameter gradient
         plain = m4q.plant_rollout_param_grad_batch(*args, **kw)
         assert set(plain) == {"J", "grad_theta"} and np.array_equal(plain["J"], out["J"])
         assert np.abs(plain["grad_theta"] - out["grad_theta"]).max() <= TOL * max(1.0, np.abs(ref["grad_theta"]).max())

@@ -5,7 +5,10 @@ tests/golden/strong_drive_truth.npz (mpmath at 40 digits), at the bound each fam
     Hamiltonian and process states  rel <= 1e-12        generator states  rel <= 1e-11        (rel: max|d| / max(1, max|ref|))
     gradients, linearisation, QP    1e-10 max(1, max|ref|)                                     
 tests/test_strong_drive_host.py holds the preconditions and the fp64 definitions (to a tenth of these bounds); every test here
-prints the device's error beside the definition's.  The truth is read, not computed."""
+prints the device's error beside the definition's.  The truth is read, not computed.
+The parameter gradient (plant_param_grad_kernel) runs on the same cases with the (1 + p_tot) d block of param_block_expm squared
+- in the shared layout with the gains the quiet member's block squares 2 to 5 times while its forward step does not - against
+tests/golden/strong_drive_param_truth.npz, at the gradient family's bound."""
 import numpy as np
 import pytest
 
@@ -60,11 +63,11 @@ def _definition_chain(cs):
     return _CHAINS[cs.id]
 
 
-def _figure_bound(cs, tr):
+def _figure_bound(cs, tr, data=None):
     """The bound of a figure q = Re(d^H W d), d = x - f, against the truth: the rollout family's bound of the figure's own
     evaluation, 1e-12 max(1, sum|W| dmax^2) (tests/test_gpu_rollout.py), plus what a state within its bound e = 1e-12 max(1, max|x|)
-    (1e-11: generator) can move it, 2 sum|W| dmax e."""
-    f = cs.f[:, None, :] if cs.f.ndim == 2 else cs.f
+    (1e-11: generator) can move it, 2 sum|W| dmax e.  data [B|-, N + 1, n]: column t against column t of it, in place of the target."""
+    f = data if data is not None else (cs.f[:, None, :] if cs.f.ndim == 2 else cs.f)
     dmax = np.abs(tr["xs"] - f).max()
     w = np.abs(cs.W).sum()
     return 1e-12 * max(1.0, w * dmax ** 2) + 2 * w * dmax * _state_bound(cs) * max(1.0, np.abs(tr["xs"]).max())
@@ -365,3 +368,72 @@ def test_a_member_that_is_not_finite_leaves_the_others_alone(cell):
         clean = m4q.plant_rollout_multi_batch(cs.x0, cs.us, cs.op0, cs.ops, cs.ts, cs.W, cs.f, cs.kind, figure=figure)
         out = m4q.plant_rollout_multi_batch(cs.x0, us, cs.op0, cs.ops, cs.ts, cs.W, cs.f, cs.kind, figure=figure)
         assert _bits(out["J"][:, others], clean["J"][:, others]) and np.isnan(out["J"][:, BAD]).all()
+
+
+# ---------------------------------------------------------------- the parameter gradient
+PAIRS = sd.all_param_pairs()
+PAIR_IDS = [sd.pair_id(*k) for k in PAIRS]
+
+
+def _param_s_note(pr):
+    s = pr.s()["param_block"]
+    return "%s; param_block s per member (max over t) %s, member 0 along t %s" % (_s_note(pr.cs), s.max(axis=1).tolist(), s[0].tolist())
+
+
+def _column_figures(pr):
+    """q [B, N + 1]: column t of plant_rollout_batch's figure against column t of the data."""
+    cs = pr.cs
+    return np.stack([_rollout(cs, (cs.x0, cs.us, cs.op0, cs.ops, cs.u_scale, pr.data[..., t, :]), keep="none", figure="all")["q"][:, t]
+                     for t in range(cs.N + 1)], axis=1)
+
+
+@pytest.mark.parametrize("key", PAIRS, ids=PAIR_IDS)
+def test_plant_parameter_gradient(key):
+    pr = sd.param_case(*key)
+    cs = pr.cs
+    tr = sd.param_truth(pr)
+    args, kw = pr.args()
+    ref = m4q.plant_param_grad_reference(*args, **kw)
+    out = m4q.plant_rollout_param_grad_batch(*args, **kw)
+    assert set(out) == set(tr)
+    for name in sorted(set(tr) - {"J"}):
+        err = rel(out[name], tr[name])
+        print("%s %s: device %.2e, definition %.2e, over max(1, max|ref|), max|ref| = %.3e" % (pr.id, name, err, rel(ref[name], tr[name]),
+                                                                                             np.abs(tr[name]).max()))
+        assert out[name].shape == tr[name].shape and np.isfinite(out[name]).all()
+        assert err <= TOL
+    cw = pr.weights()
+    err_J, Jb = np.abs(out["J"] - tr["J"]).max(), cw.sum() * _figure_bound(cs, sd.truth(cs), pr.data)
+    print("%s J: max|dJ| %.2e, definition %.2e, bound %.2e, max|J| = %.3e; %s"
+          % (pr.id, err_J, np.abs(ref["J"] - tr["J"]).max(), Jb, np.abs(tr["J"]).max(), _param_s_note(pr)))
+    assert np.isfinite(out["J"]).all() and err_J <= Jb
+    # J is the ordered sum of the rollout's own figures, weighted, each product rounded before it is added
+    q = _column_figures(pr)
+    J = np.zeros(cs.B)
+    for t in range(cs.N + 1):
+        if cw[t] != 0.0:
+            J = J + cw[t] * q[:, t]
+    assert _bits(out["J"], J)
+    # the quiet member alone: the same bits - with the gains in the shared layout its block squares and its forward step does not
+    for b in cs.quiet:
+        a_args, a_kw = pr.alone(b)
+        alone = m4q.plant_rollout_param_grad_batch(*a_args, **a_kw)
+        assert all(_bits(alone[name][0], out[name][b]) for name in out)
+
+
+@pytest.mark.parametrize("cell", sd.PARAM_CELLS)
+def test_a_member_that_is_not_finite_leaves_the_others_gradients_alone(cell):
+    """Per layout, B = 5, N = 6, the cell's last direction set.  Member BAD's control at t = 1 is NaN: its J and its gradients are
+    NaN, every other member's outputs are the clean run's bits."""
+    pr = sd.param_case(cell, "per", 5, 6, *sd.param_sets(cell)[-1])
+    cs = pr.cs
+    args, kw = pr.args()
+    us = cs.us.copy()
+    us[BAD, 1, 0] = np.nan
+    others = [b for b in range(cs.B) if b != BAD]
+    clean = m4q.plant_rollout_param_grad_batch(*args, **kw)
+    out = m4q.plant_rollout_param_grad_batch(args[0], us, *args[2:], **kw)
+    assert set(out) == ({"J", "grad_theta", "grad_scale"} if pr.sg else {"J", "grad_theta"})
+    for name in out:
+        assert np.isfinite(clean[name]).all() and _bits(out[name][others], clean[name][others]), name
+        assert np.isnan(out[name][BAD]).all(), name

@@ -1,12 +1,15 @@
 """CPU checks of the plant-parameter gradient and of the calibration (mpc4quantum_amd/plant_param.py): the NumPy / SciPy definition
 against central differences of its own J and against an independent forward chain, the exact identity with the control gradient,
 the fit on noise-free data from perturbed plants, and every ValueError of the Python layer before the library is touched."""
+import os
+
 import numpy as np
 import pytest
 
 import mpc4quantum_amd as m4q
 from mpc4quantum_amd import _lib, plant_param
 from tests import grad_cases as gc
+from tests import kernel_variants as kv
 from tests import plant_param_cases as pc
 from tests.test_grad_host import FD_BOUND, H_FD        # the same differencing of the same kind of objective: the same step and bound
 
@@ -93,6 +96,68 @@ def test_direction_of_a_control_operator_is_the_control_gradient(name):
     assert np.abs(par["grad_theta"] - want).max() <= 1e-12 * scale and np.abs(want).max() > 1e-3
     if "grad_scale" in par:
         assert np.abs(par["grad_scale"] - ctl["grad_scale"]).max() <= 1e-12 * max(1.0, np.abs(ctl["grad_scale"]).max())
+
+
+# ---------------------------------------------------------------- the direction-count matrix
+def test_param_rule_lines_read_as_mirrored():
+    """kernel_variants.param_cells() / param_waves() against the lines of m4q_kernels.hip they were written from."""
+    with open(os.path.join(kv.CSRC, "m4q_kernels.hip")) as fh:
+        k = fh.read()
+    for line in ("  if constexpr ((1 + PT) * D > 16) {\n    return UNBUILT;\n",
+                 "    return launch_param_pt<PLANT, PT + 1>(a, p_tot, s);\n",
+                 "    const auto go = [&](auto plant) { return launch_param_pt<decltype(plant)::value, 1>(a, p_tot, s); };\n",
+                 "constexpr int param_waves() { return (1 + PT) * (PLANT == PLANT_PROCESS ? DQ : DD) > 6 ? 1 : WAVES; }\n",
+                 "constexpr int WAVES = NX <= 9 ? 2 : 1;\n"):
+        assert k.count(line) == 1, line
+    assert k.count("#if !defined(M4Q_NO_AUX) && M4Q_ORDER == 1\n") == 2                  # the kernel; its launcher
+    assert k.count("  constexpr int D = PLANT == PLANT_PROCESS ? DQ : DD;\n") >= 2
+    body = k[k.index("static int launch_param_by_plant("):k.index("static int launch_plant_param_grad(")]
+    assert body.count("  if constexpr (!SQUARE) {\n    return UNBUILT;\n") == 1
+    assert body.count("    if (a.roll.kind == PLANT_HAMILTONIAN) return go(ic<PLANT_HAMILTONIAN>{});\n") == 1
+    assert body.count("      if constexpr (QUARTIC) return go(ic<PLANT_PROCESS>{});\n      else return UNBUILT;\n") == 1
+
+
+def test_param_cells_are_the_built_instances():
+    H, P = kv.HAMILTONIAN, kv.PROCESS
+    want = [(4, 1, H, 7), (4, 2, H, 7), (9, 2, H, 4), (16, 1, H, 3), (16, 3, H, 3), (16, 1, P, 7), (16, 3, P, 7)]
+    cells = kv.param_cells()
+    assert cells == [(nx, nu, kind, pt) for nx, nu, kind, top in want for pt in range(1, top + 1)]
+    assert len(cells) == 38 == len(set(cells)) and 14 + 4 + 6 + 14 == 38
+    for nx, nu, kind, top in want:
+        d = kv.param_dim(nx, kind)
+        assert plant_param.max_directions(d) == top and (1 + top) * d <= 16 < (2 + top) * d
+        assert gc.plant_case(pc.cell_name(nx, nu, kind)).d == d and pc.p_max(pc.cell_name(nx, nu, kind)) == top
+    # the occupancy switch: one wave per SIMD past 6 columns - from PT = 3 at d = 2, from PT = 2 at d = 3, always at d = 4
+    assert [kv.param_waves(4, H, pt) for pt in range(1, 8)] == [2, 2, 1, 1, 1, 1, 1]
+    assert [kv.param_waves(9, H, pt) for pt in range(1, 5)] == [2, 1, 1, 1]
+    assert {kv.param_waves(16, kind, pt) for kind in (H, P) for pt in range(1, 4)} == {1}
+    # the matrix runs every cell at both splits, in both layouts
+    cases = pc.matrix_cases()
+    assert {(name, pt) for name, pt, p, sg, v in cases} == {(pc.cell_name(nx, nu, kind), pt) for nx, nu, kind, pt in cells}
+    assert len(cases) == 2 * (13 + 12 + 6 + 5 + 3 + 13 + 11) == len({pc.matrix_id(c) for c in cases})
+    for name, pt, p, sg, v in cases:
+        m = gc.plant_case(name).m
+        assert p >= 1 and p + (m if sg else 0) == pt
+    assert not [1 for name, pt, p, sg, v in cases if name == "16-3" and sg]                # (d = 4, m = 3: no room for the gains)
+
+
+MATRIX = pc.matrix_cases()
+
+
+@pytest.mark.parametrize("case", MATRIX, ids=[pc.matrix_id(c) for c in MATRIX])
+def test_matrix_cases_tell_their_directions_apart(case):
+    """On the definition alone: every column of [grad_theta, grad_scale] is non-trivial (max_b |g[:, j]| > 1e-3) and no two columns
+    lie within 1e-6 max|ref| of each other - a swapped or repeated direction, or a gain stored into a theta slot, is far outside
+    the device's bound of 1e-10 max(1, max|ref|)."""
+    c, args, kw = pc.matrix_inputs(case)
+    name, pt, p, sg, variant = case
+    ref = m4q.plant_param_grad_reference(*args, scale_grad=sg, **kw)
+    assert ref["grad_theta"].shape == (pc.MATRIX_B, p) and (not sg or ref["grad_scale"].shape == (pc.MATRIX_B, c.m))
+    small, near = pc.columns(ref)
+    print("%s: smallest column maximum %.3e, nearest two columns %.3e max|ref|" % (pc.matrix_id(case), small, near))
+    assert small > 1e-3 and near > 1e-6
+    assert all(args[4][..., j, :, :].any() for j in range(p))
+    assert set(pc.MATRIX_RESEED) <= {pc.matrix_id(c) for c in MATRIX}
 
 
 # ---------------------------------------------------------------- the fit

@@ -2,7 +2,9 @@
 the preconditions that make the cases worth running (a quiet member beside one that squares three times or more, s changing along
 the horizon, no norm where rounding could move s); the stored truth (tests/golden/strong_drive_truth.npz) against a recomputation
 with mpmath; and the project's fp64 definitions against that truth at ONE TENTH of the bound each family's GPU test holds the
-device to (1e-12 Hamiltonian / process states, 1e-11 generator states, 1e-10 max(1, max|ref|) gradients and linearisation)."""
+device to (1e-12 Hamiltonian / process states, 1e-11 generator states, 1e-10 max(1, max|ref|) gradients and linearisation).  The parameter
+gradient runs on the same cases (sd.ParamCase): its own preconditions on the (1 + p_tot) d block of param_block_expm, its truth
+(tests/golden/strong_drive_param_truth.npz) and its definition against that truth, at the end of the file."""
 import importlib.util
 import math
 import os
@@ -15,6 +17,7 @@ from mpc4quantum_amd import _lib
 from oracle import m4q_oracle as orc
 from tests import grad_cases as gc
 from tests import kernel_variants as kv
+from tests import plant_param_cases as pc
 from tests import strong_drive_cases as sd
 
 CASES = sd.all_cases()
@@ -188,3 +191,111 @@ def test_the_multi_rollout_definition_against_the_truth(key, figure):
     want = tr["q"][:, cs.N] if figure == "last" else tr["J_sum"]
     print("%s %s: J %.2e (max %.3e)" % (cs.id, figure, rel(ref["J"][:, 0], want), np.abs(want).max()))
     assert rel(ref["J"][:, 0], want) <= 1e-11
+
+
+# ---------------------------------------------------------------- the parameter gradient
+PAIRS = sd.all_param_pairs()
+PAIR_IDS = [sd.pair_id(*k) for k in PAIRS]
+
+
+def test_the_parameter_cells_and_sets():
+    assert set(sd.PARAM_CELLS) == set(sd.QP_CELLS) and len(sd.PARAM_CELLS) == 7
+    names = {pc.cell_name(nx, nu, kind) for nx, nu, kind, pt in kv.param_cells()}
+    assert names == set(sd.PARAM_CELLS)                              # (16, 2) is plant-only: the C entry refuses it
+    assert len(PAIRS) == 65 == len(set(PAIR_IDS)) and sd.param_sets("16-3") == [(3, False)]
+    assert sd.param_sets("4-1") == [(7, False), (6, True)] and sd.param_sets("16-3-process") == [(7, False), (4, True)]
+    assert set(sd.PARAM_RESEED) <= set(PAIR_IDS)
+
+
+@pytest.mark.parametrize("key", PAIRS, ids=PAIR_IDS)
+def test_parameter_gradient_preconditions(key):
+    """The (1 + p_tot) d block of param_block_expm squares where the forward exponent does, and more.  The purpose of the sets with
+    the gains in the shared layout: the quiet member's forward exponent stays at s = 0 - its u_scale is small - while its block
+    squares, because the gain directions carry the UNSCALED strong control u[t][k]: s_block > s_forward inside one wavefront, the
+    direction far larger than the exponent."""
+    pr = sd.param_case(*key)
+    cs = pr.cs
+    s, norms = pr.s(), pr.norms()
+    a, f = s["param_block"], s["forward"]
+    print("%s: forward s =\n%s\nparam_block s =\n%s" % (pr.id, f, a))
+    assert set(s) == {"forward", "param_block"} and a.shape == f.shape == (cs.B, cs.N)
+    assert pr.param_block(0, 0).shape == ((1 + pr.p_tot) * cs.d,) * 2 and (1 + pr.p_tot) * cs.d <= 16
+    assert a[cs.driven].max() >= 3 and (cs.B == 1 or a[:4].max() >= 3)         # (in the first quad, beside the quiet one)
+    if cs.N == 6:
+        for b in cs.driven:
+            assert len(set(a[b])) >= 2, (b, a[b])                    # s changes along the horizon
+    assert (a >= f).all()
+    assert min(sd.octave_margin(x) for v in norms.values() for x in v.reshape(-1)) > 1e-6
+    for b in cs.quiet:
+        assert (f[b] == 0).all()
+        if pr.sg and not cs.per:
+            assert a[b].max() >= 1
+        else:
+            assert (a[b] == 0).all()
+    assert np.array_equal(f, cs.s()["forward"])
+
+
+def test_the_parameter_block_is_the_definitions_own():
+    """ParamCase.param_block is the matrix grad._block_expm exponentiates in plant_param._param_member."""
+    from scipy.linalg import expm
+    from mpc4quantum_amd.grad import _block_expm
+    for key in (("4-2", "shared", 5, 6, 5, True), ("9-2", "per", 5, 6, 4, False)):
+        pr = sd.param_case(*key)
+        d = pr.cs.d
+        X, _ = pr.cs.generator(sd.QUIET, 2)
+        U, dUs = _block_expm(X, pr.directions(sd.QUIET, 2))
+        F = expm(pr.param_block(sd.QUIET, 2))
+        assert len(dUs) == pr.p_tot and np.array_equal(F[:d, :d], U)
+        assert all(np.array_equal(F[:d, (1 + e) * d:(2 + e) * d], dUs[e]) for e in range(pr.p_tot))
+
+
+
+def _param_generator_module():
+    spec = importlib.util.spec_from_file_location("make_golden_strong_drive_param", os.path.join(os.path.dirname(sd.TRUTH_FILE),
+                                                                                                  "make_golden_strong_drive_param.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_every_pair_has_its_truth():
+    for key in PAIRS:
+        pr = sd.param_case(*key)
+        tr = sd.param_truth(pr)
+        assert set(tr) == ({"J", "grad_theta", "grad_scale"} if pr.sg else {"J", "grad_theta"}), pr.id
+        assert tr["J"].shape == (pr.cs.B,) and tr["grad_theta"].shape == (pr.cs.B, pr.p) and all(np.isfinite(a).all() for a in tr.values())
+        assert not pr.sg or tr["grad_scale"].shape == (pr.cs.B, pr.cs.m)
+        for name in set(tr) - {"J"}:
+            assert np.all(np.abs(tr[name]).max(axis=0) > 1e-3), (pr.id, name)       # no column is trivial
+    assert os.path.getsize(sd.PARAM_TRUTH_FILE) < 1 << 20
+
+
+# (the five runs take five times as long as the recomputation of strong_drive_truth.npz above - 1 + p_tot exponentials per member
+# and step - and the two B = 5, N = 6 runs are most of it: the three short runs are recomputed, both layouts among them; the
+# definition is held to every stored pair below)
+REGEN_RUNS = [("shared", 5, 1), ("per", 1, 1), ("shared", 1, 6)]
+
+
+@pytest.mark.parametrize("cell", ["4-1", "16-1-process"])
+def test_the_parameter_fixture_regenerates_bit_for_bit(cell):
+    mg = _param_generator_module()
+    for variant, B, N in REGEN_RUNS:
+        for p, sg in sd.param_sets(cell):
+            pr = sd.param_case(cell, variant, B, N, p, sg)
+            again, stored = mg.compute(pr), sd.param_truth(pr)
+            assert set(again) == set(stored)
+            for field in stored:
+                a, b = np.ascontiguousarray(again[field]), stored[field]
+                assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes(), (pr.id, field)
+
+
+@pytest.mark.parametrize("key", PAIRS, ids=PAIR_IDS)
+def test_the_parameter_gradient_definition_against_the_truth(key):
+    pr = sd.param_case(*key)
+    tr = sd.param_truth(pr)
+    args, kw = pr.args()
+    ref = m4q.plant_param_grad_reference(*args, **kw)
+    assert set(ref) == set(tr)
+    errs = {name: rel(ref[name], tr[name]) for name in sorted(tr)}
+    print("%s: %s" % (pr.id, ", ".join("%s %.2e (max %.3e)" % (name, errs[name], np.abs(tr[name]).max()) for name in sorted(tr))))
+    assert max(errs.values()) <= 1e-11
