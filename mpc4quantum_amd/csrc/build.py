@@ -17,7 +17,7 @@ LIB = os.path.join(PKG, "libm4q_hip.so")
 LIB_GEN = os.path.join(PKG, "libm4q_hip_gen.so")   # the closed-loop kernels with the generator plant (m4q_kernels.hip: M4Q_VARIANT_GEN)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-command-line-argument"]
-HEADERS = ["m4q_device.h", "m4q_dpp_gen.h", "m4q_mpc.h", "m4q_tile.h", "m4q_tile3.h", "m4q_tile_opnd.h", "m4q_rollout_pair.h", "m4q_args.h", "m4q_paths.h", "m4q_lift.h", "m4q_noise.h", "m4q_fit.h", "m4q_fit_qr.h", "m4q_online.h", "m4q_grad.h", "m4q_plant_param.h", "m4q_plant_lin.h", "m4q_plant_qp.h", "m4q_plant_step.h", "m4q_rollout_multi.h", "m4q_model_multi.h", "m4q_robust_host.h", "m4q_feedback.h", "m4q_observe.h", "m4q_shapes.inc",
+HEADERS = ["m4q_device.h", "m4q_dpp_gen.h", "m4q_mpc.h", "m4q_tile.h", "m4q_tile3.h", "m4q_tile_opnd.h", "m4q_ls_table.h", "m4q_rollout_pair.h", "m4q_args.h", "m4q_paths.h", "m4q_lift.h", "m4q_noise.h", "m4q_fit.h", "m4q_fit_qr.h", "m4q_online.h", "m4q_grad.h", "m4q_plant_param.h", "m4q_plant_lin.h", "m4q_plant_qp.h", "m4q_plant_step.h", "m4q_rollout_multi.h", "m4q_model_multi.h", "m4q_robust_host.h", "m4q_feedback.h", "m4q_observe.h", "m4q_shapes.inc",
            os.path.join("..", "..", "include", "m4q.h")]
 STAMP = os.path.join(OBJ, "flags.stamp")       # the extra flags the objects in OBJ were built with
 

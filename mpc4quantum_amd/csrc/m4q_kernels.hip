@@ -179,12 +179,30 @@ template <class S, bool TL, bool EXACT> constexpr bool exact_tile() { return EXA
 template <int N, bool SG> constexpr int model_lds_elems() {
   return SG ? (ROWS + NP) * N * ModelPitch<N>::value : ROWS * model_elems<N>();
 }
+// everything but the line search's weight table, which lies behind it
 template <class S, bool TL = false, bool TILE = false, bool EXACT = false, bool SG = false>
-constexpr size_t mpc_lds_layout_bytes() {
+constexpr size_t mpc_lds_fixed_bytes() {
   constexpr int N = TL ? NX - 1 : NX;
   return sizeof(S) * (size_t)(model_lds_elems<N, SG>() + cost_elems<N>() + (cost_transposed<S, N, EXACT>() ? 2 * N * N : 0)) +
          sizeof(cplx) * (size_t)(ROWS * SCRATCH_ELEMS) + sizeof(double) * (size_t)WLS_DOUBLES + (size_t)stash_bytes<S, SG>() +
          (TILE ? (size_t)(TILE_LDS_BYTES + tile_opnd::bytes(NU, (N + 3) / 4)) : 0) + (exact_tile<S, TL, EXACT>() ? (size_t)(TILE_LDS_BYTES + TILE_PIN_LDS_BYTES) : 0);
+}
+// Which kernels read the node weights of the line search (line_search_tl_nodes, m4q_mpc.h: n - 1 even) from a table (m4q_ls_table.h)
+// that every workgroup builds at kernel entry: the clipped tile kernels, in what their eighth of a CU's LDS leaves - 47 nodes at
+// (9, 2, 1), horizons up to 46; a longer one runs without it.  Config 3 -0.9 % (profiles/r11_ab_experiments.txt).  The DPP and the exact
+// kernels keep the divisions (the exact ones carry 150-250 spilled registers and have not measured faster with such cuts: see
+// shift_in_update() below).
+template <bool TL, bool TILE, bool EXACT>
+constexpr bool ls_weights_tabled() {
+  return TL && TILE && !EXACT && (NX - 1) % 2 == 0;
+}
+template <class S, bool TL = false, bool TILE = false, bool EXACT = false, bool SG = false>
+constexpr int ls_table_nodes() {
+  return ls_weights_tabled<TL, TILE, EXACT>() ? ls_table::capacity(NX, (int)mpc_lds_fixed_bytes<S, TL, TILE, EXACT, SG>()) : 0;
+}
+template <class S, bool TL = false, bool TILE = false, bool EXACT = false, bool SG = false>
+constexpr size_t mpc_lds_layout_bytes() {
+  return mpc_lds_fixed_bytes<S, TL, TILE, EXACT, SG>() + (size_t)ls_table::bytes(NX, ls_table_nodes<S, TL, TILE, EXACT, SG>());
 }
 
 __device__ __forceinline__ int row_bcast_int(int v) { return __shfl(v, 0, 16); }
@@ -341,6 +359,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
   volatile M4Q_LDS int* tiw = (volatile M4Q_LDS int*)(tgb + ROWS * TILE_GB_DOUBLES);
   volatile M4Q_LDS double* tpin = (volatile M4Q_LDS double*)(tiw + ROWS * TILE_IO_WORDS);      // (exact_tile kernels only)
   volatile M4Q_LDS double* timg = (volatile M4Q_LDS double*)(tiw + ROWS * TILE_IO_WORDS);      // (TILE: the sweep's operand image, m4q_tile_opnd.h)
+  // the line search's weight table (m4q_ls_table.h), behind everything else
+  constexpr bool LS_TABLE = ls_weights_tabled<TL, TILE, EXACT>();
+  constexpr int LS_NODES = ls_table_nodes<S, TL, TILE, EXACT, SG>();
+  double* ldsT = nullptr;
+  if constexpr (LS_TABLE) ldsT = reinterpret_cast<double*>(m4q_lds_raw + mpc_lds_fixed_bytes<S, TL, TILE, EXACT, SG>());
   int T0, flags;
   bool ls_diag, two_phase;
   int n_pieces;                // work items per instance: head [step_begin, 2), then [2, XCUTS[0]), ... , [.., step_end)
@@ -384,6 +407,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
     ls_diag = a->Wls != nullptr;
     if (ls_diag) {
       for (int e = threadIdx.x; e < WLS_DOUBLES; e += 64) ldsW[e] = gld(a->Wls, e);
+      if constexpr (LS_TABLE) {
+        // (once per launch: the weights, the horizon and the slots are the same for every pass)
+        if (ls_table::tabled(T0, LS_NODES)) {
+          wave_sync();
+#pragma unroll 1
+          for (int e = threadIdx.x; e < (T0 + 1) * NX; e += 64) ldsT[e] = ls_table::entry(ldsW, NX, DD, T0, e / NX, e % NX);
+        }
+      }
     }
     // cut the run in two work items per instance when the launch covers both regimes
     two_phase = a->step_begin < 2 && a->step_end > 2;
@@ -910,7 +941,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG ? WAVES_S
       double al = 1.0, stepn = 0.0;
       if constexpr (TL) {
         // (the host selects TL only with diagonal costs)
-        if constexpr (NS % 2 == 0) line_search_tl_nodes<NX, NU, DD, TILE>(z, ldsW, ldsW + 2 * NX, ldsW + 4 * NX, jj, al, stepn);
+        if constexpr (NS % 2 == 0 && LS_TABLE) {
+          // (wave-uniform: the horizon is the launch's)
+          if (ls_table::tabled(T, LS_NODES)) line_search_tl_nodes<NX, NU, DD, TILE, true>(z, ldsW, ldsW + 2 * NX, ldsW + 4 * NX, jj, al, stepn, ldsT);
+          else line_search_tl_nodes<NX, NU, DD, TILE>(z, ldsW, ldsW + 2 * NX, ldsW + 4 * NX, jj, al, stepn);
+        } else if constexpr (NS % 2 == 0) line_search_tl_nodes<NX, NU, DD, TILE>(z, ldsW, ldsW + 2 * NX, ldsW + 4 * NX, jj, al, stepn);
         else line_search_tl<NX, NU, DD>(z, ldsW, ldsW + 2 * NX, ldsW + 4 * NX, jj, al, stepn);
       } else if (ls_diag) {
         line_search_diag<S, NX, NU, DD>(z, ldsW, ldsW + 2 * NX, ldsW + 4 * NX, jj, al, stepn);

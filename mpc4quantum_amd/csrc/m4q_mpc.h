@@ -9,6 +9,7 @@
 #include "m4q_args.h"
 #include "m4q_device.h"
 #include "m4q_rollout_pair.h"
+#include "m4q_ls_table.h"
 
 // Settled by A/B runs and no longer switches (the losing branches are gone from the source; their numbers are in
 // profiles/r02_ab_experiments.txt, r03_exact_qp_log.txt, r04_ab_experiments.txt):
@@ -2238,9 +2239,12 @@ __device__ __forceinline__ void line_search_tl(const ZView<NX - 1, NU>& z, const
 // Same terms, same weights; the sums run in a different order.  One node per lane and trip: two or three in flight at once cost
 // the kernel 78 / 219 spilled registers (32.2 / 37.4 ms against 29.95; profiles/r04_ab_experiments.txt).
 // TCONST: the target is the same at every node (the caller has seen QP_TARG_CONST): loaded once.
-template <int NX, int NU, int D, bool TCONST = false>
+// TAB: the weights of a node come from row t of the table `tab` that the kernel built at its entry (m4q_ls_table.h: W[t][slot], the
+// values this loop forms otherwise) - one address per node and one LDS read per slot, just before its use, instead of two divisions
+// of a Z slot, a block test and a pointer select for each of fifteen weights.  The caller has seen that the horizon fits the table.
+template <int NX, int NU, int D, bool TCONST = false, bool TAB = false>
 __device__ __forceinline__ void line_search_tl_nodes(const ZView<NX - 1, NU>& z, const double* wq, const double* wqf, const double* wr,
-                                                     int jj, double& alpha, double& step_norm) {
+                                                     int jj, double& alpha, double& step_norm, const double* tab = nullptr) {
   constexpr int NS = NX - 1;
   static_assert(NS % 2 == 0, "node-per-lane line search: 16-byte pairs");
   const int T = z.T;
@@ -2283,6 +2287,7 @@ __device__ __forceinline__ void line_search_tl_nodes(const ZView<NX - 1, NU>& z,
     for (int u = 0; u < ROUNDS; ++u) {
       const int t = t0 + 16 * u;
       const bool live = t <= T;
+      const double* row = TAB ? tab + ls_table::index(NX, ls_table::read_node(T, t), 0) : nullptr;
       // off-diagonal slots c = a D + b, a != b: traceless coordinate c - 1
 #pragma unroll
       for (int c = 1; c < NX; ++c) {
@@ -2290,7 +2295,9 @@ __device__ __forceinline__ void line_search_tl_nodes(const ZView<NX - 1, NU>& z,
         if (a == b) continue;
         const double e = g[u][c - 1] - tg[u][c - 1], d = o[u][c - 1] - g[u][c - 1];
         const int off = a > b ? nxt : 0;            // antisymmetric coordinates live in the imaginary halves
-        double w = 0.5 * (weight(c * (T + 1) + (live ? t : T) + off) + weight((b * D + a) * (T + 1) + (live ? t : T) + off));
+        double w;
+        if constexpr (TAB) w = row[ls_table::offdiag_slot(D, c)];
+        else w = 0.5 * (weight(c * (T + 1) + (live ? t : T) + off) + weight((b * D + a) * (T + 1) + (live ? t : T) + off));
         w = live ? w : 0.0;
         num = fma(w * e, d, num);
         den = fma(w * d, d, den);
@@ -2308,7 +2315,9 @@ __device__ __forceinline__ void line_search_tl_nodes(const ZView<NX - 1, NU>& z,
           ts = fma(cf, tg[u][l * D + l - 1], ts);
         }
         const double e = gs - ts, d = os - gs;
-        const double w = live ? weight((a * D + a) * (T + 1) + t) : 0.0;
+        double w;
+        if constexpr (TAB) { w = row[ls_table::diag_slot(NX, D, a)]; w = live ? w : 0.0; }
+        else w = live ? weight((a * D + a) * (T + 1) + t) : 0.0;
         num = fma(w * e, d, num);
         den = fma(w * d, d, den);
         nrm = fma(live ? d : 0.0, d, nrm);
